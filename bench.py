@@ -19,6 +19,11 @@ A step = one pass of the hot path (one mm_gemm_enqueue through the C ABI) over o
 already resident in HBM.  Timing = W untimed steps, barrier + synchronize, EXACTLY K steps,
 synchronize + barrier, MAX over ranks.  GOp/s = 1e-9 * 2*N*K*M / t as host/RunHardware.cpp:174-180.
 
+--dump-outputs DIR: after the timed region, what its last step computed -- C of the job -- goes to DIR as .npy (float32, or
+float64 for double): C.npy holds a fixed, seeded sample of C's rows (all of them when they fit, at most 48 MiB over all
+ranks), C_rows.npy the row numbers in the job (float64); rank r > 0 of an N > 1 run writes C_rank<r>*.npy.  The operands
+are generated on device from fixed seeds, so two builds run with the same arguments can be compared output for output.
+
 Besides the contract keys the line carries
   roofline     the dominant kernel against its roof, from HIP events on the launch stream
   cpu_baseline the reference's OWN hlslib CPU-simulation path (oracle/_ref, compiled from the
@@ -553,6 +558,8 @@ def main():
                          "strong_scaling_vs_scale_base = value / this.  Also read from MM_SCALE_BASE")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-extra", action="store_true", help="skip the workloads[] / weak_scaling extras")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write a seeded sample of the timed job's output C (its last step) to DIR as .npy")
     args = ap.parse_args()
 
     import torch
@@ -676,13 +683,29 @@ def main():
     hbm = HbmBusy(g, torch, dev, local_rank) if (world == 1 and not args.no_extra) else None
     hbm_box = {}
 
-    def run_job(n_total, seed_base):
+    def dump_outputs(c, row0):
+        """A fixed, seeded sample of C's rows (the last timed step's output) as float32 / float64 .npy files."""
+        import numpy as np
+        rows_here, cols = c.shape
+        out_dt = torch.float64 if c.dtype == torch.float64 else torch.float32
+        budget = (48 << 20) // world                        # bytes of C per rank: well under 64 MB in all
+        take = min(rows_here, max(1, budget // (cols * (8 if out_dt == torch.float64 else 4))))
+        idx = np.arange(rows_here) if take == rows_here else np.sort(np.random.default_rng(20240611).choice(rows_here, take, replace=False))
+        sample = c[torch.from_numpy(idx).to(c.device)].to(out_dt).cpu().numpy()
+        name = "C" if rank == 0 else f"C_rank{rank}"
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, name + ".npy"), sample)
+        np.save(os.path.join(args.dump_outputs, name + "_rows.npy"), (row0 + idx).astype(np.float64))
+
+    def run_job(n_total, seed_base, dump=False):
         """One timed region of the contract over the job of n_total rows; rank r owns row_slab(r)."""
         row0, rows = row_slab(n_total, world, rank)
         a, b, c = alloc_fill(g, torch, dev, local_rank, dtype, rows, k, m, seed_base + rank, 7)
         own_elapsed, launch_ms = timed_steps(g, torch, a, b, c, dtype, map_op, reduce_op, args.steps, args.warmup, barrier,
                                              PATHS.get(args.workload, 0))
         elapsed = max_over_ranks(own_elapsed)
+        if dump and rows:
+            dump_outputs(c, row0)
         if hbm is not None and world == 1:    # the DRAM-side figure of this kernel: an untimed leg of back-to-back launches, after the timed region
             hbm_box.clear()
             hbm_box["avg_launch_ms"] = round(sum(launch_ms) / len(launch_ms), 4)
@@ -709,7 +732,7 @@ def main():
     else:
         scaling = "weak"
         n_total = args.size * world
-    rows, elapsed, launch_ms, rows_all, per_rank = run_job(n_total, 1000)
+    rows, elapsed, launch_ms, rows_all, per_rank = run_job(n_total, 1000, dump=args.dump_outputs is not None)
 
     weak = None
     if world > 1 and scaling == "strong" and not args.no_extra:

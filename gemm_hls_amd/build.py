@@ -24,6 +24,8 @@ BIN = os.path.join(ROOT, "bin")
 LIB = os.path.join(HERE, "libmm_gemm_amd.so")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = "gfx950"
+# parallel compiles: MAX_JOBS when the environment sets one (a shared build host grants a share of its CPUs), else up to 16
+JOBS = int(os.environ.get("MAX_JOBS") or 0) or min(16, os.cpu_count() or 4)
 # --offload-compress: the device code objects are stored zstd-compressed (the generic-semiring families are 11 types x
 # 25 operator pairs of kernels; 7.3 MB -> ~2 MB), the runtime inflates them when the library is loaded
 COMMON = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function", "--offload-compress"]
@@ -70,9 +72,10 @@ LAB_REPLACES = {"lab_mfma_f32.hip": "mm_mfma_f32.o", "lab_mfma_f16.hip": "mm_mfm
 def build_lab(product_objs, headers, verbose=True):
     """tools/lab/libmm_gemm_amd_lab.so: the SAME C ABI with the four matrix-core translation units swapped for their
     lab editions (every schedule / ring depth / ablation the kernels went through, incl. the ones that skip work on
-    purpose).  Measurement tooling only (MM_LIB=lab for tools/sweep.py and friends); nothing in the product links it."""
-    if not os.path.isdir(LAB_DIR) or os.environ.get("MM_BUILD_LAB") != "1":
-        return   # measurement tooling: built on request only (MM_BUILD_LAB=1), not by every build()
+    purpose).  Measurement tooling only (MM_LIB=lab for tools/sweep.py and friends); nothing in the product links it,
+    but every build() compiles it, so that the tests of the lab library run on every checkout."""
+    if not os.path.isdir(LAB_DIR):
+        return
     os.makedirs(os.path.join(LAB_DIR, "_obj"), exist_ok=True)
     jobs, lab_objs = [], []
     for src, replaced in LAB_REPLACES.items():
@@ -80,7 +83,7 @@ def build_lab(product_objs, headers, verbose=True):
         lab_objs.append(obj)
         if newer(obj, [os.path.join(LAB_DIR, src)] + headers + [__file__]):
             jobs.append([HIPCC] + COMMON + ["-DMM_LAB_BUILD", "-c", os.path.join(LAB_DIR, src), "-o", obj])
-    with concurrent.futures.ThreadPoolExecutor(max_workers=os.cpu_count() or 4) as ex:
+    with concurrent.futures.ThreadPoolExecutor(max_workers=JOBS) as ex:
         list(ex.map(run, jobs))
     keep = [o for o in product_objs if os.path.basename(o) not in LAB_REPLACES.values()]
     if jobs or newer(LAB_LIB, keep + lab_objs):
@@ -102,7 +105,7 @@ def build(verbose=True):
         objs.append(obj)
         if newer(obj, [os.path.join(CSRC, src)] + headers + [__file__]):
             jobs.append([HIPCC] + COMMON + EXTRA.get(src, []) + ["-c", os.path.join(CSRC, src), "-o", obj])
-    with concurrent.futures.ThreadPoolExecutor(max_workers=os.cpu_count() or 4) as ex:
+    with concurrent.futures.ThreadPoolExecutor(max_workers=JOBS) as ex:
         list(ex.map(run, jobs))
     if jobs or newer(LIB, objs):   # also after an object was rebuilt by hand
         run([HIPCC, "--offload-arch=" + ARCH, "-shared", "-fPIC", "--offload-compress", "-o", LIB] + objs)
@@ -174,7 +177,7 @@ def build(verbose=True):
     shim("libmmkernel_double.so", defs("double", mp, rd))
     # the same library over the k-ordered kernel (MM_PATH_ORDERED): the bit-true "simulation" build.  The reference's own
     # test/TestSimulation.cpp compares half results EXACTLY with its binary16-accumulating Naive (its `half` is not
-    # std::is_floating_point, test/TestSimulation.cpp:80-85) -- tests/ref_hosts links it against this one
+    # std::is_floating_point, test/TestSimulation.cpp:80-85) -- oracle/build_ref_hosts.py links it against this one
     shim("libmmkernel_half_ordered.so", defs("half", mp, rd) + ["-DMM_DEFAULT_PATH=MM_PATH_ORDERED"])
     exe("TestSimulation.exe", "TestSimulation.cpp", defs(dt, mp, rd), shim="libmmkernel.so")
     exe(f"TestSimulation_static_float_{tag}.exe", "TestSimulation.cpp", defs(dt, mp, rd, static),
@@ -192,7 +195,7 @@ def build(verbose=True):
                 if newer(out, [os.path.join(probe_dir, f)]):
                     host_jobs.append([HIPCC, "--offload-arch=" + ARCH, "-O2", "-w",
                                       os.path.join(probe_dir, f), "-o", out])
-    with concurrent.futures.ThreadPoolExecutor(max_workers=os.cpu_count() or 4) as ex:
+    with concurrent.futures.ThreadPoolExecutor(max_workers=JOBS) as ex:
         list(ex.map(run, shim_jobs))      # the shims first: the CTest binaries link against them
         list(ex.map(run, host_jobs))
     if verbose and host_jobs:

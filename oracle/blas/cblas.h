@@ -2,7 +2,7 @@
  * (include/Utility.h:14-16,76-103: cblas_sgemm / cblas_dgemm, row-major), so that the reference's own hosts can be built
  * with -DMM_HAS_BLAS as its CMake does when it finds a BLAS (CMakeLists.txt:75-85) on an image that ships a CBLAS library
  * (/opt/conda/lib/libmkl_rt.so, LP64: 32-bit integers) but no header for it.  Declarations of a public, vendor-neutral
- * interface (netlib's cblas.h); nothing here is an implementation.  Used only by tests/ref_hosts/build_ref_hosts.py. */
+ * interface (netlib's cblas.h); nothing here is an implementation.  Used only by oracle/build_ref_hosts.py. */
 #ifndef MM_TEST_CBLAS_H
 #define MM_TEST_CBLAS_H
 #ifdef __cplusplus

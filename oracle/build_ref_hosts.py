@@ -2,9 +2,9 @@
 """TEST INFRASTRUCTURE: builds the reference's OWN host programs, unmodified and from where they lie under
 /root/reference, against THIS repository's library -- the strongest form of the drop-in claim (missing 1):
 
-    /root/reference/host/RunHardware.cpp        -> bin/ref_hosts/<config>/RunHardware.exe
-    /root/reference/test/TestSimulation.cpp     -> bin/ref_hosts/<config>/TestSimulation.exe
-    /root/reference/src/PrintSpecifications.cpp -> bin/ref_hosts/<config>/PrintSpecifications.exe
+    /root/reference/host/RunHardware.cpp        -> oracle/_ref/ref_hosts/<config>/RunHardware.exe
+    /root/reference/test/TestSimulation.cpp     -> oracle/_ref/ref_hosts/<config>/TestSimulation.exe
+    /root/reference/src/PrintSpecifications.cpp -> oracle/_ref/ref_hosts/<config>/PrintSpecifications.exe
 
 The only things added to the reference's compile line are one include path for the hlslib names its host uses
 (include/compat: hlslib::ocl::{Context, Program, Kernel, Buffer, ...} over include/mm_gemm.h; hlslib itself is an absent
@@ -14,7 +14,8 @@ the place of the reference's `mmkernel` target (CMakeLists.txt:138-150).  The re
 Vitis); this script re-does what it did for these three files: configure_file(include/Config.h.in -> Config.h)
 (CMakeLists.txt:136) and the definitions MM_DYNAMIC_SIZES / MM_TRANSPOSED_A / MM_HALF_PRECISION
 (CMakeLists.txt:96-112).  No reference source is copied into the repository: the generated Config.h and the binaries go
-to bin/ref_hosts/ (git-ignored; travels to the GPU box with the snapshot, where /root/reference does not exist).
+to oracle/_ref/ref_hosts/ (git-ignored, next to the reference kernel builds of oracle/build_ref.sh; they travel with
+oracle/_ref to the GPU box, where /root/reference does not exist).
 
 usage: build_ref_hosts.py            (all configurations below; a no-op with a note when /root/reference is absent)
 """
@@ -23,14 +24,15 @@ import re
 import subprocess
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+HERE = os.path.dirname(os.path.abspath(__file__))
+ROOT = os.path.dirname(HERE)
 REF = os.environ.get("MM_REFERENCE_DIR", "/root/reference")
-OUT = os.path.join(ROOT, "bin", "ref_hosts")
+OUT = os.path.join(HERE, "_ref", "ref_hosts")
 CXX = os.environ.get("MM_HOST_CXX", "/opt/rocm/lib/llvm/bin/clang++")   # half needs _Float16 on the host: clang, not g++ 11
 WIDTH = {"float": 4, "int": 4, "unsigned": 4, "double": 8, "long": 8, "half": 2, "short": 2, "uint8_t": 1, "char": 1}
 
 # The BLAS the reference's oracle is linked against in the *_blas configurations (its CMake: find_package(BLAS), -DMM_HAS_BLAS,
-# CMakeLists.txt:75-85,151,205).  This image ships MKL's single dynamic library without headers: tests/ref_hosts/blas/cblas.h
+# CMakeLists.txt:75-85,151,205).  This image ships MKL's single dynamic library without headers: oracle/blas/cblas.h
 # declares the two CBLAS entry points include/Utility.h:76-103 calls.
 SYSTEM_LIB_DIR = "/usr/lib/x86_64-linux-gnu"
 BLAS_LIBRARY = os.environ.get("MM_BLAS_LIBRARY", "/opt/conda/lib/libmkl_rt.so")
@@ -89,7 +91,7 @@ def run(cmd):
 def build(verbose=True):
     if not os.path.isdir(os.path.join(REF, "host")):
         if verbose:
-            print(f"build_ref_hosts: {REF} not present (GPU box?) - using prebuilt bin/ref_hosts if any")
+            print(f"build_ref_hosts: {REF} not present (GPU box?) - using prebuilt oracle/_ref/ref_hosts if any")
         return []
     lib_dir = os.path.join(ROOT, "gemm_hls_amd")
     built = []
@@ -103,14 +105,14 @@ def build(verbose=True):
         flags += ["-DMM_TRANSPOSED_A"] if transposed else []
         flags += ["-DMM_HALF_PRECISION"] if dtype == "half" else []
         flags += ["-DMM_HALF_CONTRACT_REFERENCE"] if name == "half_reference_contract" else []
-        rpath = "-Wl,-rpath,$ORIGIN/../../../gemm_hls_amd:$ORIGIN/../.."
+        rpath = "-Wl,-rpath,$ORIGIN/../../../../gemm_hls_amd:$ORIGIN/../../../../bin"
         device = ["-L" + lib_dir, "-lmm_gemm_amd", rpath]
         if name.endswith("_blas"):
             if not os.path.exists(BLAS_LIBRARY):
                 if verbose:
                     print(f"build_ref_hosts: {BLAS_LIBRARY} not found - skipping {name} (set MM_BLAS_LIBRARY)")
                 continue
-            flags += ["-DMM_HAS_BLAS", "-I" + os.path.join(ROOT, "tests", "ref_hosts", "blas")]
+            flags += ["-DMM_HAS_BLAS", "-I" + os.path.join(HERE, "blas")]
             # the BLAS's directory goes LAST on the run path, behind the system's library directory: /opt/conda/lib also holds an
             # older libstdc++ than the one libmm_gemm_amd.so was linked against, which must not be the one that gets loaded
             device += [BLAS_LIBRARY, "-Wl,--disable-new-dtags", "-Wl,-rpath," + SYSTEM_LIB_DIR + ":" + os.path.dirname(BLAS_LIBRARY)]

@@ -19,6 +19,8 @@ NP_DTYPES = {"float": np.float32, "double": np.float64, "half": np.float16, "int
              "unsigned": np.uint32, "long": np.int64, "unsigned long": np.uint64}
 
 _lib = None
+# the host's share of CPUs when the environment names one (OMP_NUM_THREADS), else all of them
+_THREADS = int(os.environ.get("OMP_NUM_THREADS") or 0) or os.cpu_count() or 1
 
 
 def build():
@@ -76,7 +78,7 @@ def naive(dtype, map_op, reduce_op, a, b, transposed_a=False, threads=None, wide
     c = np.empty((n, m), dtype=NP_DTYPES[dtype])
     fn = lib().mm_oracle_naive_wide if wide_half else lib().mm_oracle_naive
     rc = fn(DTYPES[dtype], OPS[map_op], OPS[reduce_op], int(transposed_a), _ptr(a), _ptr(b), _ptr(c),
-            n, k, m, threads or (os.cpu_count() or 1))
+            n, k, m, threads or _THREADS)
     assert rc == 0
     return c
 

@@ -243,12 +243,20 @@ def test_empty_and_degenerate_problems_at_every_entry_point():
 
 # ---- multi-GPU ------------------------------------------------------------------------------------
 def test_multi_device_ragged_split_is_bit_identical_to_one_device():
-    """Runs wherever >= 2 GPUs are visible (the driver's 8-GPU node; skipped on the 1-GPU box):
-    2 and ALL devices, N not divisible by the device count, against the one-device bits."""
+    """2 and ALL devices, N not divisible by the device count, against the one-device bits.  On a box with one GPU, "all"
+    is the 8 logical devices of md_virtual_devices (tests/test_gpu_multi_device.py), dealt out over the one physical GPU."""
     import torch
     have = torch.cuda.device_count()
     if have < 2:
-        pytest.skip("needs at least 2 GPUs")
+        g.set_tuning("md_virtual_devices", 8)
+        have = 8
+    try:
+        _ragged_split_vs_one_device(have)
+    finally:
+        g.set_tuning("md_virtual_devices", -1)
+
+
+def _ragged_split_vs_one_device(have):
     n, k, m = 2500 + 13, 1024, 1040
     rng = np.random.default_rng(5)
     a = rng.uniform(1, 10, size=(n, k)).astype(np.float32)
@@ -308,6 +316,32 @@ def test_bench_gpus_2_launched_plainly_spawns_its_own_ranks():
     assert out["config"]["rows_per_gpu"] == [3072, 2928]
 
 
+def test_bench_dump_outputs_writes_the_timed_jobs_result(tmp_path):
+    """`bench.py --dump-outputs DIR`: after exactly --steps timed steps, a seeded sample of the job's C (4096 x 4096 float:
+    64 MiB, more than the dump's budget, so sampled) with its row numbers -- equal, bit for bit, to the same call on the same
+    seeded device-generated operands made here."""
+    import torch
+    out_dir = tmp_path / "dump"
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--size", "4096",
+           "--no-extra", "--no-cpu-baseline", "--dump-outputs", str(out_dir)]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    out = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+    assert out["steps"] == 3 and out["ms_per_step"] > 0
+    c = np.load(out_dir / "C.npy")
+    rows = np.load(out_dir / "C_rows.npy")
+    assert c.dtype == np.float32 and rows.dtype == np.float64 and c.shape == (len(rows), 4096)
+    assert 0 < c.nbytes + rows.nbytes <= 64 << 20 and len(rows) < 4096
+    assert np.all(np.diff(rows) > 0) and rows[0] >= 0 and rows[-1] < 4096
+    dev = torch.device("cuda:0")
+    a = torch.empty((4096, 4096), device=dev)
+    b = torch.empty((4096, 4096), device=dev)
+    g._check(g.lib().mm_fill_device(0, g.DTYPES["float"], a.data_ptr(), a.numel(), 1000))   # bench.py's seeds of the job
+    g._check(g.lib().mm_fill_device(0, g.DTYPES["float"], b.data_ptr(), b.numel(), 7))
+    want = g.matmul(a, b)[torch.from_numpy(rows.astype(np.int64)).to(dev)].cpu().numpy()
+    assert np.array_equal(c, want)
+
+
 def test_race_screen_of_the_hand_synchronised_kernels():
     """tools/soak.py: every DMA-ring kernel repeated under an uneven background load gives the same bits
     every time and equals an independently scheduled kernel of the same arithmetic (a few seconds)."""
@@ -364,11 +398,11 @@ def test_lab_variant_ids_are_not_in_the_product():
 
 
 def test_lab_library_runs_the_retired_schedules_and_gates_its_ablations():
-    """tools/lab/libmm_gemm_amd_lab.so (MM_LIB=lab for the measurement tools; built only by MM_BUILD_LAB=1 python
-    gemm_hls_amd/build.py): same C ABI, the lab editions of the matrix-core kernels.  Retired schedules still compute the
+    """tools/lab/libmm_gemm_amd_lab.so (MM_LIB=lab for the measurement tools; built by gemm_hls_amd/build.py
+    with the product): same C ABI, the lab editions of the matrix-core kernels.  Retired schedules still compute the
     product; ablations need MM_ABLATIONS=1."""
     if not os.path.exists(os.path.join(ROOT, "tools", "lab", "libmm_gemm_amd_lab.so")):
-        pytest.skip("the lab library is built on request only (MM_BUILD_LAB=1)")
+        pytest.skip("tools/lab/libmm_gemm_amd_lab.so not built (gemm_hls_amd/build.py builds it)")
     code = (
         "import os, sys, numpy as np\n"
         f"sys.path.insert(0, {os.path.join(ROOT, 'tools')!r})\n"
@@ -406,8 +440,6 @@ def test_enqueue_is_capturable_into_a_hip_graph(path_name, shape):
     import torch
     path = g.PATH_SPLIT if path_name == "split" else g.PATH_AUTO
     n, k, m = shape     # whole tiles (64 x 64 geometry twice) / split-K (8 chunks + the ordered reduction) / stream-K (ONE teams kernel, the last part to arrive gathers: Combine::LastArriver) under AUTO
-    if path_name == "split" and shape != (384, 256, 320):
-        pytest.skip("one shape is enough for the opt-in path")
     a, b = _oracle.fill("float", n, k, m)
     ta, tb = torch.from_numpy(a).cuda(), torch.from_numpy(b).cuda()
     if path_name == "auto":

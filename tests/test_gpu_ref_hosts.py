@@ -1,5 +1,5 @@
 """The reference's OWN host programs -- /root/reference/host/RunHardware.cpp, test/TestSimulation.cpp and
-src/PrintSpecifications.cpp, compiled UNMODIFIED from where they lie by tests/ref_hosts/build_ref_hosts.py against
+src/PrintSpecifications.cpp, compiled UNMODIFIED from where they lie by oracle/build_ref_hosts.py against
 include/compat (hlslib::ocl over include/mm_gemm.h) and this repository's libraries -- run on the MI355X.
 
 This is the drop-in claim in its strongest form: not a re-written runner that prints the same lines, but
@@ -7,7 +7,7 @@ the reference's callers themselves, generating the seeded inputs, driving Contex
 MakeKernel / ExecuteTask / CopyToHost (host/RunHardware.cpp:114-190) or calling MatrixMultiplicationKernel directly
 (test/TestSimulation.cpp:61-92), and verifying the device's result with THEIR reference implementation and THEIR
 tolerance rule (1e-3 relative for float / double, exact for integers and for half).  The binaries are built where
-/root/reference exists (build()) and travel with the snapshot; nothing here reads /root/reference at run time."""
+/root/reference exists (build()) into oracle/_ref/ref_hosts and travel with oracle/_ref; nothing here reads /root/reference at run time."""
 import os
 import re
 import subprocess
@@ -16,7 +16,7 @@ import sys
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HOSTS = os.path.join(ROOT, "bin", "ref_hosts")
+HOSTS = os.path.join(ROOT, "oracle", "_ref", "ref_hosts")
 STATIC = "float_static_528x512x560"
 # the reference's benchmark parser (scripts/build_manager.py:601)
 PERF = re.compile(r"([\d\.]+) seconds[^\d]+([\d\.]+) GOp/s")
@@ -25,7 +25,7 @@ PERF = re.compile(r"([\d\.]+) seconds[^\d]+([\d\.]+) GOp/s")
 def _exe(config, name):
     path = os.path.join(HOSTS, config, name)
     if not os.path.exists(path):
-        pytest.skip(f"{os.path.relpath(path, ROOT)} not built (tests/ref_hosts/build_ref_hosts.py needs /root/reference)")
+        pytest.skip(f"{os.path.relpath(path, ROOT)} not built (oracle/build_ref_hosts.py needs /root/reference)")
     return path
 
 
@@ -227,7 +227,7 @@ def test_reference_hosts_no_transposed_blas_build():
     """The one combination that is NOT built: -DMM_TRANSPOSED_A with -DMM_HAS_BLAS.  The reference's BLAS call passes
     lda = size_k with CblasTrans (include/Utility.h:86-87,99-100), which is the leading dimension of a K x N matrix only when
     N == K -- for any other shape its oracle reads the wrong elements.  Kept as a written-down skip, not a build."""
-    sys.path.insert(0, os.path.join(ROOT, "tests", "ref_hosts"))
+    sys.path.insert(0, os.path.join(ROOT, "oracle"))
     import build_ref_hosts
     assert not any(name.endswith("_blas") and cfg[3] for name, cfg in build_ref_hosts.CONFIGS.items())
 
