@@ -9,6 +9,8 @@
 #include <stdint.h>
 #include <stdlib.h>
 
+#include <type_traits>
+
 #include "../../include/mm_gemm.h"
 
 namespace mm {
@@ -44,13 +46,22 @@ MM_INT_LIMITS(int64_t, INT64_MIN, INT64_MAX)
 MM_INT_LIMITS(uint64_t, 0, UINT64_MAX)
 #undef MM_INT_LIMITS
 
+// Integer Add / Multiply wrap mod 2^width (include/mm_gemm.h): they are computed in an unsigned type at least as wide as
+// unsigned int, where wrapping is defined.  In T itself a signed overflow -- or a uint16_t product, promoted to int --
+// is undefined behaviour, and the compiler does exploit it: (Multiply, And) on int / long took products that wrap to 0
+// (INT_MIN * 2) for nonzero (tests/test_gpu_value_ranges.py).  Floating types: T.
+template <typename T, bool = std::is_integral<T>::value> struct WrapType { using type = T; };
+template <typename T> struct WrapType<T, true> { using type = decltype(0u + (typename std::make_unsigned<T>::type)0); };
+
 template <int OP, typename T> struct Op;
 template <typename T> struct Op<MM_OP_ADD, T> {
-  __device__ static __forceinline__ T apply(T a, T b) { return (T)(a + b); }
+  using W = typename WrapType<T>::type;
+  __device__ static __forceinline__ T apply(T a, T b) { return (T)((W)a + (W)b); }
   __host__ __device__ static constexpr T identity() { return (T)0; }
 };
 template <typename T> struct Op<MM_OP_MULTIPLY, T> {
-  __device__ static __forceinline__ T apply(T a, T b) { return (T)(a * b); }
+  using W = typename WrapType<T>::type;
+  __device__ static __forceinline__ T apply(T a, T b) { return (T)((W)a * (W)b); }
   __host__ __device__ static constexpr T identity() { return (T)1; }
 };
 template <typename T> struct Op<MM_OP_AND, T> {

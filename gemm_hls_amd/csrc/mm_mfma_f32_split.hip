@@ -1,6 +1,7 @@
 // fp32 (Multiply, Add) on the bf16 matrix cores: C = A x B with every fp32 operand split into three
 // bf16 planes, x = x1 + x2 + x3 (x1 = bf16(x), x2 = bf16(x - x1), x3 = bf16(x - x1 - x2); each
-// subtraction is exact in fp32, so the three planes carry all 24 significand bits), and the six
+// subtraction is exact in fp32, so the three planes carry all 24 significand bits of any |x| >= 2^-108; below that
+// x2 / x3 are bf16 subnormals, quantum 2^-133, and x is kept to within 2^-134 absolute: include/mm_gemm.h), and the six
 // products of weight >= 2^-16 kept:
 //     a*b ~= a1*b3 + a3*b1 + a2*b2 + a1*b2 + a2*b1 + a1*b1        (dropped: a2*b3 + a3*b2 + a3*b3 <= 2^-25 |a*b|)
 // Every bf16 x bf16 product is exact in the MFMA's fp32 datapath, so a product is represented to

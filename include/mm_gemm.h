@@ -50,7 +50,14 @@ typedef enum {
  * is THIS LIBRARY'S CHOICE (the mathematical identity).  The published hlslib is believed to seed Max with
  * numeric_limits<T>::min() -- for floating types the smallest POSITIVE value -- which differs from lowest()
  * only when every mapped value of an output is negative; on the reference's own inputs ([1,10]) both give
- * the same bits, which is all that parity is pinned on. */
+ * the same bits, which is all that parity is pinned on.
+ * Integer types: Add and Multiply wrap mod 2^width for EVERY integer type, signed ones included (two's complement, as
+ * the unsigned type of the same width computes them); Min / Max are typed compares (std::min / std::max); And gives 0 / 1.
+ * Floating-point Min / Max: MM_PATH_ORDERED is std::min / std::max to the letter (b < a ? b : a; NaN and signed-zero
+ * ties follow from that); MM_PATH_AUTO's register-tiled kernel uses IEEE minNum / maxNum instead (a NaN operand is
+ * dropped; which zero a (+0, -0) tie returns is unspecified) -- the same value for every pair of numbers.
+ * A Min reduction whose mapped values are all +inf (or NaN) returns max(), not inf: the identity max() is never
+ * replaced by a value that is not below it -- Naive's semantics (e.g. (Add, Min) over a row of A that is all +inf). */
 typedef enum {
   MM_OP_ADD = 0,
   MM_OP_MULTIPLY = 1,
@@ -72,15 +79,20 @@ typedef enum {
  *                    "ordered", fully predicated 64 x 64 tiles, for everything else ("ordered_variant"
  *                    = 0 forces it: the cross-check).
  *   MM_PATH_SPLIT    float (Multiply, Add) only, opt-in: fp32 operands split into three bf16
- *                    planes (all 24 significand bits), six bf16 matrix-core products per
- *                    element pair accumulated in fp32 -- each product good to ~2^-25, i.e. at
- *                    least as fine as an fp32 multiply; 1.7x the fp32 matrix-core peak.  Any
+ *                    planes (all 24 significand bits for magnitudes >= 2^-108), six bf16 matrix-core
+ *                    products per element pair accumulated in fp32 -- each product good to ~2^-25,
+ *                    i.e. at least as fine as an fp32 multiply; 1.7x the fp32 matrix-core peak.  Any
  *                    N, K, M and any element-aligned pointers; needs 6 bytes of stream-ordered
  *                    workspace per element of A and B (hipMallocAsync on the launch stream).
- *                    Inputs must be finite and below 2^127 in magnitude for the error bound
- *                    to hold (an inf/nan operand still gives non-finite results, but +inf may
- *                    become nan).  Any other configuration: MM_ERR_UNSUPPORTED.  RunHardware:
- *                    MM_PATH=split with "hw".  See mm_release_workspace(). */
+ *                    Error bound: |C - AB| <= 2^-19 (|A||B|) elementwise when every nonzero operand
+ *                    is finite and 2^-112 <= |x| < 2^127.  Below 2^-112 the second and third
+ *                    planes fall into bf16's subnormal range (quantum 2^-133) and lose bits: each
+ *                    operand is then represented to within 2^-134 ABSOLUTE, and the bound is
+ *                    2^-19 (|A||B|)_ij + 2^-134 (sum_k |a_ik| + sum_k |b_kj|) -- e.g. A ~ 2^-120
+ *                    next to B ~ 2^120 gives ~1e-5 normwise, fp32-subnormal A much more; the
+ *                    default fp32 path has no such limit.  An inf/nan operand still gives
+ *                    non-finite results, but +inf may become nan.  Any other configuration:
+ *                    MM_ERR_UNSUPPORTED.  RunHardware: MM_PATH=split with "hw".  See mm_release_workspace(). */
 typedef enum { MM_PATH_AUTO = 0, MM_PATH_ORDERED = 1, MM_PATH_SPLIT = 2 } mm_path_t;
 
 /* Layout of A: row-major N x K (default) or K x N == the reference's MM_TRANSPOSED_A

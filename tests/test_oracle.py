@@ -4,7 +4,7 @@
   * the committed outputs of the reference's OWN kernel (tests/golden/ref_*.npz, produced from
     /root/reference/kernel/*.cpp via oracle/_ref),
   * the reference's own kernel run live, when oracle/_ref is present,
-  * independent numpy arithmetic.
+  * independent numpy arithmetic (tests/_semiring_ref.py: all 275 configurations on full-range and edge-valued operands).
 """
 import glob
 import hashlib
@@ -15,6 +15,7 @@ import numpy as np
 import pytest
 
 import _oracle
+import _semiring_ref as sr
 
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
@@ -95,6 +96,35 @@ def test_naive_matches_numpy_semiring(dtype, ops):
         assert np.allclose(c, red, rtol=1e-5)
     else:
         assert np.array_equal(c, red.astype(npdt))  # modular wrap-around like C++ narrowing
+
+
+def _operand_sets(dtype, mp, rd, n, k, m, rng, transposed_a=False):
+    a_shape = (k, n) if transposed_a else (n, k)
+    axis = 1 if transposed_a else 0
+    if not sr.is_float(dtype):
+        return {"full_range": sr.int_operands(dtype, mp, rd, a_shape, (k, m), rng, a_row_axis=axis)}
+    return {"finite": sr.float_operands(dtype, mp, rd, a_shape, (k, m), rng, non_finite=False, a_row_axis=axis),
+            "non_finite": sr.float_operands(dtype, mp, rd, a_shape, (k, m), rng, non_finite=True, a_row_axis=axis)}
+
+
+def test_naive_equals_the_independent_reference_on_every_configuration():
+    """The C oracle's Naive and tests/_semiring_ref.py -- two restatements of include/Utility.h:18-42 written apart --
+    agree bit for bit (NaN payloads aside) on all 11 x 5 x 5 (dtype, map, reduce) configurations, on the operand sets the
+    device tests use: every bit pattern of the integer types with min / max / 0 / +-1 planted, floating operands of both
+    signs over most of the exponent range with +-0, subnormals, the extremes, +-inf and NaN planted."""
+    n, k, m = 23, 40, 29
+    checked = 0
+    for dtype, mp, rd in sr.CONFIGS:
+        rng = np.random.default_rng(checked)
+        for transposed_a in (False, True):
+            for name, (a, b) in _operand_sets(dtype, mp, rd, n, k, m, rng, transposed_a).items():
+                what = f"{dtype} ({mp}, {rd}) {name}{' K x N A' if transposed_a else ''} {n}x{k}x{m}"
+                want = sr.reference(dtype, mp, rd, a, b, transposed_a=transposed_a)
+                sr.assert_not_degenerate(want, mp, rd, what)
+                got = _oracle.naive(dtype, mp, rd, a, b, transposed_a=transposed_a, threads=2)
+                assert sr.same_bits(got, want), f"{what}: oracle != reference first at {sr.first_difference(got, want)}"
+        checked += 1
+    assert checked == 275
 
 
 def test_naive_transposed_a_indexing():
