@@ -24,7 +24,8 @@ EXPORTS = ["mm_init", "mm_alloc", "mm_free", "mm_copy_to_device", "mm_copy_to_ho
            "MatrixMultiplicationKernel", "mm_set_default_config", "mm_dtype_size",
            "mm_config_supported", "mm_kernel_name", "mm_kernel_info", "mm_last_error",
            "mm_gemm_host", "mm_tuning_set", "mm_tuning_get", "mm_release_workspace", "mm_device_pci_bus_id",
-           "mm_row_slab", "mm_gemm_multi_device_timed"]
+           "mm_row_slab", "mm_gemm_multi_device_timed", "mm_gemm_batched_enqueue", "mm_gemm_batched_launch",
+           "mm_kernel_name_batched"]
 
 
 class MMError(RuntimeError):
@@ -93,6 +94,10 @@ def lib():
         L.mm_release_workspace.argtypes = [i]
         L.mm_device_pci_bus_id.argtypes = [i, ctypes.c_char_p, i]
         L.mm_row_slab.argtypes = [cfgp, u, u, u, i, i, ctypes.POINTER(u), ctypes.POINTER(u)]
+        L.mm_gemm_batched_enqueue.argtypes = [vp, cfgp, vp, vp, vp, u, u, u, u, sz, sz, sz]
+        L.mm_gemm_batched_launch.argtypes = [i, cfgp, vp, vp, vp, u, u, u, u, sz, sz, sz, ctypes.POINTER(ctypes.c_double)]
+        L.mm_kernel_name_batched.argtypes = [cfgp, u, u, u, u]
+        L.mm_kernel_name_batched.restype = ctypes.c_char_p
         _lib = L
     return _lib
 
@@ -114,6 +119,10 @@ def device_count():
 
 def kernel_name(cfg, n, k, m):
     return lib().mm_kernel_name(ctypes.byref(cfg), n, k, m).decode()
+
+
+def kernel_name_batched(cfg, n, k, m, batch):
+    return lib().mm_kernel_name_batched(ctypes.byref(cfg), n, k, m, batch).decode()
 
 
 def set_tuning(name, value):
@@ -179,6 +188,61 @@ def matmul(a, b, dtype="float", map_op="Multiply", reduce_op="Add", path=PATH_AU
         stream = torch.cuda.current_stream(a.device).cuda_stream
         _check(lib().mm_gemm_enqueue(ctypes.c_void_p(stream), ctypes.byref(cfg), a.data_ptr(), b.data_ptr(),
                                      out.data_ptr(), n, k, m))
+    return out
+
+
+def _batched_operand(x, name, rows, cols):
+    """(batch or None, batch stride in elements) of a 2-D or 3-D operand whose matrices are dense row-major."""
+    if x.dim() == 2:
+        if tuple(x.shape) != (rows, cols):
+            raise MMError(f"{name} has shape {tuple(x.shape)}, expected {(rows, cols)}")
+        if not x.is_contiguous():
+            raise MMError(f"{name} must be a dense row-major matrix")
+        return None, 0
+    if x.dim() != 3 or tuple(x.shape[1:]) != (rows, cols):
+        raise MMError(f"{name} has shape {tuple(x.shape)}, expected (B, {rows}, {cols}) or {(rows, cols)}")
+    if (rows > 1 and x.stride(1) != cols) or (cols > 1 and x.stride(2) != 1):
+        raise MMError(f"each matrix of {name} must be dense row-major (strides {x.stride()})")
+    if x.stride(0) < 0:
+        raise MMError(f"{name} has a negative batch stride")
+    return x.shape[0], (0 if x.shape[0] == 1 else x.stride(0))
+
+
+def bmm(a, b, dtype="float", map_op="Multiply", reduce_op="Add", path=PATH_AUTO, transposed_a=False, out=None):
+    """Strided-batched C[e] = A[e] (map, reduce) B[e] on torch's current stream (mm_gemm_batched_enqueue).
+    a: (B, N, K) -- or (B, K, N) with transposed_a -- b: (B, K, M); either may be 2-D or expanded with batch stride 0
+    (one operand shared by the batch).  Each matrix must be dense row-major; the batch stride may be anything the C ABI
+    accepts.  out: (B, N, M) contiguous.  Asynchronous, like any torch op."""
+    import torch
+    if not (a.is_cuda and b.is_cuda):
+        raise MMError("bmm needs device tensors: there is no CPU path")
+    if a.device != b.device:
+        raise MMError(f"operands live on different devices: {a.device} and {b.device}")
+    tdt = torch_dtype(dtype)
+    if a.dtype != tdt or b.dtype != tdt:
+        raise MMError(f"operand dtypes {a.dtype}, {b.dtype} do not match Data_t={dtype} ({tdt})")
+    if a.dim() not in (2, 3) or b.dim() not in (2, 3):
+        raise MMError("bmm takes 2-D or 3-D operands")
+    k, m = b.shape[-2], b.shape[-1]
+    n = a.shape[-1] if transposed_a else a.shape[-2]
+    if (a.shape[-2] if transposed_a else a.shape[-1]) != k:
+        raise MMError(f"inner dimensions differ: A {tuple(a.shape)}{' (K x N)' if transposed_a else ''}, B {tuple(b.shape)}")
+    ba, sa = _batched_operand(a, "a", *((k, n) if transposed_a else (n, k)))
+    bb, sb = _batched_operand(b, "b", k, m)
+    batches = {x for x in (ba, bb) if x is not None and x != 1}
+    if len(batches) > 1:
+        raise MMError(f"batch sizes differ: {ba} and {bb}")
+    batch = batches.pop() if batches else 1
+    if out is None:
+        out = torch.empty((batch, n, m), dtype=tdt, device=a.device)
+    elif (tuple(out.shape) != (batch, n, m) or out.dtype != tdt or out.device != a.device or not out.is_contiguous()):
+        raise MMError(f"out must be a contiguous {tdt} tensor of shape {(batch, n, m)} on {a.device}; got "
+                      f"{tuple(out.shape)}, {out.dtype}, {out.device}, contiguous={out.is_contiguous()}")
+    cfg = make_config(dtype, map_op, reduce_op, path, transposed_a)
+    with torch.cuda.device(a.device):
+        stream = torch.cuda.current_stream(a.device).cuda_stream
+        _check(lib().mm_gemm_batched_enqueue(ctypes.c_void_p(stream), ctypes.byref(cfg), a.data_ptr(), b.data_ptr(),
+                                             out.data_ptr(), n, k, m, batch, sa, sb, n * m))
     return out
 
 

@@ -92,10 +92,10 @@ std::once_flag g_tuning_once;
 std::atomic<int> g_tuning[mm::TUNE_COUNT];
 const char *const kTuneName[mm::TUNE_COUNT] = {"f32_variant", "f64_variant", "f16_variant", "i8_variant", "band_rows",
                                                "valu_variant", "split_variant", "f32_splitk", "ablations", "debug_poison", "kxn_prepass_min_m",
-                                               "md_virtual_devices", "ordered_variant", "half_contract"};
+                                               "md_virtual_devices", "ordered_variant", "half_contract", "batch_chunk"};
 const char *const kTuneEnv[mm::TUNE_COUNT] = {"MM_F32_VARIANT", "MM_F64_VARIANT", "MM_F16_VARIANT", "MM_I8_VARIANT",
                                               "MM_BAND_ROWS", "MM_VALU_VARIANT", "MM_SPLIT_VARIANT", "MM_F32_SPLITK", "MM_ABLATIONS", "MM_DEBUG_POISON", "MM_KXN_PREPASS_MIN_M",
-                                              "MM_MD_VIRTUAL_DEVICES", "MM_ORDERED_VARIANT", "MM_HALF_CONTRACT"};
+                                              "MM_MD_VIRTUAL_DEVICES", "MM_ORDERED_VARIANT", "MM_HALF_CONTRACT", "MM_BATCH_CHUNK"};
 void tuning_init() {
   for (int i = 0; i < mm::TUNE_COUNT; ++i) {
     const char *e = getenv(kTuneEnv[i]);
@@ -211,6 +211,117 @@ int check_problem(const mm_config_t *cfg, const void *a, const void *b, void *c,
   if (k == 0) return fail(MM_ERR_BAD_ARGUMENT, "size_k must be positive");
   if (n && m && (!a || !b || !c)) return fail(MM_ERR_BAD_ARGUMENT, "null matrix pointer");
   return MM_OK;
+}
+
+// ---- strided batches (mm_gemm_batched_*) -----------------------------------------------------------------------------
+// The family a batched launch runs: the single launch's, each matrix-core family through its batched resolver (decided on
+// the whole batch), except where that family would need workspace (split-K planes, stream-K scratch, a K x N transposition
+// pre-pass): those shapes go to the family with the same contract -- fp32 (Multiply, Add) to its whole-tile geometries
+// (K x N A: the direct K x N kernel), half (Multiply, Add) to half_wide (f32 accumulation, one rounding: mfma_f16's
+// contract), the 8-bit products to the register-tiled VALU kernel (exact).  Pure arithmetic: no device is touched.
+Family choose_batched(const mm_config_t &cfg, const mm::Problem &p) {
+  const auto valu_or_ordered = [&] { return mm::valu_tile_serves(cfg, p) ? FAM_VALU_TILE : FAM_ORDERED; };
+  switch (Family f = choose(cfg, p)) {
+    case FAM_MFMA_F32:   // (a library built without the batched fp32 kernels -- tools/lab -- resolves none)
+      return mm::mfma_f32_batched_resolve(p, f32_variant()) >= 0 ? f : valu_or_ordered();
+    case FAM_MFMA_F64: return mm::mfma_f64_batched_resolve(p) >= 0 ? f : valu_or_ordered();
+    case FAM_MFMA_I8: return mm::mfma_i8_batched_resolve(p) >= 0 ? f : valu_or_ordered();
+    case FAM_MFMA_F16: return mm::mfma_f16_batched_resolve(p) >= 0 ? f : FAM_HALF_WIDE;
+    case FAM_F32_SPLIT: return FAM_NONE;   // MM_PATH_SPLIT needs workspace: not batched
+    default: return f;
+  }
+}
+
+// Every element meets the single launch's alignment rule: the fast families need each element's a, b and c 16-byte aligned.
+bool batch_aligned16(const mm::Problem &p, size_t es) {
+  const size_t strides = p.batch > 1 ? ((p.stride_a | p.stride_b | p.stride_c) * es) : 0;
+  return aligned16(p) && (strides & 15u) == 0;
+}
+
+// All argument checks of a batched call, before any device is touched.  *fam: the family that will run (FAM_NONE: an empty
+// batch, a no-op).
+int check_batched(const mm_config_t *cfg, const mm::Problem &p, Family *fam) {
+  if (!valid_cfg(cfg)) return fail(MM_ERR_BAD_ARGUMENT, "invalid mm_config_t");
+  if (p.k == 0) return fail(MM_ERR_BAD_ARGUMENT, "size_k must be positive");
+  if (cfg->path == MM_PATH_SPLIT) return fail(MM_ERR_UNSUPPORTED, "MM_PATH_SPLIT has no batched form (it needs workspace)");
+  *fam = FAM_NONE;
+  if (p.batch == 0 || p.n == 0 || p.m == 0) return MM_OK;   // nothing to write
+  if (!p.a || !p.b || !p.c) return fail(MM_ERR_BAD_ARGUMENT, "null matrix pointer");
+  if (p.batch > 1 && p.stride_c < (size_t)p.n * p.m)
+    return fail(MM_ERR_BAD_ARGUMENT, "stride_c %zu < N * M = %zu: the outputs of the batch would overlap", p.stride_c,
+                (size_t)p.n * p.m);
+  Family f = choose_batched(*cfg, p);
+  if (f == FAM_NONE) return fail(MM_ERR_UNSUPPORTED, "no batched kernel serves this configuration");
+  const bool aligned = batch_aligned16(p, mm_dtype_size(cfg->dtype));
+  if (f == FAM_ORDERED_TILE && !aligned) f = FAM_ORDERED;   // the k-ordered contract takes any element-aligned pointer
+  if (f != FAM_ORDERED && f != FAM_HALF_WIDE && !aligned)
+    return fail(MM_ERR_BAD_ARGUMENT, "every element's a, b and c must be 16-byte aligned for the fast path (bases %p, %p, %p; "
+                "strides %zu, %zu, %zu elements); use aligned strides or MM_PATH_ORDERED", p.a, p.b, p.c, p.stride_a,
+                p.stride_b, p.stride_c);
+  *fam = f;
+  return MM_OK;
+}
+
+// Elements per launch: the batch_chunk knob, and a grid of at most 2^22 workgroups (of at most 512 threads) -- counted in
+// 64 x 64 tiles, the smallest any family uses.  An element bigger than that runs alone, as a single launch would.
+unsigned batch_chunk(const mm::Problem &p) {
+  const unsigned long long tiles = (unsigned long long)((p.n + 63) / 64) * ((p.m + 63) / 64);
+  unsigned long long chunk = std::max(1ull, (1ull << 22) / tiles);
+  const int knob = mm::tuning(mm::TUNE_BATCH_CHUNK);
+  if (knob > 0) chunk = std::min<unsigned long long>(chunk, (unsigned)knob);
+  return (unsigned)std::min<unsigned long long>(chunk, p.batch);
+}
+
+// Launches the batch as consecutive launches of at most batch_chunk() elements on `s`.  The family and the fp32 geometry
+// are decided once, on the whole batch, so that an element's kernel does not depend on how the batch was chunked.
+int dispatch_batched(hipStream_t s, const mm_config_t &cfg, const mm::Problem &p, Family fam) {
+  if (p.batch == 0 || p.n == 0 || p.m == 0) return MM_OK;
+  const size_t es = mm_dtype_size(cfg.dtype);
+  const int kernel = fam == FAM_MFMA_F32 ? mm::mfma_f32_batched_resolve(p, f32_variant())
+                   : fam == FAM_MFMA_F64 ? mm::mfma_f64_batched_resolve(p)
+                   : fam == FAM_MFMA_F16 ? mm::mfma_f16_batched_resolve(p)
+                   : fam == FAM_MFMA_I8 ? mm::mfma_i8_batched_resolve(p) : -1;
+  const unsigned chunk = batch_chunk(p);
+  (void)hipGetLastError();   // a stale error of the application's own calls must not be reported as this launch's
+  for (unsigned e0 = 0; e0 < p.batch; e0 += chunk) {
+    mm::Problem q = p;
+    q.batch = std::min(chunk, p.batch - e0);
+    q.a = (const char *)p.a + (size_t)e0 * p.stride_a * es;
+    q.b = (const char *)p.b + (size_t)e0 * p.stride_b * es;
+    q.c = (char *)p.c + (size_t)e0 * p.stride_c * es;
+    int e;
+    switch (fam) {
+      case FAM_MFMA_F32: e = mm::launch_mfma_f32_batched(s, q, kernel); break;
+      case FAM_MFMA_F64: e = mm::launch_mfma_f64_batched(s, q, kernel); break;
+      case FAM_MFMA_F16: e = mm::launch_mfma_f16_batched(s, q, kernel); break;
+      case FAM_MFMA_I8: e = mm::launch_mfma_i8_batched(s, q, kernel); break;
+      case FAM_HALF_WIDE: e = mm::launch_half_wide_batched(s, q); break;
+      case FAM_VALU_TILE:
+        e = mm::launch_valu_tile_batched(s, cfg, q);
+        if (e == mm::kErrNotSupported) e = mm::launch_ordered_batched(s, cfg, q);
+        break;
+      case FAM_ORDERED_TILE:
+        e = mm::launch_valu_tile_exact_batched(s, cfg, q);
+        if (e == mm::kErrNotSupported) e = mm::launch_ordered_batched(s, cfg, q);
+        break;
+      default: e = mm::launch_ordered_batched(s, cfg, q); break;
+    }
+    if (e == mm::kErrNotSupported)
+      return fail(MM_ERR_UNSUPPORTED, "configuration (dtype %d, map %d, reduce %d) is not compiled into this library",
+                  (int)cfg.dtype, (int)cfg.map_op, (int)cfg.reduce_op);
+    if (e != 0) return hip_fail((hipError_t)e, "batched kernel launch");
+  }
+  return MM_OK;
+}
+
+mm::Problem batched_problem(const mm_config_t *cfg, const void *a, const void *b, void *c, unsigned n, unsigned k,
+                            unsigned m, unsigned batch, size_t stride_a, size_t stride_b, size_t stride_c) {
+  mm::Problem p{a, b, c, n, k, m, cfg && cfg->layout_a == MM_A_TRANSPOSED};
+  p.batch = batch;
+  p.stride_a = stride_a;
+  p.stride_b = stride_b;
+  p.stride_c = stride_c;
+  return p;
 }
 
 // hipEvent_t with a destructor: no exit path of the timed launch can leak one
@@ -427,6 +538,45 @@ int mm_gemm_launch(int device, const mm_config_t *cfg, const void *a, const void
   mm::Problem p{a, b, c, n, k, m, cfg->layout_a == MM_A_TRANSPOSED};
   MM_HIP(hipEventRecord(start.e, nullptr));
   rc = dispatch(nullptr, *cfg, p);
+  if (rc != MM_OK) return rc;
+  MM_HIP(hipEventRecord(stop.e, nullptr));
+  MM_HIP(hipEventSynchronize(stop.e));
+  if (elapsed_seconds) {
+    float ms = 0.f;
+    MM_HIP(hipEventElapsedTime(&ms, start.e, stop.e));
+    *elapsed_seconds = 1e-3 * (double)ms;
+  }
+  return MM_OK;
+}
+
+int mm_gemm_batched_enqueue(void *hip_stream, const mm_config_t *cfg, const void *a, const void *b, void *c, unsigned n,
+                            unsigned k, unsigned m, unsigned batch, size_t stride_a, size_t stride_b, size_t stride_c) {
+  const mm::Problem p = batched_problem(cfg, a, b, c, n, k, m, batch, stride_a, stride_b, stride_c);
+  Family fam;
+  int rc = check_batched(cfg, p, &fam);
+  if (rc || fam == FAM_NONE) return rc;   // (FAM_NONE: an empty batch, nothing to do)
+  if ((rc = ensure_init())) return rc;
+  return dispatch_batched((hipStream_t)hip_stream, *cfg, p, fam);
+}
+
+int mm_gemm_batched_launch(int device, const mm_config_t *cfg, const void *a, const void *b, void *c, unsigned n,
+                           unsigned k, unsigned m, unsigned batch, size_t stride_a, size_t stride_b, size_t stride_c,
+                           double *elapsed_seconds) {
+  const mm::Problem p = batched_problem(cfg, a, b, c, n, k, m, batch, stride_a, stride_b, stride_c);
+  Family fam;
+  int rc = check_batched(cfg, p, &fam);
+  if (rc) return rc;
+  if (fam == FAM_NONE) {   // an empty batch: nothing to launch or time
+    if (elapsed_seconds) *elapsed_seconds = 0.0;
+    return MM_OK;
+  }
+  if ((rc = check_device(device))) return rc;
+  MM_HIP(hipSetDevice(device));
+  Event start, stop;
+  MM_HIP(hipEventCreate(&start.e));
+  MM_HIP(hipEventCreate(&stop.e));
+  MM_HIP(hipEventRecord(start.e, nullptr));
+  rc = dispatch_batched(nullptr, *cfg, p, fam);
   if (rc != MM_OK) return rc;
   MM_HIP(hipEventRecord(stop.e, nullptr));
   MM_HIP(hipEventSynchronize(stop.e));
@@ -766,6 +916,25 @@ const char *mm_kernel_name(const mm_config_t *cfg, unsigned n, unsigned k, unsig
     case FAM_NONE: return "unsupported";
     case FAM_VALU_TILE: return "valu_tile";
     case FAM_ORDERED_TILE: return "ordered_tile";   // k ascending, one accumulator, unfused: Naive's bits on 128 x 128 register tiles
+    default: return "ordered";
+  }
+}
+
+const char *mm_kernel_name_batched(const mm_config_t *cfg, unsigned n, unsigned k, unsigned m, unsigned batch) {
+  if (!valid_cfg(cfg)) return "invalid";
+  const mm::Problem p = batched_problem(cfg, nullptr, nullptr, nullptr, n, k, m, batch ? batch : 1, 0, 0, 0);
+  switch (choose_batched(*cfg, p)) {   // the resolver dispatch_batched uses
+    case FAM_MFMA_F32: {
+      const int v = mm::mfma_f32_batched_resolve(p, f32_variant());
+      return v < 0 ? "unsupported" : mm::mfma_f32_name(v);
+    }
+    case FAM_MFMA_F64: return mm::mfma_f64_batched_name(p);
+    case FAM_MFMA_F16: return mm::mfma_f16_batched_name(p);
+    case FAM_MFMA_I8: return mm::mfma_i8_batched_name(p);
+    case FAM_HALF_WIDE: return "ordered_wide_f16";
+    case FAM_VALU_TILE: return "valu_tile";
+    case FAM_ORDERED_TILE: return "ordered_tile";
+    case FAM_NONE: return "unsupported";
     default: return "ordered";
   }
 }

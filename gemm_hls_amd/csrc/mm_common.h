@@ -88,7 +88,33 @@ struct Problem {
   // 0 = n.  Decisions that change the summation order (split-K) are taken on the whole job, so that a row's bits do
   // not depend on how the rows were dealt out.
   unsigned n_total = 0;
+  // strided batch (mm_gemm_batched_*): `batch` problems of this shape, element e at a + e * stride_a, b + e * stride_b,
+  // c + e * stride_c (strides in elements; 0 = one operand shared by every element).  Only the *_batched launchers read
+  // these; every other launcher runs the one problem at (a, b, c).
+  unsigned batch = 1;
+  size_t stride_a = 0, stride_b = 0, stride_c = 0;
 };
+
+// Batched launches: `p.batch` copies of the tile grid in ONE launch; the kernel derives the element from the workgroup id
+// (XCD-remapped linear id = element * tiles + tile, so one element's tiles stay contiguous on an XCD) and moves the A, B and
+// C bases by it.  No workspace, no split of K.  Grid-size limits are the caller's (mm_capi.hip splits the batch).
+int launch_ordered_batched(hipStream_t s, const mm_config_t &cfg, const Problem &p);
+int launch_half_wide_batched(hipStream_t s, const Problem &p);
+int launch_valu_tile_batched(hipStream_t s, const mm_config_t &cfg, const Problem &p);
+int launch_valu_tile_exact_batched(hipStream_t s, const mm_config_t &cfg, const Problem &p);
+int mfma_f32_batched_resolve(const Problem &p, int variant);   // 33 / 8 / 35 (row-major), 8 (K x N A); -1 = unsupported
+int launch_mfma_f32_batched(hipStream_t s, const Problem &p, int resolved_variant);
+// the other matrix-core families: resolve once on the whole batch (-1: not served batched -- e.g. a K x N A the single
+// launch would transpose first), then launch each chunk with that kernel
+int mfma_f64_batched_resolve(const Problem &p);
+int mfma_f16_batched_resolve(const Problem &p);
+int mfma_i8_batched_resolve(const Problem &p);
+const char *mfma_f64_batched_name(const Problem &p);
+const char *mfma_f16_batched_name(const Problem &p);
+const char *mfma_i8_batched_name(const Problem &p);
+int launch_mfma_f64_batched(hipStream_t s, const Problem &p, int resolved);
+int launch_mfma_f16_batched(hipStream_t s, const Problem &p, int resolved);
+int launch_mfma_i8_batched(hipStream_t s, const Problem &p, int resolved);
 
 // Launchers (one translation unit each).  Return hipError_t as int; hipErrorNotSupported (801)
 // means "this family does not serve this (config, shape)".
@@ -174,6 +200,7 @@ enum Tunable {
   TUNE_HALF_CONTRACT,      // MM_HALF_CONTRACT  1 / "reference": half (Multiply, Add) under MM_PATH_AUTO keeps the REFERENCE's arithmetic
                            //                 (binary16 products and binary16 accumulation, k ascending: kernel/Compute.cpp:129-133) on the
                            //                 k-ordered tile kernel instead of the matrix cores' f32 accumulation; 0 / "wide" / unset: f32
+  TUNE_BATCH_CHUNK,        // MM_BATCH_CHUNK  mm_gemm_batched_*: at most this many elements per launch (tests); -1: only the grid limits
   TUNE_COUNT
 };
 int tuning(Tunable t);  // mm_capi.hip
@@ -202,12 +229,14 @@ inline unsigned band_rows(unsigned bm = 256, unsigned bn = 256, unsigned per_cu 
 // problems and leaves CUs idle on small ones.  Estimated time of a candidate ~ (workgroups the
 // busiest CU runs) x tile area / relative efficiency; the smallest wins.
 struct TileCandidate { int id; unsigned bm, bn, per_cu; double eff; };
-inline int pick_tile(const TileCandidate *cands, int count, unsigned n, unsigned m, double *best_time = nullptr) {
+// `copies`: copies of the N x M tile grid the launch runs side by side (the elements of a batched launch).
+inline int pick_tile(const TileCandidate *cands, int count, unsigned n, unsigned m, double *best_time = nullptr,
+                     unsigned long long copies = 1) {
   double best = 0;
   int pick = cands[0].id;
   for (int i = 0; i < count; ++i) {
     const TileCandidate &c = cands[i];
-    const unsigned long long tiles = (unsigned long long)((n + c.bm - 1) / c.bm) * ((m + c.bn - 1) / c.bn);
+    const unsigned long long tiles = (unsigned long long)((n + c.bm - 1) / c.bm) * ((m + c.bn - 1) / c.bn) * copies;
     const unsigned long long slots = 256ull * c.per_cu, full = tiles / slots, rem = tiles % slots;
     const double t = ((double)full * c.per_cu + (double)((rem + 255) / 256)) * c.bm * c.bn / c.eff;
     if (best == 0 || t < best * 0.999) { best = t; pick = c.id; }
@@ -226,6 +255,20 @@ __device__ __forceinline__ unsigned xcd_remap(unsigned bid, unsigned nwg) {
   const unsigned xcd = bid % kXcds, slot = bid / kXcds;
   const unsigned base = xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
   return base + slot;
+}
+
+// Batched launches (the *_batched_kernel forms): `batch` elements of one shape, `batch` copies of the tile grid in one
+// launch.  The XCD-remapped linear id is decomposed as (element, tile), so one element's tiles stay contiguous in an XCD's
+// chunk of the grid (a broadcast B, or one element's A panels, stays in that XCD's L2); the element index is uniform across
+// the workgroup (SGPRs) and moves the A, B and C bases before anything else.  Returns the element's linear tile id.
+template <typename PA, typename PB, typename PC>
+__device__ __forceinline__ unsigned batched_tile(PA &A, PB &B, PC &C, unsigned tiles, unsigned batch, size_t stride_a,
+                                                 size_t stride_b, size_t stride_c) {
+  const unsigned g = xcd_remap(blockIdx.x, tiles * batch), e = g / tiles;
+  A += e * stride_a;
+  B += e * stride_b;
+  C += e * stride_c;
+  return g - e * tiles;
 }
 
 }  // namespace mm

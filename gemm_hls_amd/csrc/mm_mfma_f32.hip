@@ -116,6 +116,39 @@ int launch_geo(hipStream_t s, const Problem &p, unsigned splits = 1) {
   return rc ? rc : (int)f;
 }
 
+// Batched launches (mm_gemm_batched_*): `batch` copies of the whole-tile grid in one launch, as the split-K launch holds
+// `splits` copies -- the copies are the elements.  The XCD-remapped linear id is decomposed as (element, tile), so one
+// element's tiles stay contiguous in an XCD's chunk of the grid; the element index is uniform (SGPRs) and moves the A, B
+// and C bases before anything else.  Per element exactly mfma_f32_kernel's whole-tile arithmetic: the same bits.
+template <typename G, bool AT>
+__global__ __launch_bounds__(G::THREADS, G::MIN_WAVES) void mfma_f32_batched_kernel(
+    const float *__restrict__ A, const float *__restrict__ B, float *__restrict__ C, unsigned N, unsigned K, unsigned M,
+    unsigned tiles_n, unsigned tiles_m, unsigned kBand, unsigned batch, size_t stride_a, size_t stride_b, size_t stride_c) {
+  const unsigned nwg = tiles_n * tiles_m;
+  const unsigned g = xcd_remap(blockIdx.x, nwg * batch), e = g / nwg;
+  A += e * stride_a;
+  B += e * stride_b;
+  C += e * stride_c;
+  const unsigned lin = g - e * nwg;
+  const unsigned band = lin / (kBand * tiles_m), within = lin % (kBand * tiles_m);
+  const unsigned rows_in_band = min(kBand, tiles_n - band * kBand);
+  const unsigned tile_row = band * kBand + within % rows_in_band;
+  const unsigned tile_col = within / rows_in_band;
+  tile_body<G, AT>(A, B, C, N, K, M, K, M, N, M, tile_row * G::BM, tile_col * G::BN);
+}
+
+template <typename G, bool AT = false>
+int launch_geo_batched(hipStream_t s, const Problem &p) {
+  const unsigned tiles_n = (p.n + G::BM - 1) / G::BM, tiles_m = (p.m + G::BN - 1) / G::BN;
+  static unsigned long long configured = 0;
+  if (int e = ensure_dynamic_lds((const void *)mfma_f32_batched_kernel<G, AT>, G::LDS_BYTES, configured)) return e;
+  (void)hipGetLastError();
+  hipLaunchKernelGGL((mfma_f32_batched_kernel<G, AT>), dim3(tiles_n * tiles_m * p.batch), dim3(G::THREADS), G::LDS_BYTES, s,
+                     (const float *)p.a, (const float *)p.b, (float *)p.c, p.n, p.k, p.m, tiles_n, tiles_m,
+                     band_rows(G::BM, G::BN, G::MIN_WAVES), p.batch, p.stride_a, p.stride_b, p.stride_c);
+  return (int)hipGetLastError();
+}
+
 // The geometries of the product.  Every shipped geometry exists as a (ScalarBase, VectorAddress) pair with identical
 // arithmetic; the launcher takes the first when the problem allows it.
 //                       TM WM WN BK  chain            chunk  reads            DMA
@@ -400,6 +433,27 @@ void mfma_f32_geometry(int v, unsigned *bm, unsigned *bn, unsigned *bk, unsigned
 static bool sdma_fits(const Problem &p, unsigned bk) {
   const unsigned long long span = 256ull * (p.a_transposed ? 1ull : p.k) * 4ull, spanb = 32ull * (p.m > p.n ? p.m : p.n) * 4ull;
   return p.k >= bk && span < (1ull << 32) && spanb < (1ull << 32);
+}
+
+// Batched: whole tiles only -- no split-K planes, no stream-K scratch, no K x N pre-pass (a K x N A runs the direct
+// 256 x 256 K x N kernel).  The geometry is picked on the tile count of the whole batch (p.batch copies of the grid); a
+// pinned f32_variant among the whole-tile geometries is honoured.  Every one of them gives the same bits per element.
+int mfma_f32_batched_resolve(const Problem &p, int variant) {
+  if (!mfma_f32_serves(p)) return -1;
+  if (p.a_transposed) return 8;
+  if (variant == 33 || variant == 8 || variant == 35) return variant;
+  return pick_tile(kAutoCands, 3, p.n, p.m, nullptr, p.batch ? p.batch : 1);
+}
+
+int launch_mfma_f32_batched(hipStream_t s, const Problem &p, int v) {
+  if (!mfma_f32_serves(p)) return kErrNotSupported;
+  if (p.a_transposed) return sdma_fits(p, 16) ? launch_geo_batched<T256x256, true>(s, p) : launch_geo_batched<T256x256v, true>(s, p);
+  switch (v) {
+    case 33: return sdma_fits(p, 16) ? launch_geo_batched<T128x256>(s, p) : launch_geo_batched<T128x256v>(s, p);
+    case 8: return sdma_fits(p, 16) ? launch_geo_batched<T256x256>(s, p) : launch_geo_batched<T256x256v>(s, p);
+    case 35: return sdma_fits(p, 32) ? launch_geo_batched<T128x128>(s, p) : launch_geo_batched<T128x128v>(s, p);
+  }
+  return kErrNotSupported;
 }
 
 int launch_mfma_f32(hipStream_t s, const Problem &p, int variant) {

@@ -1,80 +1,12 @@
-// LAB EDITION (tools/lab, built into libmm_gemm_amd_lab.so only): the schedules, cache-policy experiments, tile shapes
-// and ablations (some return WRONG results on purpose; they need MM_ABLATIONS=1) behind the numbers under profiles/.
-// The product file is gemm_hls_amd/csrc/mm_mfma_i8.hip.
-//
-// int8_t / uint8_t (Multiply, Add) fast path for gfx950 on v_mfma_i32_32x32x32_i8.
-//
-// Why the signed-int8 matrix core serves BOTH element types exactly: the reference's semiring on
-// an 8-bit Data_t wraps every product and every sum to 8 bits (hlslib::op::Multiply/Add return
-// Data_t), i.e. the result is sum_k a*b taken mod 2^8.  uint8 and int8 bit patterns are congruent
-// mod 2^8, products and sums of congruent numbers stay congruent, and the i32 accumulator wraps mod
-// 2^32 (a multiple of 2^8), so (int8)(i32 accumulator) is bit-identical to Naive
-// (include/Utility.h:18-42) for int8_t and for uint8_t (the type the reference special-cases at
-// CMakeLists.txt:46-47).  Checked against the oracle in tests/test_gpu_parity.py.
-//
-// Organisation as mm_mfma_f16.hip: 256 x 256 x 128(bytes) slabs, 8 wavefronts of 64 x 128, A operand
-// by one ds_read_b128 (16 consecutive k of a row, rows swizzled with (row>>1)&7), B operand (16
-// consecutive k of ONE column of the row-major B) by two ds_read_b64_tr_b8: lane i of a 16-lane
-// group receives column i of the [8 k][16 col] block whose rows the group's lanes point at,
-// out[i][j] = in[2j + (i>>3)][i&7] (profiles/r01_probe_ds_read_b64_tr_b8_and_mfma_i8.txt).  A B
-// k-row is 256 B = one bank row, so the 16-B chunk index is XORed with (k&7)<<1 on the DMA source
-// side: the 8 rows of a block then sit in 8 different chunk pairs and a half-wave reads 256
-// distinct bytes.  Operand layout of the MFMA (same probe): lane l, byte b <-> k = 16*(l>>5) + b.
-// Edges: N arbitrary, K % 32 == 0, M % 16 == 0 (reference contract for 1-byte types: K % 64,
-// M % 64); a K x N A (N % 16 == 0) is gathered like B; other shapes go to the predicated kernels.
-#include <cstdlib>
-#include <type_traits>
-
-#include "../../gemm_hls_amd/csrc/mm_common.h"
-
-namespace mm {
-namespace {
-
-using i32x4 = __attribute__((ext_vector_type(4))) int;
-using i32x16 = __attribute__((ext_vector_type(16))) int;
-typedef int v2i __attribute__((vector_size(8)));
-typedef __attribute__((address_space(3))) void *lptr_t;
-
-struct GeoI8 {
-  static constexpr int WM = 4, WN = 2, NS = 2, TM = 2, TN = 4;
-  static constexpr int NW = WM * WN, THREADS = NW * 64;
-  static constexpr int BM = 256, BN = 256, BK = 128;           // BK in elements == bytes
-  static constexpr int CPR = 8;                                // 16-B chunks per A row
-  static constexpr int BROW = BN, BCH = BROW / 16;             // B k-row bytes / chunks
-  static constexpr int A_BYTES = BM * BK, B_BYTES = BK * BROW;
-  static constexpr int STAGE_BYTES = A_BYTES + B_BYTES, LDS_BYTES = NS * STAGE_BYTES;
-  static constexpr int NA = A_BYTES / 1024, NB = B_BYTES / 1024;
-  static constexpr int LA = NA / NW, LB = NB / NW;
-  static constexpr int KS = BK / 32;                           // MFMA k-steps per slab
-};
-
-// asm LDS-DMA (see mm_mfma_f16.hip: transpose-read builtins make hipcc drain builtin DMAs)
-__device__ __forceinline__ void dma16(const void *gsrc, unsigned lds_byte_addr) {
-  unsigned keep;
-  asm volatile(
-      "s_mov_b32 %0, m0\n\t"
-      "s_mov_b32 m0, %2\n\t"
-      "s_nop 0\n\t"
-      "global_load_lds_dwordx4 %1, off\n\t"
-      "s_mov_b32 m0, %0"
-      : "=&s"(keep)
-      : "v"(gsrc), "s"(lds_byte_addr)
-      : "memory");
-}
-
-__device__ __forceinline__ i32x4 join(v2i lo, v2i hi) {
-  i32x4 r;
-  r[0] = lo[0]; r[1] = lo[1]; r[2] = hi[0]; r[3] = hi[1];
-  return r;
-}
-
-template <bool AT>
-__global__ __launch_bounds__(GeoI8::THREADS) void mfma_i8_kernel(const signed char *__restrict__ A,
+// The kernels of mm_mfma_i8.hip, compiled twice by it: MM_BATCHED 0 the single-problem kernels, 1 their *_batched twins
+// (mm_batched_kernel.h).  Definitions that are not kernels appear in the first pass only.
+#include "mm_batched_kernel.h"
+template <typename G, bool AT>
+__global__ __launch_bounds__(G::THREADS) void MM_KNAME(mfma_i8_kernel)(const signed char *__restrict__ A,
                                                                  const signed char *__restrict__ B,
                                                                  signed char *__restrict__ C, unsigned N, unsigned K,
                                                                  unsigned M, unsigned tiles_n, unsigned tiles_m,
-                                                                 unsigned kBand) {
-  using G = GeoI8;
+                                                                 unsigned kBand MM_BATCH_PARAMS) {
   constexpr int TM = G::TM, TN = G::TN, BK = G::BK, NS = G::NS, CPR = G::CPR;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const unsigned lane = threadIdx.x & 63u;
@@ -82,7 +14,7 @@ __global__ __launch_bounds__(GeoI8::THREADS) void mfma_i8_kernel(const signed ch
   const unsigned wm = wave / G::WN, wn = wave % G::WN;
   const unsigned lo = lane & 31u, hi = lane >> 5;
 
-  const unsigned lin = xcd_remap(blockIdx.x, tiles_n * tiles_m);
+  const unsigned lin = MM_TILE_LIN(blockIdx.x, tiles_n * tiles_m);
   const unsigned band = lin / (kBand * tiles_m), within = lin % (kBand * tiles_m);
   const unsigned rows_in_band = min(kBand, tiles_n - band * kBand);
   const unsigned row0 = (band * kBand + within % rows_in_band) * G::BM, col0 = (within / rows_in_band) * G::BN;
@@ -246,6 +178,7 @@ __global__ __launch_bounds__(GeoI8::THREADS) void mfma_i8_kernel(const signed ch
     }
   }
 }
+#if !MM_BATCHED
 
 
 // =================================================================================================
@@ -258,42 +191,45 @@ __global__ __launch_bounds__(GeoI8::THREADS) void mfma_i8_kernel(const signed ch
 // Requirements: K % 64 == 0 (the reference's contract for 1-byte types), M % 16 == 0, row-major A.
 struct GeoI8PP {
   static constexpr int BM = 256, BN = 256, BK = 64, NS = 4, THREADS = 512;
-  static constexpr int TM = 4, TN = 2;
   static constexpr int A_BYTES = BM * BK, B_BYTES = BK * BN, STAGE_BYTES = A_BYTES + B_BYTES;
   static constexpr int LDS_BYTES = NS * STAGE_BYTES;
   static constexpr int BROW = BN;
 };
 #define MM_DMA_PIECE(vo, sb, la) "s_mov_b32 m0, " la "\n\ts_nop 0\n\tglobal_load_lds_dwordx4 " vo ", " sb "\n\t"
 
-template <int VAR, bool AT = false>  // VAR bit 1: lock-step ablation; AT: A stored K x N, staged and gathered like B
-__global__ __launch_bounds__(GeoI8PP::THREADS) void mfma_i8_pp_kernel(const signed char *__restrict__ A,
+#endif  // !MM_BATCHED
+template <bool AT>  // AT: A stored K x N, staged and gathered like B
+__global__ __launch_bounds__(GeoI8PP::THREADS) void MM_KNAME(mfma_i8_pp_kernel)(const signed char *__restrict__ A,
                                                                         const signed char *__restrict__ B,
                                                                         signed char *__restrict__ C, unsigned N, unsigned K,
                                                                         unsigned M, unsigned tiles_n, unsigned tiles_m,
-                                                                        unsigned kBand) {
+                                                                        unsigned kBand MM_BATCH_PARAMS) {
+  // pingpong_k64 on v_mfma_i32_16x16x64_i8 since round 3 (one 64-deep slab = one MFMA k; the 32x32x32 edition is in the lab)
   using G = GeoI8PP;
-  constexpr int TM = G::TM, TN = G::TN;
+  constexpr int RB = 8, NB = 4;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const unsigned lane = threadIdx.x & 63u;
   const unsigned wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const unsigned group = wave >> 2, wq = wave & 3u;
   const unsigned wm = wq >> 1, wn = (wq & 1u) * 2 + group;
-  const unsigned lo = lane & 31u, hi = lane >> 5;
+  const unsigned l15 = lane & 15u, g = lane >> 4;
 
-  const unsigned lin = xcd_remap(blockIdx.x, tiles_n * tiles_m);
+  const unsigned lin = MM_TILE_LIN(blockIdx.x, tiles_n * tiles_m);
   const unsigned band = lin / (kBand * tiles_m), within = lin % (kBand * tiles_m);
   const unsigned rows_in_band = min(kBand, tiles_n - band * kBand);
   const unsigned row0 = (band * kBand + within % rows_in_band) * G::BM, col0 = (within / rows_in_band) * G::BN;
 
+  // DMA.  Row-major A: 16 pieces of 16 rows x 64 B, source chunk = pc ^ (-(row>>2))&3; B and a K x N A: 16 pieces of
+  // 4 k-rows x 256 B, source chunk = pb ^ (((k&7)<<1) | ((k>>4)&1))  (see pingpong_16x16x64)
   unsigned voff_a[2], voff_b[2];
 #pragma unroll
   for (int i = 0; i < 2; ++i) {
     const unsigned piece = wave + 8 * i;
-    const unsigned row = piece * 16 + lane / 4, pc = lane % 4;         // 16 A pieces of 16 rows x 64 B
-    const unsigned kr = piece * 4 + lane / 16, pb = lane % 16;         // 16 B pieces of 4 k-rows x 256 B
-    const unsigned lc = pb ^ ((kr & 7u) << 1);
+    const unsigned row = piece * 16 + lane / 4, pc = lane % 4;
+    const unsigned kr = piece * 4 + lane / 16, pb = lane % 16;
+    const unsigned lc = pb ^ (((kr & 7u) << 1) | ((kr >> 4) & 1u));
     voff_a[i] = AT ? kr * N + (min(row0 + lc * 16, N - 16) - row0)
-                   : (min(row0 + row, N - 1) - row0) * K + (pc ^ ((row >> 2) & 3u)) * 16;
+                   : (min(row0 + row, N - 1) - row0) * K + (pc ^ ((0u - (row >> 2)) & 3u)) * 16;
     voff_b[i] = kr * M + (min(col0 + lc * 16, M - 16) - col0);
   }
   const char *a_base = (const char *)A + (AT ? (size_t)row0 : (size_t)row0 * K);
@@ -315,69 +251,53 @@ __global__ __launch_bounds__(GeoI8PP::THREADS) void mfma_i8_pp_kernel(const sign
                  : "memory");
   };
 
-  // A fragment: row = wm*128 + mi*32 + lo, chunk (2*ks + hi) ^ ((lo>>2)&3)
-  const unsigned ca = hi ^ ((lo >> 2) & 3u);
-  const unsigned a_row_byte = (wm * 128 + lo) * G::BK;
-  const unsigned a_off[2] = {a_row_byte + ca * 16, a_row_byte + (ca ^ 2u) * 16};
-  // B fragment (8-bit transpose read): y = lane&15 -> block row r = y>>1, 8-byte half q = y&1; gq = 16-col half
-  //   k = ks*32 + 16*hi + 8*h + r ; 32-col block = wn*2 + ni, physical block = logical ^ r
-  const unsigned y = lane & 15u, gq = (lane >> 4) & 1u, r = y >> 1, q = y & 1u;
-  unsigned b_off[TN];
+  // A (row-major): row = wm*128 + rb*16 + l15, chunk g (16 k bytes), physical = g ^ (-(l15>>2))&3
+  const unsigned a_off = (wm * 128 + l15) * G::BK + (g ^ ((0u - (l15 >> 2)) & 3u)) * 16;
+  // B (8-bit transpose read): block row r = l15>>1 (k = 16*g + 8*h2 + r), 8-byte half q = l15&1 of the 16 columns
+  const unsigned r = l15 >> 1, q = l15 & 1u, xk = (r << 1) | (g & 1u);
+  unsigned b_off[NB];
 #pragma unroll
-  for (int ni = 0; ni < TN; ++ni)
-    b_off[ni] = G::A_BYTES + (16 * hi + r) * G::BROW + 8 * q + ((((wn * 2 + ni) ^ r) * 2) + gq) * 16;
-  unsigned at_off[TM];  // K x N A: the same gather over the [k][256 rows] image
+  for (int nb = 0; nb < NB; ++nb) b_off[nb] = G::A_BYTES + (16 * g + r) * G::BROW + 8 * q + ((wn * 4 + nb) ^ xk) * 16;
+  unsigned at_off[RB];  // K x N A: the same gather over the [k][256 rows] image (this wavefront's 16-row chunks wm*8 .. +7)
 #pragma unroll
-  for (int mi = 0; mi < TM; ++mi)
-    at_off[mi] = (16 * hi + r) * G::BM + 8 * q + ((((wm * 4 + mi) ^ r) * 2) + gq) * 16;
+  for (int rb = 0; rb < RB; ++rb) at_off[rb] = (16 * g + r) * G::BM + 8 * q + ((wm * 8 + rb) ^ xk) * 16;
 
-  i32x16 acc[TM][TN];
+  i32x4 acc[RB][NB];
 #pragma unroll
-  for (int mi = 0; mi < TM; ++mi)
+  for (int rb = 0; rb < RB; ++rb)
 #pragma unroll
-    for (int ni = 0; ni < TN; ++ni) acc[mi][ni] = (i32x16)0;
+    for (int nb = 0; nb < NB; ++nb) acc[rb][nb] = (i32x4)0;
 
   auto sync = [&]() {
     __builtin_amdgcn_sched_barrier(0);
     __builtin_amdgcn_s_barrier();
     __builtin_amdgcn_sched_barrier(0);
   };
+  auto tr2 = [&](const char *p, unsigned row_bytes) {
+    const v2i v0 = __builtin_amdgcn_ds_read_tr8_b64_v2i32((v2i __attribute__((address_space(3))) *)(lptr_t)p);
+    const v2i v1 = __builtin_amdgcn_ds_read_tr8_b64_v2i32((v2i __attribute__((address_space(3))) *)(lptr_t)(p + 8 * row_bytes));
+    return join(v0, v1);
+  };
   auto phase = [&](auto bufc, unsigned u) {
     constexpr int BUF = decltype(bufc)::value;
     const char *base = smem + BUF * G::STAGE_BYTES;
-    i32x4 af[TM][2], bf[TN][2];
+    i32x4 af[RB], bf[NB];
 #pragma unroll
-    for (int ks = 0; ks < 2; ++ks) {
+    for (int nb = 0; nb < NB; ++nb) bf[nb] = tr2(base + b_off[nb], G::BROW);
 #pragma unroll
-      for (int ni = 0; ni < TN; ++ni) {
-        const char *p = base + b_off[ni] + ks * 32 * G::BROW;
-        const v2i v0 = __builtin_amdgcn_ds_read_tr8_b64_v2i32((v2i __attribute__((address_space(3))) *)(lptr_t)p);
-        const v2i v1 = __builtin_amdgcn_ds_read_tr8_b64_v2i32((v2i __attribute__((address_space(3))) *)(lptr_t)(p + 8 * G::BROW));
-        bf[ni][ks] = join(v0, v1);
-      }
-#pragma unroll
-      for (int mi = 0; mi < TM; ++mi) {
-        if (AT) {
-          const char *p = base + at_off[mi] + ks * 32 * G::BM;
-          const v2i v0 = __builtin_amdgcn_ds_read_tr8_b64_v2i32((v2i __attribute__((address_space(3))) *)(lptr_t)p);
-          const v2i v1 = __builtin_amdgcn_ds_read_tr8_b64_v2i32((v2i __attribute__((address_space(3))) *)(lptr_t)(p + 8 * G::BM));
-          af[mi][ks] = join(v0, v1);
-        } else {
-          af[mi][ks] = *(const i32x4 *)(base + a_off[ks] + mi * 32 * G::BK);
-        }
-      }
+    for (int rb = 0; rb < RB; ++rb) {
+      if (AT) af[rb] = tr2(base + at_off[rb], G::BM);
+      else af[rb] = *(const i32x4 *)(base + a_off + rb * 16 * G::BK);
     }
     issue(u + 3, (BUF + 3) & 3);
     asm volatile("s_waitcnt vmcnt(8)\n\ts_waitcnt lgkmcnt(0)" ::: "memory");
     sync();
     __builtin_amdgcn_s_setprio(1);
 #pragma unroll
-    for (int ks = 0; ks < 2; ++ks)
+    for (int rb = 0; rb < RB; ++rb)
 #pragma unroll
-      for (int mi = 0; mi < TM; ++mi)
-#pragma unroll
-        for (int ni = 0; ni < TN; ++ni)
-          acc[mi][ni] = __builtin_amdgcn_mfma_i32_32x32x32_i8(af[mi][ks], bf[ni][ks], acc[mi][ni], 0, 0, 0);
+      for (int nb = 0; nb < NB; ++nb)
+        acc[rb][nb] = __builtin_amdgcn_mfma_i32_16x16x64_i8(af[rb], bf[nb], acc[rb][nb], 0, 0, 0);
     __builtin_amdgcn_s_setprio(0);
     sync();
   };
@@ -387,7 +307,7 @@ __global__ __launch_bounds__(GeoI8PP::THREADS) void mfma_i8_pp_kernel(const sign
   issue(2, 2);
   asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
   sync();
-  const bool shifted = !(VAR & 2) && group == 1;
+  const bool shifted = group == 1;
   if (shifted) sync();
   for (unsigned u = 0; u < U; u += 4) {
     phase(std::integral_constant<int, 0>{}, u);
@@ -396,21 +316,18 @@ __global__ __launch_bounds__(GeoI8PP::THREADS) void mfma_i8_pp_kernel(const sign
     if (u + 3 < U) phase(std::integral_constant<int, 3>{}, u + 3);
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  if (!shifted && !(VAR & 2)) sync();
+  if (!shifted) sync();
   sync();
 
-  // epilogue: low 8 bits of the i32 sums through this wave's 8 KiB slice, 16-B global stores
+  // epilogue: low 8 bits of the i32 sums through this wave's 8 KiB slice, 16-B global stores (C/D: column l15, rows 4*g + i)
   {
     char *slice = smem + wave * (128 * 64);
 #pragma unroll
-    for (int mi = 0; mi < TM; ++mi)
+    for (int rb = 0; rb < RB; ++rb)
 #pragma unroll
-      for (int ni = 0; ni < TN; ++ni)
+      for (int nb = 0; nb < NB; ++nb)
 #pragma unroll
-        for (int rr = 0; rr < 16; ++rr) {
-          const unsigned row = mi * 32 + (rr & 3) + 8 * (rr >> 2) + 4 * hi;
-          slice[row * 64 + ni * 32 + lo] = (char)acc[mi][ni][rr];
-        }
+        for (int i = 0; i < 4; ++i) slice[(rb * 16 + 4 * g + i) * 64 + nb * 16 + l15] = (char)acc[rb][nb][i];
     using u32x4 = __attribute__((ext_vector_type(4))) unsigned;
 #pragma unroll
     for (int it = 0; it < 128 * 4 / 64; ++it) {
@@ -421,6 +338,7 @@ __global__ __launch_bounds__(GeoI8PP::THREADS) void mfma_i8_pp_kernel(const sign
     }
   }
 }
+#if !MM_BATCHED
 
 // Ping-pong with full-line A requests (see mfma_f16_pp2_kernel in mm_mfma_f16.hip): A staged in
 // double slabs [256 rows][128 B] (ring of 3 x 32 KiB, chunk ^ (row>>1)&7), B in 64-deep slabs (ring of
@@ -433,12 +351,12 @@ struct GeoI8PP2 {
   static constexpr int BROW = BN;
 };
 
-template <int VAR>
-__global__ __launch_bounds__(GeoI8PP2::THREADS) void mfma_i8_pp2_kernel(const signed char *__restrict__ A,
+#endif  // !MM_BATCHED
+__global__ __launch_bounds__(GeoI8PP2::THREADS) void MM_KNAME(mfma_i8_pp2_kernel)(const signed char *__restrict__ A,
                                                                          const signed char *__restrict__ B,
                                                                          signed char *__restrict__ C, unsigned N, unsigned K,
                                                                          unsigned M, unsigned tiles_n, unsigned tiles_m,
-                                                                         unsigned kBand) {
+                                                                         unsigned kBand MM_BATCH_PARAMS) {
   using G = GeoI8PP2;
   constexpr int TM = G::TM, TN = G::TN;
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -448,7 +366,7 @@ __global__ __launch_bounds__(GeoI8PP2::THREADS) void mfma_i8_pp2_kernel(const si
   const unsigned wm = wq >> 1, wn = (wq & 1u) * 2 + group;
   const unsigned lo = lane & 31u, hi = lane >> 5;
 
-  const unsigned lin = xcd_remap(blockIdx.x, tiles_n * tiles_m);
+  const unsigned lin = MM_TILE_LIN(blockIdx.x, tiles_n * tiles_m);
   const unsigned band = lin / (kBand * tiles_m), within = lin % (kBand * tiles_m);
   const unsigned rows_in_band = min(kBand, tiles_n - band * kBand);
   const unsigned row0 = (band * kBand + within % rows_in_band) * G::BM, col0 = (within / rows_in_band) * G::BN;
@@ -553,7 +471,7 @@ __global__ __launch_bounds__(GeoI8PP2::THREADS) void mfma_i8_pp2_kernel(const si
   issue_b(2, 2);
   asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
   sync();
-  const bool shifted = !(VAR & 2) && group == 1;
+  const bool shifted = group == 1;
   if (shifted) sync();
   unsigned ab = 0;
   for (unsigned u = 0; u < U; u += 4) {
@@ -567,7 +485,7 @@ __global__ __launch_bounds__(GeoI8PP2::THREADS) void mfma_i8_pp2_kernel(const si
     ab = ab1 == 2 ? 0 : ab1 + 1;
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  if (!shifted && !(VAR & 2)) sync();
+  if (!shifted) sync();
   sync();
 
   {
@@ -591,9 +509,10 @@ __global__ __launch_bounds__(GeoI8PP2::THREADS) void mfma_i8_pp2_kernel(const si
     }
   }
 }
+#if !MM_BATCHED
 
-// Ping-pong kernel on v_mfma_i32_16x16x64_i8 ("pp2s", round 3): same tile, rings, DMA and segment protocol as
-// pp2, the matrix instruction in its 16 x 16 x 64 form (4 accumulator registers, 16 cycles) -- on full-range random
+// pingpong_16x16x64 (round 3, the default): same tile, rings, DMA and segment protocol as
+// pingpong_32x32x32, the matrix instruction in its 16 x 16 x 64 form (4 accumulator registers, 16 cycles) -- on full-range random
 // bytes the register-only loop of this form holds 1.97 GHz = 4.09 POp/s where the 32x32x32 form holds 1.67 GHz =
 // 3.50 POp/s (profiles/r03b_probe_mfma_power_by_shape_and_operand_order.txt), and the kernel is power-limited.
 // A wavefront's 128 x 64 block is 8 x 4 accumulators; a 64-deep slab is ONE MFMA k: 8 A operands (ds_read_b128:
@@ -602,12 +521,12 @@ __global__ __launch_bounds__(GeoI8PP2::THREADS) void mfma_i8_pp2_kernel(const si
 // instead of in column by 16, so the chunk index is XORed with ((k&7)<<1) | ((k>>4)&1): the 16 k-rows a half-wave
 // touches fall into the 16 different chunks of the 256-byte bank row.  Integer sums: bit-identical to every
 // other schedule and to Naive.
-template <int VAR>
-__global__ __launch_bounds__(GeoI8PP2::THREADS) void mfma_i8_pp2s_kernel(const signed char *__restrict__ A,
+#endif  // !MM_BATCHED
+__global__ __launch_bounds__(GeoI8PP2::THREADS) void MM_KNAME(mfma_i8_pp2s_kernel)(const signed char *__restrict__ A,
                                                                           const signed char *__restrict__ B,
                                                                           signed char *__restrict__ C, unsigned N, unsigned K,
                                                                           unsigned M, unsigned tiles_n, unsigned tiles_m,
-                                                                          unsigned kBand) {
+                                                                          unsigned kBand MM_BATCH_PARAMS) {
   using G = GeoI8PP2;
   constexpr int RB = 8, NB = 4;
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -617,7 +536,7 @@ __global__ __launch_bounds__(GeoI8PP2::THREADS) void mfma_i8_pp2s_kernel(const s
   const unsigned wm = wq >> 1, wn = (wq & 1u) * 2 + group;
   const unsigned l15 = lane & 15u, g = lane >> 4;
 
-  const unsigned lin = xcd_remap(blockIdx.x, tiles_n * tiles_m);
+  const unsigned lin = MM_TILE_LIN(blockIdx.x, tiles_n * tiles_m);
   const unsigned band = lin / (kBand * tiles_m), within = lin % (kBand * tiles_m);
   const unsigned rows_in_band = min(kBand, tiles_n - band * kBand);
   const unsigned row0 = (band * kBand + within % rows_in_band) * G::BM, col0 = (within / rows_in_band) * G::BN;
@@ -716,7 +635,7 @@ __global__ __launch_bounds__(GeoI8PP2::THREADS) void mfma_i8_pp2s_kernel(const s
   issue_b(2, 2);
   asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
   sync();
-  const bool shifted = !(VAR & 2) && group == 1;
+  const bool shifted = group == 1;
   if (shifted) sync();
   unsigned ab = 0;
   for (unsigned u = 0; u < U; u += 4) {
@@ -730,7 +649,7 @@ __global__ __launch_bounds__(GeoI8PP2::THREADS) void mfma_i8_pp2s_kernel(const s
     ab = ab1 == 2 ? 0 : ab1 + 1;
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  if (!shifted && !(VAR & 2)) sync();
+  if (!shifted) sync();
   sync();
 
   {  // C/D of the 16x16 form: column l15, rows 4*g + i
@@ -751,94 +670,6 @@ __global__ __launch_bounds__(GeoI8PP2::THREADS) void mfma_i8_pp2s_kernel(const s
     }
   }
 }
-#undef MM_DMA_PIECE
-
-}  // namespace
-
-bool mfma_i8_serves(const Problem &p) {
-  if (!(p.n >= 1 && p.m >= 16 && p.k >= 32 && p.m % 16 == 0 && p.k % 32 == 0)) return false;
-  return !p.a_transposed || (p.n >= 16 && p.n % 16 == 0);
-}
-
-// 32-bit byte offsets inside a tile's rows (see mm_mfma_f16.hip): 256 rows x K B and 128 k-rows x max(M, N) B below 4 GiB
-static bool pp_reach(const Problem &p) {
-  return 256ull * (p.a_transposed ? 1ull : p.k) < (1ull << 32) && 128ull * (p.m > p.n ? p.m : p.n) < (1ull << 32);
-}
-bool mfma_i8_pp_serves(const Problem &p) {
-  return !p.a_transposed && p.k % 64 == 0 && p.k >= 256 && p.m % 16 == 0 && p.m >= 16 && p.n >= 1 && pp_reach(p);
-}
-
-bool mfma_i8_pp_at_serves(const Problem &p) {
-  return p.a_transposed && p.k % 64 == 0 && p.k >= 256 && p.m % 16 == 0 && p.m >= 16 && p.n % 16 == 0 && p.n >= 16 && pp_reach(p);
-}
-
-template <int VAR, bool AT = false>
-static int launch_i8_pp(hipStream_t s, const Problem &p) {
-  using G = GeoI8PP;
-  const unsigned tiles_n = (p.n + G::BM - 1) / G::BM, tiles_m = (p.m + G::BN - 1) / G::BN;
-  static unsigned long long configured = 0;
-  if (int e = ensure_dynamic_lds((const void *)mfma_i8_pp_kernel<VAR, AT>, G::LDS_BYTES, configured)) return e;
-  hipLaunchKernelGGL((mfma_i8_pp_kernel<VAR, AT>), dim3(tiles_n * tiles_m), dim3(G::THREADS), G::LDS_BYTES, s,
-                     (const signed char *)p.a, (const signed char *)p.b, (signed char *)p.c, p.n, p.k, p.m, tiles_n, tiles_m,
-                     band_rows());
-  return (int)hipGetLastError();
-}
-
-bool mfma_i8_pp2_serves(const Problem &p) { return mfma_i8_pp_serves(p) && p.k % 128 == 0 && p.k >= 512; }
-
-static int launch_i8_pp2(hipStream_t s, const Problem &p) {
-  using G = GeoI8PP2;
-  const unsigned tiles_n = (p.n + G::BM - 1) / G::BM, tiles_m = (p.m + G::BN - 1) / G::BN;
-  static unsigned long long configured = 0;
-  if (int e = ensure_dynamic_lds((const void *)mfma_i8_pp2_kernel<0>, G::LDS_BYTES, configured)) return e;
-  hipLaunchKernelGGL((mfma_i8_pp2_kernel<0>), dim3(tiles_n * tiles_m), dim3(G::THREADS), G::LDS_BYTES, s,
-                     (const signed char *)p.a, (const signed char *)p.b, (signed char *)p.c, p.n, p.k, p.m, tiles_n, tiles_m,
-                     band_rows());
-  return (int)hipGetLastError();
-}
-
-static int launch_i8_pp2s(hipStream_t s, const Problem &p) {
-  using G = GeoI8PP2;
-  const unsigned tiles_n = (p.n + G::BM - 1) / G::BM, tiles_m = (p.m + G::BN - 1) / G::BN;
-  static unsigned long long configured = 0;
-  if (int e = ensure_dynamic_lds((const void *)mfma_i8_pp2s_kernel<0>, G::LDS_BYTES, configured)) return e;
-  hipLaunchKernelGGL((mfma_i8_pp2s_kernel<0>), dim3(tiles_n * tiles_m), dim3(G::THREADS), G::LDS_BYTES, s,
-                     (const signed char *)p.a, (const signed char *)p.b, (signed char *)p.c, p.n, p.k, p.m, tiles_n, tiles_m,
-                     band_rows());
-  return (int)hipGetLastError();
-}
-
-const char *mfma_i8_name(const Problem &) { return "mfma_i8_lab"; }   // the lab does not name its schedules
-
-int launch_mfma_i8(hipStream_t s, const Problem &p) {
-  if (!mfma_i8_serves(p)) return kErrNotSupported;
-  // i8_variant knob: 0 = one-slab-per-barrier kernel, 10 = ping-pong, 12 = ping-pong in lock step
-  // (ablation), 100 = ping-pong with full-line A requests; default: the best the shape allows
-  const int v = tuning(TUNE_I8_VARIANT);
-  if (mfma_i8_pp_at_serves(p) && v != 0) return launch_i8_pp<0, true>(s, p);  // K x N A on the ping-pong schedule
-  if (mfma_i8_pp2_serves(p) && (v < 0 || v == 200)) return launch_i8_pp2s(s, p);   // 16x16x64 matrix instruction: +7.6 % (profiles/r03e_*)
-  if (mfma_i8_pp2_serves(p) && v == 100) return launch_i8_pp2(s, p);
-  if (mfma_i8_pp_serves(p) && v != 0) return v == 12 ? launch_i8_pp<2>(s, p) : launch_i8_pp<0>(s, p);
-  using G = GeoI8;
-  const unsigned tiles_n = (p.n + G::BM - 1) / G::BM, tiles_m = (p.m + G::BN - 1) / G::BN;
-  static unsigned long long configured = 0, configured_at = 0;
-  if (p.a_transposed) {
-    if (int e = ensure_dynamic_lds((const void *)mfma_i8_kernel<true>, G::LDS_BYTES, configured_at)) return e;
-    hipLaunchKernelGGL(mfma_i8_kernel<true>, dim3(tiles_n * tiles_m), dim3(G::THREADS), G::LDS_BYTES, s,
-                       (const signed char *)p.a, (const signed char *)p.b, (signed char *)p.c, p.n, p.k, p.m, tiles_n,
-                       tiles_m, band_rows());
-    return (int)hipGetLastError();
-  }
-  if (int e = ensure_dynamic_lds((const void *)mfma_i8_kernel<false>, G::LDS_BYTES, configured)) return e;
-  hipLaunchKernelGGL(mfma_i8_kernel<false>, dim3(tiles_n * tiles_m), dim3(G::THREADS), G::LDS_BYTES, s,
-                     (const signed char *)p.a, (const signed char *)p.b, (signed char *)p.c, p.n, p.k, p.m, tiles_n,
-                     tiles_m, band_rows());
-  return (int)hipGetLastError();
-}
-
-// The lab edition has no batched form: mm_gemm_batched_* of this library run the 8-bit products on the fallback families
-int mfma_i8_batched_resolve(const Problem &) { return -1; }
-const char *mfma_i8_batched_name(const Problem &) { return "unsupported"; }
-int launch_mfma_i8_batched(hipStream_t, const Problem &, int) { return kErrNotSupported; }
-
-}  // namespace mm
+#undef MM_KNAME
+#undef MM_BATCH_PARAMS
+#undef MM_TILE_LIN

@@ -23,68 +23,35 @@ template <typename T, int MAP, int RED, bool AT, typename ACC = T>
 __global__ __launch_bounds__(256) void ordered_kernel(const T *__restrict__ A, const T *__restrict__ B,
                                                       T *__restrict__ C, unsigned N, unsigned K,
                                                       unsigned M) {
-  __shared__ T As[kBK][kTile + 1];  // [k][row], +1: column reads of a row-major source
-  __shared__ T Bs[kBK][kTile];      // [k][col]
-  const unsigned tid = threadIdx.x;
-  const unsigned tx = tid % 16, ty = tid / 16;
-  const unsigned row0 = blockIdx.y * kTile, col0 = blockIdx.x * kTile;
-
-  ACC acc[kPerThread][kPerThread];
-#pragma unroll
-  for (int i = 0; i < kPerThread; ++i)
-#pragma unroll
-    for (int j = 0; j < kPerThread; ++j) acc[i][j] = Op<RED, ACC>::identity();
-
-  for (unsigned k0 = 0; k0 < K; k0 += kBK) {
-    // stage A: 64 rows x 16 k
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      unsigned r, kk;
-      if (AT) { r = tid % 64; kk = tid / 64 + 4 * i; }   // A is K x N: consecutive lanes along N
-      else    { kk = tid % 16; r = tid / 16 + 16 * i; }  // A is N x K: consecutive lanes along K
-      const unsigned gr = row0 + r, gk = k0 + kk;
-      T v = (T)0;
-      if (gr < N && gk < K) v = AT ? A[(size_t)gk * N + gr] : A[(size_t)gr * K + gk];
-      As[kk][r] = v;
-    }
-    // stage B: 16 k x 64 cols
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const unsigned c = tid % 64, kk = tid / 64 + 4 * i;
-      const unsigned gc = col0 + c, gk = k0 + kk;
-      Bs[kk][c] = (gc < M && gk < K) ? B[(size_t)gk * M + gc] : (T)0;
-    }
-    __syncthreads();
-    const unsigned kmax = (K - k0) < (unsigned)kBK ? (K - k0) : (unsigned)kBK;
-    for (unsigned kk = 0; kk < kmax; ++kk) {  // strictly ascending k
-      T av[kPerThread], bv[kPerThread];
-#pragma unroll
-      for (int i = 0; i < kPerThread; ++i) av[i] = As[kk][ty * kPerThread + i];
-#pragma unroll
-      for (int j = 0; j < kPerThread; ++j) bv[j] = Bs[kk][tx + 16 * j];
-#pragma unroll
-      for (int i = 0; i < kPerThread; ++i)
-#pragma unroll
-        for (int j = 0; j < kPerThread; ++j)
-          acc[i][j] = Op<RED, ACC>::apply(acc[i][j], Op<MAP, ACC>::apply((ACC)av[i], (ACC)bv[j]));
-    }
-    __syncthreads();
-  }
-#pragma unroll
-  for (int i = 0; i < kPerThread; ++i) {
-    const unsigned gr = row0 + ty * kPerThread + i;
-    if (gr >= N) continue;
-#pragma unroll
-    for (int j = 0; j < kPerThread; ++j) {
-      const unsigned gc = col0 + tx + 16 * j;
-      if (gc < M) C[(size_t)gr * M + gc] = (T)acc[i][j];
-    }
-  }
+#define MM_ORDERED_BATCHED 0
+#include "mm_ordered_body.inc"
+#undef MM_ORDERED_BATCHED
 }
 
-template <typename T, int MAP, int RED>
+// `p.batch` elements of one shape in one launch: a 1-D grid of batch x tiles workgroups, element-major
+template <typename T, int MAP, int RED, bool AT, typename ACC = T>
+__global__ __launch_bounds__(256) void ordered_batched_kernel(const T *__restrict__ A, const T *__restrict__ B,
+                                                              T *__restrict__ C, unsigned N, unsigned K, unsigned M,
+                                                              size_t stride_a, size_t stride_b, size_t stride_c) {
+#define MM_ORDERED_BATCHED 1
+#include "mm_ordered_body.inc"
+#undef MM_ORDERED_BATCHED
+}
+
+// BATCHED: the p.batch elements of p (strides p.stride_*) in one launch of ordered_batched_kernel
+template <typename T, int MAP, int RED, bool BATCHED, typename ACC = T>
 int launch_t(hipStream_t s, const Problem &p) {
   if (p.n == 0 || p.m == 0) return 0;
+  if constexpr (BATCHED) {
+    const unsigned tiles = ((p.m + kTile - 1) / kTile) * ((p.n + kTile - 1) / kTile);
+    if (p.a_transposed)
+      hipLaunchKernelGGL((ordered_batched_kernel<T, MAP, RED, true, ACC>), dim3(tiles * p.batch), dim3(256), 0, s,
+                         (const T *)p.a, (const T *)p.b, (T *)p.c, p.n, p.k, p.m, p.stride_a, p.stride_b, p.stride_c);
+    else
+      hipLaunchKernelGGL((ordered_batched_kernel<T, MAP, RED, false, ACC>), dim3(tiles * p.batch), dim3(256), 0, s,
+                         (const T *)p.a, (const T *)p.b, (T *)p.c, p.n, p.k, p.m, p.stride_a, p.stride_b, p.stride_c);
+    return (int)hipGetLastError();
+  }
   dim3 grid((p.m + kTile - 1) / kTile, (p.n + kTile - 1) / kTile);
   if (p.a_transposed)
     hipLaunchKernelGGL((ordered_kernel<T, MAP, RED, true>), grid, dim3(256), 0, s, (const T *)p.a,
@@ -95,26 +62,44 @@ int launch_t(hipStream_t s, const Problem &p) {
   return (int)hipGetLastError();
 }
 
-template <typename T, int MAP>
+template <typename T, int MAP, bool BATCHED>
 int launch_red(hipStream_t s, int red, const Problem &p) {
   switch (red) {
-    case MM_OP_ADD: return launch_t<T, MAP, MM_OP_ADD>(s, p);
-    case MM_OP_MULTIPLY: return launch_t<T, MAP, MM_OP_MULTIPLY>(s, p);
-    case MM_OP_AND: return launch_t<T, MAP, MM_OP_AND>(s, p);
-    case MM_OP_MIN: return launch_t<T, MAP, MM_OP_MIN>(s, p);
-    case MM_OP_MAX: return launch_t<T, MAP, MM_OP_MAX>(s, p);
+    case MM_OP_ADD: return launch_t<T, MAP, MM_OP_ADD, BATCHED>(s, p);
+    case MM_OP_MULTIPLY: return launch_t<T, MAP, MM_OP_MULTIPLY, BATCHED>(s, p);
+    case MM_OP_AND: return launch_t<T, MAP, MM_OP_AND, BATCHED>(s, p);
+    case MM_OP_MIN: return launch_t<T, MAP, MM_OP_MIN, BATCHED>(s, p);
+    case MM_OP_MAX: return launch_t<T, MAP, MM_OP_MAX, BATCHED>(s, p);
   }
   return kErrNotSupported;
 }
 
-template <typename T>
+template <typename T, bool BATCHED>
 int launch_map(hipStream_t s, const mm_config_t &cfg, const Problem &p) {
   switch (cfg.map_op) {
-    case MM_OP_ADD: return launch_red<T, MM_OP_ADD>(s, cfg.reduce_op, p);
-    case MM_OP_MULTIPLY: return launch_red<T, MM_OP_MULTIPLY>(s, cfg.reduce_op, p);
-    case MM_OP_AND: return launch_red<T, MM_OP_AND>(s, cfg.reduce_op, p);
-    case MM_OP_MIN: return launch_red<T, MM_OP_MIN>(s, cfg.reduce_op, p);
-    case MM_OP_MAX: return launch_red<T, MM_OP_MAX>(s, cfg.reduce_op, p);
+    case MM_OP_ADD: return launch_red<T, MM_OP_ADD, BATCHED>(s, cfg.reduce_op, p);
+    case MM_OP_MULTIPLY: return launch_red<T, MM_OP_MULTIPLY, BATCHED>(s, cfg.reduce_op, p);
+    case MM_OP_AND: return launch_red<T, MM_OP_AND, BATCHED>(s, cfg.reduce_op, p);
+    case MM_OP_MIN: return launch_red<T, MM_OP_MIN, BATCHED>(s, cfg.reduce_op, p);
+    case MM_OP_MAX: return launch_red<T, MM_OP_MAX, BATCHED>(s, cfg.reduce_op, p);
+  }
+  return kErrNotSupported;
+}
+
+template <bool BATCHED>
+int launch_type(hipStream_t s, const mm_config_t &cfg, const Problem &p) {
+  switch (cfg.dtype) {
+    case MM_DTYPE_F32: return launch_map<float, BATCHED>(s, cfg, p);
+    case MM_DTYPE_F64: return launch_map<double, BATCHED>(s, cfg, p);
+    case MM_DTYPE_F16: return launch_map<half_t, BATCHED>(s, cfg, p);
+    case MM_DTYPE_I8: return launch_map<int8_t, BATCHED>(s, cfg, p);
+    case MM_DTYPE_U8: return launch_map<uint8_t, BATCHED>(s, cfg, p);
+    case MM_DTYPE_I16: return launch_map<int16_t, BATCHED>(s, cfg, p);
+    case MM_DTYPE_U16: return launch_map<uint16_t, BATCHED>(s, cfg, p);
+    case MM_DTYPE_I32: return launch_map<int32_t, BATCHED>(s, cfg, p);
+    case MM_DTYPE_U32: return launch_map<uint32_t, BATCHED>(s, cfg, p);
+    case MM_DTYPE_I64: return launch_map<int64_t, BATCHED>(s, cfg, p);
+    case MM_DTYPE_U64: return launch_map<uint64_t, BATCHED>(s, cfg, p);
   }
   return kErrNotSupported;
 }
@@ -133,21 +118,10 @@ int launch_half_wide(hipStream_t s, const Problem &p) {
   return (int)hipGetLastError();
 }
 
-int launch_ordered(hipStream_t s, const mm_config_t &cfg, const Problem &p) {
-  switch (cfg.dtype) {
-    case MM_DTYPE_F32: return launch_map<float>(s, cfg, p);
-    case MM_DTYPE_F64: return launch_map<double>(s, cfg, p);
-    case MM_DTYPE_F16: return launch_map<half_t>(s, cfg, p);
-    case MM_DTYPE_I8: return launch_map<int8_t>(s, cfg, p);
-    case MM_DTYPE_U8: return launch_map<uint8_t>(s, cfg, p);
-    case MM_DTYPE_I16: return launch_map<int16_t>(s, cfg, p);
-    case MM_DTYPE_U16: return launch_map<uint16_t>(s, cfg, p);
-    case MM_DTYPE_I32: return launch_map<int32_t>(s, cfg, p);
-    case MM_DTYPE_U32: return launch_map<uint32_t>(s, cfg, p);
-    case MM_DTYPE_I64: return launch_map<int64_t>(s, cfg, p);
-    case MM_DTYPE_U64: return launch_map<uint64_t>(s, cfg, p);
-  }
-  return kErrNotSupported;
+int launch_ordered(hipStream_t s, const mm_config_t &cfg, const Problem &p) { return launch_type<false>(s, cfg, p); }
+int launch_ordered_batched(hipStream_t s, const mm_config_t &cfg, const Problem &p) { return launch_type<true>(s, cfg, p); }
+int launch_half_wide_batched(hipStream_t s, const Problem &p) {
+  return launch_t<half_t, MM_OP_MULTIPLY, MM_OP_ADD, true, float>(s, p);
 }
 
 }  // namespace mm

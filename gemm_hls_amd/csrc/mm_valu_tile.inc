@@ -55,87 +55,24 @@ template <> struct FastOp<MM_OP_MAX, half_t> : Op<MM_OP_MAX, half_t> {
 };
 #endif
 
+
 template <typename T, int MAP, int RED, bool AT>
 __global__ __launch_bounds__(256) void valu_tile_kernel(const T *__restrict__ A, const T *__restrict__ B,
                                                         T *__restrict__ C, unsigned N, unsigned K, unsigned M,
                                                         unsigned tiles_n, unsigned tiles_m, unsigned kBand) {
-  __shared__ __attribute__((aligned(16))) T As[VT_BK][VT_BM + VT_PAD];
-  __shared__ __attribute__((aligned(16))) T Bs[VT_BK][VT_BN + VT_PAD];
-  const unsigned tid = threadIdx.x, tx = tid % 16, ty = tid / 16;
-  const unsigned lin = xcd_remap(blockIdx.x, tiles_n * tiles_m);
-  const unsigned band = lin / (kBand * tiles_m), within = lin % (kBand * tiles_m);
-  const unsigned rows_in_band = min(kBand, tiles_n - band * kBand);
-  const unsigned row0 = (band * kBand + within % rows_in_band) * VT_BM, col0 = (within / rows_in_band) * VT_BN;
+#define MM_VT_BATCHED 0
+#include "mm_valu_tile_body.inc"
+#undef MM_VT_BATCHED
+}
 
-  T acc[8][8];
-#pragma unroll
-  for (int i = 0; i < 8; ++i)
-#pragma unroll
-    for (int j = 0; j < 8; ++j) acc[i][j] = Op<RED, T>::identity();
-
-  using V = Vec4<T>;
-  for (unsigned k0 = 0; k0 < K; k0 += VT_BK) {
-    // ---- stage (K % 4 == 0, so a 4-wide k chunk is entirely inside or entirely outside) ----
-#pragma unroll
-    for (int u = 0; u < 2; ++u) {
-      const unsigned idx = tid + 256 * u;
-      if (AT) {  // A is K x N: rows of the tile are contiguous
-        const unsigned kr = idx / 32, r4 = (idx % 32) * 4;
-        V v = {};
-        if (k0 + kr < K && row0 + r4 < N) v = *(const V *)(A + (size_t)(k0 + kr) * N + row0 + r4);
-        *(V *)&As[kr][r4] = v;
-      } else {   // A is N x K: 4 lanes cover one row's 16 k; scatter into the k-major image
-        const unsigned r = idx / 4, kc = (idx % 4) * 4;
-        V v = {};
-        if (row0 + r < N && k0 + kc < K) v = *(const V *)(A + (size_t)(row0 + r) * K + k0 + kc);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) As[kc + e][r] = v.v[e];
-      }
-      {
-        const unsigned kr = idx / 32, c4 = (idx % 32) * 4;
-        V v = {};
-        if (k0 + kr < K && col0 + c4 < M) v = *(const V *)(B + (size_t)(k0 + kr) * M + col0 + c4);
-        *(V *)&Bs[kr][c4] = v;
-      }
-    }
-    __syncthreads();
-    const unsigned kmax = min((unsigned)VT_BK, K - k0);  // multiple of 4
-    for (unsigned kk = 0; kk < kmax; kk += 2) {
-      T a0[8], b0[8], a1[8], b1[8];
-      *(V *)&a0[0] = *(const V *)&As[kk][ty * 4];
-      *(V *)&a0[4] = *(const V *)&As[kk][64 + ty * 4];
-      *(V *)&b0[0] = *(const V *)&Bs[kk][tx * 4];
-      *(V *)&b0[4] = *(const V *)&Bs[kk][64 + tx * 4];
-      *(V *)&a1[0] = *(const V *)&As[kk + 1][ty * 4];
-      *(V *)&a1[4] = *(const V *)&As[kk + 1][64 + ty * 4];
-      *(V *)&b1[0] = *(const V *)&Bs[kk + 1][tx * 4];
-      *(V *)&b1[4] = *(const V *)&Bs[kk + 1][64 + tx * 4];
-#pragma unroll
-      for (int i = 0; i < 8; ++i)
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          const T s0 = FastOp<MAP, T>::apply(a0[i], b0[j]);
-          const T s1 = FastOp<MAP, T>::apply(a1[i], b1[j]);
-          acc[i][j] = FastOp<RED, T>::apply(FastOp<RED, T>::apply(acc[i][j], s0), s1);  // k, then k+1
-        }
-    }
-    __syncthreads();
-  }
-#pragma unroll
-  for (int i = 0; i < 8; ++i) {
-    const unsigned r = row0 + (i < 4 ? ty * 4 + i : 64 + ty * 4 + (i - 4));
-    if (r >= N) continue;
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-      const unsigned c = col0 + h * 64 + tx * 4;
-      if (c < M) {
-        V v;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) v.v[e] = acc[i][h * 4 + e];
-        *(V *)(C + (size_t)r * M + c) = v;
-      }
-    }
-  }
+template <typename T, int MAP, int RED, bool AT>
+__global__ __launch_bounds__(256) void valu_tile_batched_kernel(const T *__restrict__ A, const T *__restrict__ B,
+                                                        T *__restrict__ C, unsigned N, unsigned K, unsigned M,
+                                                        unsigned tiles_n, unsigned tiles_m, unsigned kBand,
+    unsigned batch, size_t stride_a, size_t stride_b, size_t stride_c) {
+#define MM_VT_BATCHED 1
+#include "mm_valu_tile_body.inc"
+#undef MM_VT_BATCHED
 }
 
 
@@ -166,117 +103,19 @@ template <typename T, int MAP, int RED, int TI>
 __global__ __launch_bounds__(TI == 8 ? 256 : 512, TI == 8 ? 1 : 4) void valu_tile_dma_kernel(const T *__restrict__ A, const T *__restrict__ B,
                                                             T *__restrict__ C, unsigned N, unsigned K, unsigned M,
                                                             unsigned tiles_n, unsigned tiles_m, unsigned kBand) {
-  static_assert(TI == 8 || TI == 4, "rows per thread");
-  constexpr unsigned ES = sizeof(T), EPC = 16 / ES, BK = 64 / ES;   // bytes, elements per 16-B chunk, slab depth
-  constexpr unsigned LPR = 8 * ES, KRP = 64 / LPR;                  // lanes per B k-row (128 cols), k-rows per 1-KiB piece
-  constexpr unsigned NW = TI == 8 ? 4 : 8, PW = 8 / NW;             // wavefronts; DMA pieces of A (and of B) per wavefront and slab
-  static_assert(VT_BN * ES * BK == VTD_A_BYTES && VT_BM == 128 && VT_BN == 128, "byte geometry");
-  __shared__ __attribute__((aligned(16))) char smem[2 * VTD_SLAB];
-  const unsigned tid = threadIdx.x, tx = tid % 16, ty = tid / 16;
-  const unsigned lane = tid & 63u, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const unsigned lin = xcd_remap(blockIdx.x, tiles_n * tiles_m);
-  const unsigned band = lin / (kBand * tiles_m), within = lin % (kBand * tiles_m);
-  const unsigned rows_in_band = min(kBand, tiles_n - band * kBand);
-  const unsigned row0 = (band * kBand + within % rows_in_band) * VT_BM, col0 = (within / rows_in_band) * VT_BN;
+#define MM_VT_BATCHED 0
+#include "mm_valu_tile_dma_body.inc"
+#undef MM_VT_BATCHED
+}
 
-  // DMA: 8 A pieces (16 rows x 64 B) and 8 B pieces (KRP k-rows x 128 cols) per slab, PW + PW per wave
-  unsigned voff_a[PW], voff_b[PW];
-#pragma unroll
-  for (unsigned i = 0; i < PW; ++i) {
-    const unsigned piece = wave + NW * i;
-    const unsigned row = piece * 16 + lane / 4, pc = lane % 4;
-    voff_a[i] = (min(row0 + row, N - 1) - row0) * K * ES + (pc ^ ((row >> 2) & 3u)) * 16;
-    const unsigned kr = piece * KRP + lane / LPR, c = (lane % LPR) * EPC;
-    voff_b[i] = kr * M * ES + (min(col0 + c, M - EPC) - col0) * ES;
-  }
-  const char *a_base = (const char *)A + (size_t)row0 * K * ES;
-  const char *b_base = (const char *)B + (size_t)col0 * ES;
-  const unsigned lds0 = (unsigned)(size_t)(__attribute__((address_space(3))) char *)smem;
-  const unsigned slabs = (K + BK - 1) / BK;
-  auto issue = [&](unsigned t) {  // slab t -> buffer t & 1; the last slab starts at K - BK
-    const unsigned k0 = min(t * BK, K - BK);
-    const char *ap = a_base + (size_t)k0 * ES;
-    const char *bp = b_base + (size_t)k0 * M * ES;
-    const unsigned la0 = lds0 + (t & 1u) * VTD_SLAB + wave * 1024, la1 = la0 + 4 * 1024;
-    const unsigned lb0 = la0 + VTD_A_BYTES, lb1 = lb0 + 4 * 1024;
-    unsigned keep;
-    if constexpr (PW == 2) {
-      asm volatile("s_mov_b32 %0, m0\n\t" MM_DMA_PIECE("%1", "%5", "%7") MM_DMA_PIECE("%2", "%5", "%8")
-                       MM_DMA_PIECE("%3", "%6", "%9") MM_DMA_PIECE("%4", "%6", "%10") "s_mov_b32 m0, %0"
-                   : "=&s"(keep)
-                   : "v"(voff_a[0]), "v"(voff_a[1]), "v"(voff_b[0]), "v"(voff_b[1]), "s"(ap), "s"(bp), "s"(la0), "s"(la1),
-                     "s"(lb0), "s"(lb1)
-                   : "memory");
-    } else {
-      asm volatile("s_mov_b32 %0, m0\n\t" MM_DMA_PIECE("%1", "%3", "%5") MM_DMA_PIECE("%2", "%4", "%6") "s_mov_b32 m0, %0"
-                   : "=&s"(keep)
-                   : "v"(voff_a[0]), "v"(voff_b[0]), "s"(ap), "s"(bp), "s"(la0), "s"(lb0)
-                   : "memory");
-    }
-  };
-
-  T acc[TI][8];
-#pragma unroll
-  for (int i = 0; i < TI; ++i)
-#pragma unroll
-    for (int j = 0; j < 8; ++j) acc[i][j] = Op<RED, T>::identity();
-
-  using V = Vec4<T>;
-  constexpr unsigned KSTEP = ES >= 4 ? 2 : 8 / ES;   // k per A read: 16 B (8-byte types) or 8 B
-  struct alignas(KSTEP * sizeof(T)) PK { T v[KSTEP]; };
-  // row i of this thread: TI == 8: ty*4 + i, then 64 + ty*4 + (i-4) (ty < 16); TI == 4: ty*4 + i (ty < 32).
-  // Either way all of a thread's rows have (row >> 2) & 3 == ty & 3
-  auto thread_row = [&](int i) -> unsigned { return TI == 8 ? (i < 4 ? ty * 4 + i : 64 + ty * 4 + (i - 4)) : ty * 4 + i; };
-  const unsigned a_swz = ty & 3u;
-  issue(0);
-  for (unsigned t = 0; t < slabs; ++t) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // own pieces of slab t have landed
-    __syncthreads();                                  // everybody's have; buffer (t+1)&1 is no longer being read
-    if (t + 1 < slabs) issue(t + 1);
-    const char *as = smem + (t & 1u) * VTD_SLAB;
-    const char *bs = as + VTD_A_BYTES;
-    // a full slab uses k 0..BK-1 of the buffer; the (shifted) last slab only its new k
-    const unsigned kbeg = t * BK - min(t * BK, K - BK);  // 0 except for a partial last slab
-    // one LDS read per row fetches KSTEP consecutive k (8 or 16 bytes: a pair for 4- and 8-byte types, 4 / 8 k for
-    // 2- / 1-byte types); the map-reduce steps then go pair by pair, k ascending
-    for (unsigned kk = kbeg; kk < BK; kk += KSTEP) {
-      PK av[TI];
-      const unsigned kb = kk * ES, aoff = (((kb >> 4) ^ a_swz) * 16) + (kb & 15u);
-#pragma unroll
-      for (int i = 0; i < TI; ++i) av[i] = *(const PK *)(as + thread_row(i) * 64 + aoff);
-#pragma unroll
-      for (unsigned q = 0; q < KSTEP; q += 2) {
-        T b0[8], b1[8];
-        *(V *)&b0[0] = *(const V *)(bs + ((kk + q) * VT_BN + tx * 4) * ES);
-        *(V *)&b0[4] = *(const V *)(bs + ((kk + q) * VT_BN + 64 + tx * 4) * ES);
-        *(V *)&b1[0] = *(const V *)(bs + ((kk + q + 1) * VT_BN + tx * 4) * ES);
-        *(V *)&b1[4] = *(const V *)(bs + ((kk + q + 1) * VT_BN + 64 + tx * 4) * ES);
-#pragma unroll
-        for (int i = 0; i < TI; ++i)
-#pragma unroll
-          for (int j = 0; j < 8; ++j) {
-            const T s0 = FastOp<MAP, T>::apply(av[i].v[q], b0[j]);
-            const T s1 = FastOp<MAP, T>::apply(av[i].v[q + 1], b1[j]);
-            acc[i][j] = FastOp<RED, T>::apply(FastOp<RED, T>::apply(acc[i][j], s0), s1);  // k, then k+1
-          }
-      }
-    }
-  }
-#pragma unroll
-  for (int i = 0; i < TI; ++i) {
-    const unsigned r = row0 + thread_row(i);
-    if (r >= N) continue;
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-      const unsigned c = col0 + h * 64 + tx * 4;
-      if (c < M) {
-        V v;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) v.v[e] = acc[i][h * 4 + e];
-        *(V *)(C + (size_t)r * M + c) = v;
-      }
-    }
-  }
+template <typename T, int MAP, int RED, int TI>
+__global__ __launch_bounds__(TI == 8 ? 256 : 512, TI == 8 ? 1 : 4) void valu_tile_dma_batched_kernel(const T *__restrict__ A, const T *__restrict__ B,
+                                                            T *__restrict__ C, unsigned N, unsigned K, unsigned M,
+                                                            unsigned tiles_n, unsigned tiles_m, unsigned kBand,
+    unsigned batch, size_t stride_a, size_t stride_b, size_t stride_c) {
+#define MM_VT_BATCHED 1
+#include "mm_valu_tile_dma_body.inc"
+#undef MM_VT_BATCHED
 }
 #undef MM_DMA_PIECE
 
@@ -289,9 +128,21 @@ bool vt_dma_serves(const Problem &p) {
          BK * (unsigned long long)p.m * ES < (1ull << 32);
 }
 
-template <typename T, int MAP, int RED>
+// BATCHED: p.batch elements of p's shape in one launch (the *_batched_kernel forms), same tile and kernel choice per element
+template <typename T, int MAP, int RED, bool BATCHED>
 int vt_launch(hipStream_t s, const Problem &p) {
   const unsigned tiles_n = (p.n + VT_BM - 1) / VT_BM, tiles_m = (p.m + VT_BN - 1) / VT_BN;
+  const unsigned grid = tiles_n * tiles_m * (BATCHED ? p.batch : 1u);
+  // the kernels' argument lists: the single problem's, plus the batch and the element strides for the batched forms
+#define MM_VT_LAUNCH(KERNEL, BATCHED_KERNEL, THREADS, BAND)                                                                   \
+  do {                                                                                                                      \
+    if constexpr (BATCHED)                                                                                                  \
+      hipLaunchKernelGGL(BATCHED_KERNEL, dim3(grid), dim3(THREADS), 0, s, (const T *)p.a, (const T *)p.b, (T *)p.c, p.n,   \
+                         p.k, p.m, tiles_n, tiles_m, BAND, p.batch, p.stride_a, p.stride_b, p.stride_c);                  \
+    else                                                                                                                    \
+      hipLaunchKernelGGL(KERNEL, dim3(grid), dim3(THREADS), 0, s, (const T *)p.a, (const T *)p.b, (T *)p.c, p.n, p.k, p.m, \
+                         tiles_n, tiles_m, BAND);                                                                           \
+  } while (0)
   // valu_variant knob: 0 = the synchronous kernel; 2 = the DMA-staged kernel with 8 rows per thread for the 8-byte types too
   // (their default since round 4 is 4 rows per thread on 512 threads: 4 wavefronts per SIMD; for the narrower types the same
   // form measured flat, 0.97-1.015 x the 8-row form over float / half / int / uint8, k-ordered and fast alike:
@@ -300,42 +151,41 @@ int vt_launch(hipStream_t s, const Problem &p) {
   if (vt_dma_serves<T>(p) && vv != 0) {
     if constexpr (sizeof(T) == 8) {
       if (vv != 2) {
-        hipLaunchKernelGGL((valu_tile_dma_kernel<T, MAP, RED, 4>), dim3(tiles_n * tiles_m), dim3(512), 0, s, (const T *)p.a,
-                           (const T *)p.b, (T *)p.c, p.n, p.k, p.m, tiles_n, tiles_m, band_rows(VT_BM, VT_BN, 2));
+        MM_VT_LAUNCH((valu_tile_dma_kernel<T, MAP, RED, 4>), (valu_tile_dma_batched_kernel<T, MAP, RED, 4>), 512,
+                     band_rows(VT_BM, VT_BN, 2));
         return (int)hipGetLastError();
       }
     }
-    hipLaunchKernelGGL((valu_tile_dma_kernel<T, MAP, RED, 8>), dim3(tiles_n * tiles_m), dim3(256), 0, s, (const T *)p.a,
-                       (const T *)p.b, (T *)p.c, p.n, p.k, p.m, tiles_n, tiles_m, band_rows(VT_BM, VT_BN, 2));
+    MM_VT_LAUNCH((valu_tile_dma_kernel<T, MAP, RED, 8>), (valu_tile_dma_batched_kernel<T, MAP, RED, 8>), 256,
+                 band_rows(VT_BM, VT_BN, 2));
     return (int)hipGetLastError();
   }
   if (p.a_transposed)
-    hipLaunchKernelGGL((valu_tile_kernel<T, MAP, RED, true>), dim3(tiles_n * tiles_m), dim3(256), 0, s,
-                       (const T *)p.a, (const T *)p.b, (T *)p.c, p.n, p.k, p.m, tiles_n, tiles_m, band_rows());
+    MM_VT_LAUNCH((valu_tile_kernel<T, MAP, RED, true>), (valu_tile_batched_kernel<T, MAP, RED, true>), 256, band_rows());
   else
-    hipLaunchKernelGGL((valu_tile_kernel<T, MAP, RED, false>), dim3(tiles_n * tiles_m), dim3(256), 0, s,
-                       (const T *)p.a, (const T *)p.b, (T *)p.c, p.n, p.k, p.m, tiles_n, tiles_m, band_rows());
+    MM_VT_LAUNCH((valu_tile_kernel<T, MAP, RED, false>), (valu_tile_batched_kernel<T, MAP, RED, false>), 256, band_rows());
+#undef MM_VT_LAUNCH
   return (int)hipGetLastError();
 }
 
-template <typename T, int MAP>
+template <typename T, int MAP, bool BATCHED>
 int vt_red(hipStream_t s, int red, const Problem &p) {
   switch (red) {
-    case MM_OP_ADD: return vt_launch<T, MAP, MM_OP_ADD>(s, p);
-    case MM_OP_MIN: return vt_launch<T, MAP, MM_OP_MIN>(s, p);
-    case MM_OP_MAX: return vt_launch<T, MAP, MM_OP_MAX>(s, p);
+    case MM_OP_ADD: return vt_launch<T, MAP, MM_OP_ADD, BATCHED>(s, p);
+    case MM_OP_MIN: return vt_launch<T, MAP, MM_OP_MIN, BATCHED>(s, p);
+    case MM_OP_MAX: return vt_launch<T, MAP, MM_OP_MAX, BATCHED>(s, p);
   }
   return kErrNotSupported;  // Multiply / And reductions: ordered kernel
 }
 
-template <typename T>
+template <typename T, bool BATCHED = false>
 int vt_type(hipStream_t s, const mm_config_t &cfg, const Problem &p) {
   if (p.k % 4 != 0 || p.m % 4 != 0 || (p.a_transposed && p.n % 4 != 0)) return kErrNotSupported;
   switch (cfg.map_op) {
-    case MM_OP_MULTIPLY: return vt_red<T, MM_OP_MULTIPLY>(s, cfg.reduce_op, p);
-    case MM_OP_ADD: return vt_red<T, MM_OP_ADD>(s, cfg.reduce_op, p);
-    case MM_OP_MIN: return vt_red<T, MM_OP_MIN>(s, cfg.reduce_op, p);
-    case MM_OP_MAX: return vt_red<T, MM_OP_MAX>(s, cfg.reduce_op, p);
+    case MM_OP_MULTIPLY: return vt_red<T, MM_OP_MULTIPLY, BATCHED>(s, cfg.reduce_op, p);
+    case MM_OP_ADD: return vt_red<T, MM_OP_ADD, BATCHED>(s, cfg.reduce_op, p);
+    case MM_OP_MIN: return vt_red<T, MM_OP_MIN, BATCHED>(s, cfg.reduce_op, p);
+    case MM_OP_MAX: return vt_red<T, MM_OP_MAX, BATCHED>(s, cfg.reduce_op, p);
     default: break;
   }
   return kErrNotSupported;  // And map: ordered kernel

@@ -4,6 +4,9 @@ namespace mm {
 int launch_valu_tile_fp(hipStream_t s, const mm_config_t &cfg, const Problem &p);
 int launch_valu_tile_int_narrow(hipStream_t s, const mm_config_t &cfg, const Problem &p);
 int launch_valu_tile_fp_exact(hipStream_t s, const mm_config_t &cfg, const Problem &p);   // mm_valu_tile_fp_exact.hip
+int launch_valu_tile_fp_batched(hipStream_t s, const mm_config_t &cfg, const Problem &p);
+int launch_valu_tile_int_narrow_batched(hipStream_t s, const mm_config_t &cfg, const Problem &p);
+int launch_valu_tile_fp_exact_batched(hipStream_t s, const mm_config_t &cfg, const Problem &p);
 bool valu_tile_serves(const mm_config_t &cfg, const Problem &p) {
   if (p.k % 4 != 0 || p.m % 4 != 0 || (p.a_transposed && p.n % 4 != 0)) return false;
   const bool map_ok = cfg.map_op == MM_OP_MULTIPLY || cfg.map_op == MM_OP_ADD || cfg.map_op == MM_OP_MIN || cfg.map_op == MM_OP_MAX;
@@ -27,6 +30,27 @@ int launch_valu_tile(hipStream_t s, const mm_config_t &cfg, const Problem &p) {
     case MM_DTYPE_U32: return vt_type<uint32_t>(s, cfg, p);
     case MM_DTYPE_I64: return vt_type<int64_t>(s, cfg, p);
     case MM_DTYPE_U64: return vt_type<uint64_t>(s, cfg, p);
+  }
+  return kErrNotSupported;
+}
+
+// the batched forms of the two launchers above (p.batch elements, strides p.stride_*): the same kernel per element
+int launch_valu_tile_exact_batched(hipStream_t s, const mm_config_t &cfg, const Problem &p) {
+  switch (cfg.dtype) {
+    case MM_DTYPE_F32: case MM_DTYPE_F64: case MM_DTYPE_F16: return launch_valu_tile_fp_exact_batched(s, cfg, p);
+    default: return launch_valu_tile_batched(s, cfg, p);
+  }
+}
+
+int launch_valu_tile_batched(hipStream_t s, const mm_config_t &cfg, const Problem &p) {
+  switch (cfg.dtype) {
+    case MM_DTYPE_F32: case MM_DTYPE_F64: case MM_DTYPE_F16: return launch_valu_tile_fp_batched(s, cfg, p);
+    case MM_DTYPE_I8: case MM_DTYPE_U8: case MM_DTYPE_I16: case MM_DTYPE_U16:
+      return launch_valu_tile_int_narrow_batched(s, cfg, p);
+    case MM_DTYPE_I32: return vt_type<int32_t, true>(s, cfg, p);
+    case MM_DTYPE_U32: return vt_type<uint32_t, true>(s, cfg, p);
+    case MM_DTYPE_I64: return vt_type<int64_t, true>(s, cfg, p);
+    case MM_DTYPE_U64: return vt_type<uint64_t, true>(s, cfg, p);
   }
   return kErrNotSupported;
 }

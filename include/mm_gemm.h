@@ -173,6 +173,28 @@ int mm_gemm_enqueue(void *hip_stream, const mm_config_t *cfg, const void *a_dev,
                     const void *b_dev, void *c_dev, unsigned size_n, unsigned size_k,
                     unsigned size_m);
 
+/* Strided batch: `batch` independent problems of one shape in one call (torch.bmm's role).  Element e is the single
+ * problem at a_dev + e * stride_a, b_dev + e * stride_b, c_dev + e * stride_c; strides count ELEMENTS, each matrix is
+ * dense row-major (A: N x K, or K x N with MM_A_TRANSPOSED).  stride_a or stride_b 0 = one operand shared by every
+ * element (broadcast).  With batch > 1, stride_c < N * M is refused (MM_ERR_BAD_ARGUMENT: the outputs would overlap).
+ * batch, N or M 0: nothing to do, MM_OK; K 0: refused.  Every argument is checked before any device is touched.
+ * Alignment per element as for the single launch: MM_PATH_AUTO needs every element's a, b and c 16-byte aligned (bases,
+ * and each stride times the element size a multiple of 16), else MM_ERR_BAD_ARGUMENT; MM_PATH_ORDERED takes any
+ * element-aligned pointer and strides.  MM_PATH_SPLIT: MM_ERR_UNSUPPORTED (it needs workspace).  A batched launch never
+ * allocates workspace and never splits K: per element, MM_PATH_ORDERED gives Naive's bits, integer types and Min / Max /
+ * And reductions under MM_PATH_AUTO the bits of mm_gemm_launch on that element alone, floating (Multiply, Add) the same
+ * contract and error bound as the single launch in a summation order that may differ from it.  An element's bits do not
+ * depend on its position, the other elements, the strides or how the batch is split into launches ("batch_chunk").
+ * Batches beyond a grid limit run as consecutive launches on the same stream.
+ * _enqueue: asynchronous on a caller-provided hipStream_t of the CURRENT device (like mm_gemm_enqueue); _launch: blocking,
+ * *elapsed_seconds (may be NULL) = the whole batch, all launches, timed with HIP events. */
+int mm_gemm_batched_enqueue(void *hip_stream, const mm_config_t *cfg, const void *a_dev, const void *b_dev, void *c_dev,
+                            unsigned size_n, unsigned size_k, unsigned size_m, unsigned batch,
+                            size_t stride_a, size_t stride_b, size_t stride_c);
+int mm_gemm_batched_launch(int device, const mm_config_t *cfg, const void *a_dev, const void *b_dev, void *c_dev,
+                           unsigned size_n, unsigned size_k, unsigned size_m, unsigned batch,
+                           size_t stride_a, size_t stride_b, size_t stride_c, double *elapsed_seconds);
+
 /* One node, `device_count` GPUs, rows of C split into contiguous slabs (device g gets the rows mm_row_slab() names), B
  * replicated, no collective: every outer tile of C is independent (kernel/Compute.cpp:53-60, kernel/Memory.cpp:114-127,
  * 272-286, 367-391).  Host pointers in, host pointer out; copies are outside the timed region exactly as in
@@ -233,6 +255,9 @@ int mm_config_supported(const mm_config_t *cfg);
 /* Name of the kernel family that mm_gemm_launch would run for this problem (static string),
  * e.g. "mfma_f32_128x256x32", "valu_tile", "ordered". */
 const char *mm_kernel_name(const mm_config_t *cfg, unsigned size_n, unsigned size_k, unsigned size_m);
+/* Name of the kernel family mm_gemm_batched_launch would run for `batch` elements of this shape (static string; pure
+ * arithmetic, the batched launcher's own resolver). */
+const char *mm_kernel_name_batched(const mm_config_t *cfg, unsigned size_n, unsigned size_k, unsigned size_m, unsigned batch);
 /* Geometry of the kernel family that would serve this problem: the GPU counterpart of the
  * constants src/PrintSpecifications.cpp prints for the FPGA build (memory tile = the output tile a
  * workgroup keeps resident, compute tile = what one wavefront instruction computes). */
@@ -249,7 +274,8 @@ typedef struct {
 int mm_kernel_info(const mm_config_t *cfg, unsigned size_n, unsigned size_k, unsigned size_m,
                    mm_kernel_info_t *info);
 /* Tuning knobs for sweeps ("f32_variant", "f64_variant", "f16_variant", "i8_variant", "valu_variant", "split_variant",
- * "band_rows", "f32_splitk", "ordered_variant"; -1 = the library's own choice) and ONE contract knob, "half_contract"
+ * "band_rows", "f32_splitk", "ordered_variant", "batch_chunk" = the most elements one batched launch holds, for tests;
+ * -1 = the library's own choice) and ONE contract knob, "half_contract"
  * (MM_HALF_CONTRACT = reference | wide; 1 = reference: half (Multiply, Add) under MM_PATH_AUTO is evaluated like the reference's
  * kernel -- binary16 products, binary16 accumulation, k ascending -- on the k-ordered tile kernel; unset / 0: f32 accumulation on
  * the matrix cores).  Kernel ids of this library: f32_variant 33 / 8 / 35 / 64 (the

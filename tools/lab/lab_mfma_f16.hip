@@ -1251,4 +1251,9 @@ int launch_mfma_f16(hipStream_t s, const Problem &p) {
   return launch_h<GeoH>(s, p);
 }
 
+// The lab edition has no batched form: mm_gemm_batched_* of this library run half (Multiply, Add) on the fallback families
+int mfma_f16_batched_resolve(const Problem &) { return -1; }
+const char *mfma_f16_batched_name(const Problem &) { return "unsupported"; }
+int launch_mfma_f16_batched(hipStream_t, const Problem &, int) { return kErrNotSupported; }
+
 }  // namespace mm

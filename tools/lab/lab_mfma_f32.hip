@@ -947,6 +947,9 @@ static bool sdma_fits(const Problem &p, unsigned bk) {
 }
 
 int mfma_f32_splitk(const Problem &, int) { return 1; }   // the lab edition never splits K
+// ... and has no batched form: mm_gemm_batched_* of this library run fp32 (Multiply, Add) on the VALU families
+int mfma_f32_batched_resolve(const Problem &, int) { return -1; }
+int launch_mfma_f32_batched(hipStream_t, const Problem &, int) { return kErrNotSupported; }
 
 int mfma_f32_resolve(const Problem &p, int variant) {
   if (!mfma_f32_serves(p)) return -1;
