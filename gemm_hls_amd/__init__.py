@@ -25,7 +25,8 @@ EXPORTS = ["mm_init", "mm_alloc", "mm_free", "mm_copy_to_device", "mm_copy_to_ho
            "mm_config_supported", "mm_kernel_name", "mm_kernel_info", "mm_last_error",
            "mm_gemm_host", "mm_tuning_set", "mm_tuning_get", "mm_release_workspace", "mm_device_pci_bus_id",
            "mm_row_slab", "mm_gemm_multi_device_timed", "mm_gemm_batched_enqueue", "mm_gemm_batched_launch",
-           "mm_kernel_name_batched"]
+           "mm_kernel_name_batched", "mm_gemm_accumulate_enqueue", "mm_gemm_accumulate_launch",
+           "mm_gemm_batched_accumulate_enqueue", "mm_gemm_batched_accumulate_launch"]
 
 
 class MMError(RuntimeError):
@@ -98,6 +99,11 @@ def lib():
         L.mm_gemm_batched_launch.argtypes = [i, cfgp, vp, vp, vp, u, u, u, u, sz, sz, sz, ctypes.POINTER(ctypes.c_double)]
         L.mm_kernel_name_batched.argtypes = [cfgp, u, u, u, u]
         L.mm_kernel_name_batched.restype = ctypes.c_char_p
+        L.mm_gemm_accumulate_enqueue.argtypes = [vp, cfgp, vp, vp, vp, u, u, u]
+        L.mm_gemm_accumulate_launch.argtypes = [i, cfgp, vp, vp, vp, u, u, u, ctypes.POINTER(ctypes.c_double)]
+        L.mm_gemm_batched_accumulate_enqueue.argtypes = [vp, cfgp, vp, vp, vp, u, u, u, u, sz, sz, sz]
+        L.mm_gemm_batched_accumulate_launch.argtypes = [i, cfgp, vp, vp, vp, u, u, u, u, sz, sz, sz,
+                                                        ctypes.POINTER(ctypes.c_double)]
         _lib = L
     return _lib
 
@@ -244,6 +250,74 @@ def bmm(a, b, dtype="float", map_op="Multiply", reduce_op="Add", path=PATH_AUTO,
         _check(lib().mm_gemm_batched_enqueue(ctypes.c_void_p(stream), ctypes.byref(cfg), a.data_ptr(), b.data_ptr(),
                                              out.data_ptr(), n, k, m, batch, sa, sb, n * m))
     return out
+
+
+def _device_operands(what, tdt, *xs):
+    """The checks every torch entry point makes: device tensors of one device and of the configuration's dtype."""
+    if not all(x.is_cuda for x in xs):
+        raise MMError(f"{what} needs device tensors: there is no CPU path")
+    if any(x.device != xs[0].device for x in xs):
+        raise MMError(f"operands live on different devices: {', '.join(str(x.device) for x in xs)}")
+    if any(x.dtype != tdt for x in xs):
+        raise MMError(f"operand dtypes {', '.join(str(x.dtype) for x in xs)} do not match {tdt}")
+
+
+def addmm_(c, a, b, dtype="float", map_op="Multiply", reduce_op="Add", path=PATH_AUTO, transposed_a=False):
+    """In place C <- C (+) (A (x) B) on torch's current stream (mm_gemm_accumulate_enqueue): each output's reduction starts
+    at the value C holds instead of identity() -- torch.addmm_ for (Multiply, Add), D <- min(D, A + B) for (Add, Min).
+    a: (N, K) -- or (K, N) with transposed_a -- b: (K, M), c: (N, M); contiguous device tensors of `dtype`, C not
+    overlapping A or B.  Returns c.  Asynchronous, like any torch op."""
+    tdt = torch_dtype(dtype)
+    _device_operands("addmm_", tdt, c, a, b)
+    if a.dim() != 2 or b.dim() != 2 or c.dim() != 2:
+        raise MMError("addmm_ takes 2-D operands")
+    if not (a.is_contiguous() and b.is_contiguous() and c.is_contiguous()):
+        raise MMError("addmm_ needs contiguous (row-major) operands")
+    k, m = b.shape
+    n = a.shape[1] if transposed_a else a.shape[0]
+    if (a.shape[0] if transposed_a else a.shape[1]) != k:
+        raise MMError(f"inner dimensions differ: A {tuple(a.shape)}{' (K x N)' if transposed_a else ''}, B {tuple(b.shape)}")
+    if tuple(c.shape) != (n, m):
+        raise MMError(f"c has shape {tuple(c.shape)}, expected {(n, m)}")
+    import torch
+    cfg = make_config(dtype, map_op, reduce_op, path, transposed_a)
+    with torch.cuda.device(a.device):
+        stream = torch.cuda.current_stream(a.device).cuda_stream
+        _check(lib().mm_gemm_accumulate_enqueue(ctypes.c_void_p(stream), ctypes.byref(cfg), a.data_ptr(), b.data_ptr(),
+                                                c.data_ptr(), n, k, m))
+    return c
+
+
+def baddbmm_(c, a, b, dtype="float", map_op="Multiply", reduce_op="Add", path=PATH_AUTO, transposed_a=False):
+    """Strided-batched in place C[e] <- C[e] (+) (A[e] (x) B[e]) on torch's current stream
+    (mm_gemm_batched_accumulate_enqueue) -- torch.baddbmm_ for (Multiply, Add).  a and b as for bmm (2-D, 3-D, or expanded
+    with batch stride 0); c: (B, N, M) with dense row-major matrices and a batch stride of at least N * M (2-D when B is 1),
+    not overlapping A or B.  Returns c.  Asynchronous, like any torch op."""
+    import torch
+    tdt = torch_dtype(dtype)
+    _device_operands("baddbmm_", tdt, c, a, b)
+    if a.dim() not in (2, 3) or b.dim() not in (2, 3) or c.dim() not in (2, 3):
+        raise MMError("baddbmm_ takes 2-D or 3-D operands")
+    k, m = b.shape[-2], b.shape[-1]
+    n = a.shape[-1] if transposed_a else a.shape[-2]
+    if (a.shape[-2] if transposed_a else a.shape[-1]) != k:
+        raise MMError(f"inner dimensions differ: A {tuple(a.shape)}{' (K x N)' if transposed_a else ''}, B {tuple(b.shape)}")
+    ba, sa = _batched_operand(a, "a", *((k, n) if transposed_a else (n, k)))
+    bb, sb = _batched_operand(b, "b", k, m)
+    bc, sc = _batched_operand(c, "c", n, m)
+    batches = {x for x in (ba, bb) if x is not None and x != 1}
+    if len(batches) > 1:
+        raise MMError(f"batch sizes differ: {ba} and {bb}")
+    batch = batches.pop() if batches else (bc or 1)
+    if (bc or 1) != batch or (batch > 1 and sc == 0):
+        raise MMError(f"c has shape {tuple(c.shape)} (batch stride {c.stride(0) if c.dim() == 3 else None}), expected "
+                      f"{batch} distinct ({n}, {m}) matrices")
+    cfg = make_config(dtype, map_op, reduce_op, path, transposed_a)
+    with torch.cuda.device(a.device):
+        stream = torch.cuda.current_stream(a.device).cuda_stream
+        _check(lib().mm_gemm_batched_accumulate_enqueue(ctypes.c_void_p(stream), ctypes.byref(cfg), a.data_ptr(),
+                                                        b.data_ptr(), c.data_ptr(), n, k, m, batch, sa, sb, sc))
+    return c
 
 
 def row_slab(cfg, n, k, m, world_size, rank):

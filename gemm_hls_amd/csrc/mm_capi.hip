@@ -324,6 +324,43 @@ mm::Problem batched_problem(const mm_config_t *cfg, const void *a, const void *b
   return p;
 }
 
+// ---- accumulate (mm_gemm_*accumulate_*): C <- C (+) (A (x) B) -------------------------------------------------------
+// Bytes an operand of the batch can touch: [base, base + ((batch - 1) * stride + extent) * es), extent = its elements.
+size_t batch_span(size_t extent, size_t stride, unsigned batch, size_t es) {
+  return extent ? ((size_t)(batch - 1) * stride + extent) * es : 0;
+}
+bool spans_overlap(const void *x, size_t xbytes, const void *y, size_t ybytes) {
+  const uintptr_t x0 = (uintptr_t)x, y0 = (uintptr_t)y;
+  return xbytes && ybytes && x0 < y0 + ybytes && y0 < x0 + xbytes;
+}
+
+// The batched call's checks (check_batched), K = 0 accepted, and C refused where its span overlaps A's or B's (a
+// conservative test: the kernels read A and B while other workgroups already write C).  *fam = FAM_NONE: nothing to
+// launch (an empty batch, or K = 0: C keeps its value).
+int check_accumulate(const mm_config_t *cfg, const mm::Problem &p, Family *fam) {
+  *fam = FAM_NONE;
+  if (!valid_cfg(cfg)) return fail(MM_ERR_BAD_ARGUMENT, "invalid mm_config_t");
+  if (p.k > 0) {
+    int rc = check_batched(cfg, p, fam);
+    if (rc || *fam == FAM_NONE) return rc;
+  } else {   // K = 0: the same checks on a problem that has no k, then nothing to do
+    mm::Problem q = p;
+    q.k = 1;
+    Family f;
+    if (int rc = check_batched(cfg, q, &f)) return rc;
+    if (f == FAM_NONE) return MM_OK;
+  }
+  const size_t es = mm_dtype_size(cfg->dtype);
+  const size_t c_bytes = batch_span((size_t)p.n * p.m, p.stride_c, p.batch, es);
+  if (spans_overlap(p.c, c_bytes, p.a, batch_span((size_t)p.n * p.k, p.stride_a, p.batch, es)) ||
+      spans_overlap(p.c, c_bytes, p.b, batch_span((size_t)p.k * p.m, p.stride_b, p.batch, es))) {
+    *fam = FAM_NONE;
+    return fail(MM_ERR_BAD_ARGUMENT, "c overlaps a or b (bases %p, %p, %p): an accumulating call updates C in place and reads "
+                "A and B meanwhile; pass a copy", p.a, p.b, p.c);
+  }
+  return MM_OK;
+}
+
 // hipEvent_t with a destructor: no exit path of the timed launch can leak one
 struct Event {
   hipEvent_t e = nullptr;
@@ -586,6 +623,59 @@ int mm_gemm_batched_launch(int device, const mm_config_t *cfg, const void *a, co
     *elapsed_seconds = 1e-3 * (double)ms;
   }
   return MM_OK;
+}
+
+int mm_gemm_batched_accumulate_enqueue(void *hip_stream, const mm_config_t *cfg, const void *a, const void *b, void *c,
+                                       unsigned n, unsigned k, unsigned m, unsigned batch, size_t stride_a, size_t stride_b,
+                                       size_t stride_c) {
+  mm::Problem p = batched_problem(cfg, a, b, c, n, k, m, batch, stride_a, stride_b, stride_c);
+  p.seed = true;
+  Family fam;
+  int rc = check_accumulate(cfg, p, &fam);
+  if (rc || fam == FAM_NONE) return rc;   // (FAM_NONE: an empty batch or K = 0, nothing to do)
+  if ((rc = ensure_init())) return rc;
+  return dispatch_batched((hipStream_t)hip_stream, *cfg, p, fam);
+}
+
+int mm_gemm_batched_accumulate_launch(int device, const mm_config_t *cfg, const void *a, const void *b, void *c, unsigned n,
+                                      unsigned k, unsigned m, unsigned batch, size_t stride_a, size_t stride_b,
+                                      size_t stride_c, double *elapsed_seconds) {
+  mm::Problem p = batched_problem(cfg, a, b, c, n, k, m, batch, stride_a, stride_b, stride_c);
+  p.seed = true;
+  Family fam;
+  int rc = check_accumulate(cfg, p, &fam);
+  if (rc) return rc;
+  if (fam == FAM_NONE) {   // an empty batch or K = 0: nothing to launch or time
+    if (elapsed_seconds) *elapsed_seconds = 0.0;
+    return MM_OK;
+  }
+  if ((rc = check_device(device))) return rc;
+  MM_HIP(hipSetDevice(device));
+  Event start, stop;
+  MM_HIP(hipEventCreate(&start.e));
+  MM_HIP(hipEventCreate(&stop.e));
+  MM_HIP(hipEventRecord(start.e, nullptr));
+  rc = dispatch_batched(nullptr, *cfg, p, fam);
+  if (rc != MM_OK) return rc;
+  MM_HIP(hipEventRecord(stop.e, nullptr));
+  MM_HIP(hipEventSynchronize(stop.e));
+  if (elapsed_seconds) {
+    float ms = 0.f;
+    MM_HIP(hipEventElapsedTime(&ms, start.e, stop.e));
+    *elapsed_seconds = 1e-3 * (double)ms;
+  }
+  return MM_OK;
+}
+
+// The single accumulating launch is a batch of one: the batched kernel mm_kernel_name_batched(cfg, n, k, m, 1) names.
+int mm_gemm_accumulate_enqueue(void *hip_stream, const mm_config_t *cfg, const void *a, const void *b, void *c, unsigned n,
+                               unsigned k, unsigned m) {
+  return mm_gemm_batched_accumulate_enqueue(hip_stream, cfg, a, b, c, n, k, m, 1, 0, 0, 0);
+}
+
+int mm_gemm_accumulate_launch(int device, const mm_config_t *cfg, const void *a, const void *b, void *c, unsigned n,
+                              unsigned k, unsigned m, double *elapsed_seconds) {
+  return mm_gemm_batched_accumulate_launch(device, cfg, a, b, c, n, k, m, 1, 0, 0, 0, elapsed_seconds);
 }
 
 // Rows per device of the N split: ceil(N / G) rounded up to whole tile rows of the kernel that will run on a slab of that

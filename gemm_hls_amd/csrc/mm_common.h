@@ -93,6 +93,9 @@ struct Problem {
   // these; every other launcher runs the one problem at (a, b, c).
   unsigned batch = 1;
   size_t stride_a = 0, stride_b = 0, stride_c = 0;
+  // accumulate (mm_gemm_*accumulate_*): C <- C (+) (A (x) B), each output's reduction starts at the value C holds instead
+  // of identity().  Only the *_batched launchers read it (they then run the kernels' *_batched_seeded forms).
+  bool seed = false;
 };
 
 // Batched launches: `p.batch` copies of the tile grid in ONE launch; the kernel derives the element from the workgroup id

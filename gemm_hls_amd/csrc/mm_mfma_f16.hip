@@ -100,6 +100,9 @@ __device__ __forceinline__ h8 join(s4 lo, s4 hi) {
 #undef MM_BATCHED
 #define MM_BATCHED 1
 #include "mm_mfma_f16_kernels.inc"
+#define MM_SEEDED 1
+#include "mm_mfma_f16_kernels.inc"
+#undef MM_SEEDED
 #undef MM_BATCHED
 
 #undef MM_DMA_PIECE
@@ -245,20 +248,25 @@ static Kind resolve_batched(const Problem &p) {
 int mfma_f16_batched_resolve(const Problem &p) { const Kind k = resolve_batched(p); return k == K_NONE ? -1 : (int)k; }
 const char *mfma_f16_batched_name(const Problem &p) { return kNames[resolve_batched(p)]; }
 int launch_mfma_f16_batched(hipStream_t s, const Problem &p, int kind) {
-  static unsigned long long bcfg[K_NONE] = {};
+  static unsigned long long bcfg[K_NONE] = {}, scfg[K_NONE] = {};
   if (kind < 0 || kind >= (int)K_NONE) return kErrNotSupported;
   const Kind k = (Kind)kind;
-  switch (k) {
-    case K_PP16: return launch_tile_batched(s, p, mfma_f16_pp2s_kernel_batched, 256, 256, GeoPP2::THREADS, GeoPP2::LDS_BYTES, bcfg[k]);
-    case K_PP32: return launch_tile_batched(s, p, mfma_f16_pp2_kernel_batched, 256, 256, GeoPP2::THREADS, GeoPP2::LDS_BYTES, bcfg[k]);
-    case K_PPK32: return launch_tile_batched(s, p, mfma_f16_pp_kernel_batched<false>, 256, 256, GeoPP::THREADS, GeoPP::LDS_BYTES, bcfg[k]);
-    case K_PPK32_AT: return launch_tile_batched(s, p, mfma_f16_pp_kernel_batched<true>, 256, 256, GeoPP::THREADS, GeoPP::LDS_BYTES, bcfg[k]);
-    case K_SLAB64: return launch_tile_batched(s, p, mfma_f16_kernel_batched<GeoH, false>, GeoH::BM, GeoH::BN, GeoH::THREADS, GeoH::LDS_BYTES, bcfg[k]);
-    case K_SLAB64_AT: return launch_tile_batched(s, p, mfma_f16_kernel_batched<GeoH, true>, GeoH::BM, GeoH::BN, GeoH::THREADS, GeoH::LDS_BYTES, bcfg[k]);
-    case K_SLAB64_128: return launch_tile_batched(s, p, mfma_f16_kernel_batched<GeoHS, false>, GeoHS::BM, GeoHS::BN, GeoHS::THREADS, GeoHS::LDS_BYTES, bcfg[k]);
-    case K_SLAB64_64: return launch_tile_batched(s, p, mfma_f16_kernel_batched<GeoHXS, false>, GeoHXS::BM, GeoHXS::BN, GeoHXS::THREADS, GeoHXS::LDS_BYTES, bcfg[k]);
-    default: return kErrNotSupported;
+  // SUF: _batched, or _batched_seeded for an accumulating launch (p.seed) -- the same kernel with C's value in its epilogue
+#define MM_F16_BATCHED(SUF, CFG)                                                                                                       \
+  switch (k) {                                                                                                                         \
+    case K_PP16: return launch_tile_batched(s, p, mfma_f16_pp2s_kernel##SUF, 256, 256, GeoPP2::THREADS, GeoPP2::LDS_BYTES, CFG[k]);   \
+    case K_PP32: return launch_tile_batched(s, p, mfma_f16_pp2_kernel##SUF, 256, 256, GeoPP2::THREADS, GeoPP2::LDS_BYTES, CFG[k]);    \
+    case K_PPK32: return launch_tile_batched(s, p, mfma_f16_pp_kernel##SUF<false>, 256, 256, GeoPP::THREADS, GeoPP::LDS_BYTES, CFG[k]); \
+    case K_PPK32_AT: return launch_tile_batched(s, p, mfma_f16_pp_kernel##SUF<true>, 256, 256, GeoPP::THREADS, GeoPP::LDS_BYTES, CFG[k]); \
+    case K_SLAB64: return launch_tile_batched(s, p, mfma_f16_kernel##SUF<GeoH, false>, GeoH::BM, GeoH::BN, GeoH::THREADS, GeoH::LDS_BYTES, CFG[k]); \
+    case K_SLAB64_AT: return launch_tile_batched(s, p, mfma_f16_kernel##SUF<GeoH, true>, GeoH::BM, GeoH::BN, GeoH::THREADS, GeoH::LDS_BYTES, CFG[k]); \
+    case K_SLAB64_128: return launch_tile_batched(s, p, mfma_f16_kernel##SUF<GeoHS, false>, GeoHS::BM, GeoHS::BN, GeoHS::THREADS, GeoHS::LDS_BYTES, CFG[k]); \
+    case K_SLAB64_64: return launch_tile_batched(s, p, mfma_f16_kernel##SUF<GeoHXS, false>, GeoHXS::BM, GeoHXS::BN, GeoHXS::THREADS, GeoHXS::LDS_BYTES, CFG[k]); \
+    default: return kErrNotSupported;                                                                                                  \
   }
+  if (p.seed) MM_F16_BATCHED(_batched_seeded, scfg)
+  MM_F16_BATCHED(_batched, bcfg)
+#undef MM_F16_BATCHED
 }
 
 }  // namespace mm

@@ -1,4 +1,5 @@
-// The kernels of mm_mfma_f16.hip, compiled twice by it: MM_BATCHED 0 the single-problem kernels, 1 their *_batched twins
+// The kernels of mm_mfma_f16.hip, compiled three times by it: MM_BATCHED 0 the single-problem kernels, 1 their *_batched twins,
+// MM_BATCHED 1 with MM_SEEDED 1 the *_batched_seeded forms that accumulate into C
 // (mm_batched_kernel.h).  Definitions that are not kernels appear in the first pass only.
 #include "mm_batched_kernel.h"
 template <typename G, bool AT>
@@ -169,6 +170,27 @@ __global__ __launch_bounds__(G::THREADS) void MM_KNAME(mfma_f16_kernel)(const _F
   {
     constexpr int ROWS = TM * 32;                       // rows of this wave's tile, 128 columns = 256 B each
     char *slice = smem + wave * (ROWS * 256);
+#if MM_SEEDED
+    {  // accumulate: C's tile enters the slice in the coalesced store layout (a lane reads the 16 bytes it later writes back),
+       // then every accumulator adds its own element in f32 -- the seed before the one rounding
+      using u32x4 = __attribute__((ext_vector_type(4))) unsigned;
+#pragma unroll
+      for (int it = 0; it < ROWS * 16 / 64; ++it) {
+        const unsigned c = it * 64 + lane, row = c / 16, ch = c % 16;
+        const unsigned grow = row0 + wm * ROWS + row, gcol = col0 + wn * 128 + ch * 8;
+        u32x4 v = {0u, 0u, 0u, 0u};
+        if (grow < N && gcol < M) v = *(const u32x4 *)(C + (size_t)grow * M + gcol);
+        *(u32x4 *)(slice + row * 256 + ch * 16) = v;
+      }
+#pragma unroll
+      for (int mi = 0; mi < TM; ++mi)
+#pragma unroll
+        for (int ni = 0; ni < TN; ++ni)
+#pragma unroll
+          for (int rr = 0; rr < 16; ++rr)
+          acc[mi][ni][rr] += (float)*(const _Float16 *)(slice + (mi * 32 + (rr & 3) + 8 * (rr >> 2) + 4 * hi) * 256 + (ni * 32 + lo) * 2);
+    }
+#endif
 #pragma unroll
     for (int mi = 0; mi < TM; ++mi)
 #pragma unroll
@@ -363,6 +385,27 @@ __global__ __launch_bounds__(GeoPP::THREADS) void MM_KNAME(mfma_f16_pp_kernel)(c
   //      (C/D of the 16x16 form: column l15, rows 4*g + i)
   {
     char *slice = smem + wave * (128 * 128);
+#if MM_SEEDED
+    {  // accumulate: C's tile enters the slice in the coalesced store layout (a lane reads the 16 bytes it later writes back),
+       // then every accumulator adds its own element in f32 -- the seed before the one rounding
+      using u32x4 = __attribute__((ext_vector_type(4))) unsigned;
+#pragma unroll
+      for (int it = 0; it < 128 * 8 / 64; ++it) {
+        const unsigned c = it * 64 + lane, row = c / 8, ch = c % 8;
+        const unsigned grow = row0 + wm * 128 + row, gcol = col0 + wn * 64 + ch * 8;
+        u32x4 v = {0u, 0u, 0u, 0u};
+        if (grow < N && gcol < M) v = *(const u32x4 *)(C + (size_t)grow * M + gcol);
+        *(u32x4 *)(slice + row * 128 + ch * 16) = v;
+      }
+#pragma unroll
+      for (int rb = 0; rb < RB; ++rb)
+#pragma unroll
+        for (int nb = 0; nb < NB; ++nb)
+#pragma unroll
+          for (int i = 0; i < 4; ++i)
+          acc[rb][nb][i] += (float)*(const _Float16 *)(slice + (rb * 16 + 4 * g + i) * 128 + (nb * 16 + l15) * 2);
+    }
+#endif
 #pragma unroll
     for (int rb = 0; rb < RB; ++rb)
 #pragma unroll
@@ -553,6 +596,27 @@ __global__ __launch_bounds__(GeoPP2::THREADS) void MM_KNAME(mfma_f16_pp2_kernel)
 
   {
     char *slice = smem + wave * (128 * 128);
+#if MM_SEEDED
+    {  // accumulate: C's tile enters the slice in the coalesced store layout (a lane reads the 16 bytes it later writes back),
+       // then every accumulator adds its own element in f32 -- the seed before the one rounding
+      using u32x4 = __attribute__((ext_vector_type(4))) unsigned;
+#pragma unroll
+      for (int it = 0; it < 128 * 8 / 64; ++it) {
+        const unsigned c = it * 64 + lane, row = c / 8, ch = c % 8;
+        const unsigned grow = row0 + wm * 128 + row, gcol = col0 + wn * 64 + ch * 8;
+        u32x4 v = {0u, 0u, 0u, 0u};
+        if (grow < N && gcol < M) v = *(const u32x4 *)(C + (size_t)grow * M + gcol);
+        *(u32x4 *)(slice + row * 128 + ch * 16) = v;
+      }
+#pragma unroll
+      for (int mi = 0; mi < TM; ++mi)
+#pragma unroll
+        for (int ni = 0; ni < TN; ++ni)
+#pragma unroll
+          for (int rr = 0; rr < 16; ++rr)
+          acc[mi][ni][rr] += (float)*(const _Float16 *)(slice + (mi * 32 + (rr & 3) + 8 * (rr >> 2) + 4 * hi) * 128 + (ni * 32 + lo) * 2);
+    }
+#endif
 #pragma unroll
     for (int mi = 0; mi < TM; ++mi)
 #pragma unroll
@@ -731,6 +795,27 @@ __global__ __launch_bounds__(GeoPP2::THREADS) void MM_KNAME(mfma_f16_pp2s_kernel
 
   {  // epilogue: C/D of the 16x16 form: column l15, rows 4*g + i
     char *slice = smem + wave * (128 * 128);
+#if MM_SEEDED
+    {  // accumulate: C's tile enters the slice in the coalesced store layout (a lane reads the 16 bytes it later writes back),
+       // then every accumulator adds its own element in f32 -- the seed before the one rounding
+      using u32x4 = __attribute__((ext_vector_type(4))) unsigned;
+#pragma unroll
+      for (int it = 0; it < 128 * 8 / 64; ++it) {
+        const unsigned c = it * 64 + lane, row = c / 8, ch = c % 8;
+        const unsigned grow = row0 + wm * 128 + row, gcol = col0 + wn * 64 + ch * 8;
+        u32x4 v = {0u, 0u, 0u, 0u};
+        if (grow < N && gcol < M) v = *(const u32x4 *)(C + (size_t)grow * M + gcol);
+        *(u32x4 *)(slice + row * 128 + ch * 16) = v;
+      }
+#pragma unroll
+      for (int rb = 0; rb < RB; ++rb)
+#pragma unroll
+        for (int nb = 0; nb < NB; ++nb)
+#pragma unroll
+          for (int i = 0; i < 4; ++i)
+          acc[rb][nb][i] += (float)*(const _Float16 *)(slice + (rb * 16 + 4 * g + i) * 128 + (nb * 16 + l15) * 2);
+    }
+#endif
 #pragma unroll
     for (int rb = 0; rb < RB; ++rb)
 #pragma unroll

@@ -58,7 +58,9 @@ struct Geo {
 // One k-range of one output tile: A / B point at the first k of the range (row stride of A: lda), K = its length, the
 // result goes to Cst[row * ldc + col] for rows < Nst, cols < Mst.  For a whole tile of C that is (C, M, N, M); a partial
 // tile of a stream-K launch targets a 128 x 128 scratch slot instead (ldc = 128, no limits).
-template <typename G, bool AT, bool AGENT_STORES = false>
+// SEED (accumulate, the *_batched_seeded kernels): C's value enters the first write-back to C, the chain flush into C's own
+// read-modify-write (FlushIntoC geometries only): the tile behaves as if an earlier chunk had already been flushed there.
+template <typename G, bool AT, bool AGENT_STORES = false, bool SEED = false>
 __device__ __forceinline__ void tile_body(const float *__restrict__ A, const float *__restrict__ B, float *__restrict__ Cst,
                                           unsigned N, unsigned K, unsigned M, unsigned lda, unsigned ldc, unsigned Nst,
                                           unsigned Mst, unsigned row0, unsigned col0) {
@@ -406,7 +408,8 @@ __device__ __forceinline__ void tile_body(const float *__restrict__ A, const flo
   };
 
   const unsigned steady = num_tiles - 1;  // slabs 0 .. num_tiles-2 are full and have a successor
-  bool flushed = false;
+  static_assert(!SEED || FLUSH, "the seed enters through the flush into C");
+  bool flushed = SEED;
   if (FLUSH) {
     for (unsigned t0 = 0; t0 < steady; t0 += G::CHUNK) {
       const unsigned tend = min(t0 + (unsigned)G::CHUNK, steady);

@@ -53,6 +53,9 @@ struct GeoD {
 #undef MM_BATCHED
 #define MM_BATCHED 1
 #include "mm_mfma_f64_kernels.inc"
+#define MM_SEEDED 1
+#include "mm_mfma_f64_kernels.inc"
+#undef MM_SEEDED
 #undef MM_BATCHED
 
 using D0 = GeoD<4, 2, 2>;  // 256 x 128 tile, 8 wavefronts (2 per SIMD), 96 KiB LDS
@@ -70,16 +73,25 @@ bool mfma_f64_serves(const Problem &p) {
   return !p.a_transposed || (p.n >= 2 && p.n % 2 == 0);
 }
 
-// BATCHED: the p.batch elements of p (strides p.stride_*) in one launch of mfma_f64_kernel_batched
+// BATCHED: the p.batch elements of p (strides p.stride_*) in one launch of mfma_f64_kernel_batched (p.seed: _batched_seeded)
 template <typename G, bool BATCHED = false>
 static int launch_d(hipStream_t s, const Problem &p) {
   const unsigned tiles_n = (p.n + G::BM - 1) / G::BM, tiles_m = (p.m + G::BN - 1) / G::BN;
   const unsigned grid = tiles_n * tiles_m * (BATCHED ? p.batch : 1u);
   const unsigned band = band_rows(G::BM, G::BN, G::BM * G::BN <= 64 * 64 ? 4 : G::BM * G::BN <= 128 * 128 ? 2 : 1);
-  static unsigned long long configured = 0, configured_at = 0;
+  static unsigned long long configured = 0, configured_at = 0, configured_seeded = 0, configured_seeded_at = 0;
 #define MM_F64_LAUNCH(AT)                                                                                                        \
   do {                                                                                                                           \
     if constexpr (BATCHED) {                                                                                                     \
+      if (p.seed) {                                                                                                              \
+        if (int e = ensure_dynamic_lds((const void *)mfma_f64_kernel_batched_seeded<G, AT>, G::LDS_BYTES,                       \
+                                       AT ? configured_seeded_at : configured_seeded))                                           \
+          return e;                                                                                                              \
+        hipLaunchKernelGGL((mfma_f64_kernel_batched_seeded<G, AT>), dim3(grid), dim3(G::THREADS), G::LDS_BYTES, s,              \
+                           (const double *)p.a, (const double *)p.b, (double *)p.c, p.n, p.k, p.m, tiles_n, tiles_m, band,      \
+                           p.batch, p.stride_a, p.stride_b, p.stride_c);                                                        \
+        break;                                                                                                                   \
+      }                                                                                                                          \
       if (int e = ensure_dynamic_lds((const void *)mfma_f64_kernel_batched<G, AT>, G::LDS_BYTES, AT ? configured_at : configured)) \
         return e;                                                                                                                \
       hipLaunchKernelGGL((mfma_f64_kernel_batched<G, AT>), dim3(grid), dim3(G::THREADS), G::LDS_BYTES, s, (const double *)p.a, \

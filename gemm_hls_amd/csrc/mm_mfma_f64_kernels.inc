@@ -1,5 +1,5 @@
-// The kernels of mm_mfma_f64.hip, compiled twice by it: MM_BATCHED 0 the single-problem kernels, 1 their *_batched twins
-// (mm_batched_kernel.h).  Definitions that are not kernels appear in the first pass only.
+// The kernels of mm_mfma_f64.hip, compiled three times by it: MM_BATCHED 0 the single-problem kernels, 1 their *_batched twins,
+// and MM_BATCHED 1 with MM_SEEDED 1 the *_batched_seeded forms that accumulate into C (mm_batched_kernel.h).  Definitions that are not kernels appear in the first pass only.
 #include "mm_batched_kernel.h"
 template <typename G, bool AT>
 __global__ __launch_bounds__(G::THREADS, G::MIN_WAVES) void MM_KNAME(mfma_f64_kernel)(  // 2 wavefronts per SIMD: <= 256 VGPRs, so that the
@@ -270,6 +270,9 @@ __global__ __launch_bounds__(G::THREADS, G::MIN_WAVES) void MM_KNAME(mfma_f64_ke
           f64x2 v;
           v[0] = acc[mi][pr][0][r];
           v[1] = acc[mi][pr][1][r];
+#if MM_SEEDED
+          v += *(const f64x2 *)(C + (size_t)row * M + ccol);   // accumulate: C's value enters here, read by the lane that writes it
+#endif
           *(f64x2 *)(C + (size_t)row * M + ccol) = v;
         }
       }

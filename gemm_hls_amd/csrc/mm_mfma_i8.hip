@@ -72,11 +72,21 @@ __device__ __forceinline__ i32x4 join(v2i lo, v2i hi) {
   return r;
 }
 
+// Accumulate (the *_batched_seeded kernels): the seed plus the i32 sum, low 8 bits -- which only the low 8 bits of either
+// decide, so the two C images are added bytewise, mod 2^8 per byte (sign or zero extension of the seed does not matter).
+__device__ __forceinline__ __attribute__((ext_vector_type(4))) unsigned add_bytes(__attribute__((ext_vector_type(4))) unsigned x,
+                                                                                 __attribute__((ext_vector_type(4))) unsigned y) {
+  return ((x & 0x7f7f7f7fu) + (y & 0x7f7f7f7fu)) ^ ((x ^ y) & 0x80808080u);
+}
+
 #define MM_BATCHED 0
 #include "mm_mfma_i8_kernels.inc"
 #undef MM_BATCHED
 #define MM_BATCHED 1
 #include "mm_mfma_i8_kernels.inc"
+#define MM_SEEDED 1
+#include "mm_mfma_i8_kernels.inc"
+#undef MM_SEEDED
 #undef MM_BATCHED
 #undef MM_DMA_PIECE
 
@@ -217,19 +227,25 @@ static Kind resolve_batched(const Problem &p) {
 int mfma_i8_batched_resolve(const Problem &p) { const Kind k = resolve_batched(p); return k == K_NONE ? -1 : (int)k; }
 const char *mfma_i8_batched_name(const Problem &p) { return kNames[resolve_batched(p)]; }
 int launch_mfma_i8_batched(hipStream_t s, const Problem &p, int kind) {
-  static unsigned long long bcfg[K_NONE] = {};
+  static unsigned long long bcfg[K_NONE] = {}, scfg[K_NONE] = {};
   if (kind < 0 || kind >= (int)K_NONE) return kErrNotSupported;
   const Kind k = (Kind)kind;
-  switch (k) {
-    case K_PP16: return launch_tile_batched(s, p, mfma_i8_pp2s_kernel_batched, GeoI8PP2::THREADS, GeoI8PP2::LDS_BYTES, bcfg[k]);
-    case K_PP32: return launch_tile_batched(s, p, mfma_i8_pp2_kernel_batched, GeoI8PP2::THREADS, GeoI8PP2::LDS_BYTES, bcfg[k]);
-    case K_PPK64: return launch_tile_batched(s, p, mfma_i8_pp_kernel_batched<false>, GeoI8PP::THREADS, GeoI8PP::LDS_BYTES, bcfg[k]);
-    case K_PPK64_AT: return launch_tile_batched(s, p, mfma_i8_pp_kernel_batched<true>, GeoI8PP::THREADS, GeoI8PP::LDS_BYTES, bcfg[k]);
-    case K_SLAB128: return launch_tile_batched(s, p, mfma_i8_kernel_batched<GeoI8, false>, GeoI8::THREADS, GeoI8::LDS_BYTES, bcfg[k]);
-    case K_SLAB128_AT: return launch_tile_batched(s, p, mfma_i8_kernel_batched<GeoI8, true>, GeoI8::THREADS, GeoI8::LDS_BYTES, bcfg[k]);
-    case K_SLAB128_64: return launch_tile_batched(s, p, mfma_i8_kernel_batched<GeoI8S, false>, GeoI8S::THREADS, GeoI8S::LDS_BYTES, bcfg[k], GeoI8S::BM);
-    default: return kErrNotSupported;
+  // SUF: _batched, or _batched_seeded for an accumulating launch (p.seed) -- the same kernel with C's value in its epilogue
+#define MM_I8_BATCHED(SUF, CFG)                                                                                                        \
+  switch (k) {                                                                                                                         \
+    case K_PP16: return launch_tile_batched(s, p, mfma_i8_pp2s_kernel##SUF, GeoI8PP2::THREADS, GeoI8PP2::LDS_BYTES, CFG[k]);          \
+    case K_PP32: return launch_tile_batched(s, p, mfma_i8_pp2_kernel##SUF, GeoI8PP2::THREADS, GeoI8PP2::LDS_BYTES, CFG[k]);           \
+    case K_PPK64: return launch_tile_batched(s, p, mfma_i8_pp_kernel##SUF<false>, GeoI8PP::THREADS, GeoI8PP::LDS_BYTES, CFG[k]);      \
+    case K_PPK64_AT: return launch_tile_batched(s, p, mfma_i8_pp_kernel##SUF<true>, GeoI8PP::THREADS, GeoI8PP::LDS_BYTES, CFG[k]);    \
+    case K_SLAB128: return launch_tile_batched(s, p, mfma_i8_kernel##SUF<GeoI8, false>, GeoI8::THREADS, GeoI8::LDS_BYTES, CFG[k]);    \
+    case K_SLAB128_AT: return launch_tile_batched(s, p, mfma_i8_kernel##SUF<GeoI8, true>, GeoI8::THREADS, GeoI8::LDS_BYTES, CFG[k]);  \
+    case K_SLAB128_64:                                                                                                                 \
+      return launch_tile_batched(s, p, mfma_i8_kernel##SUF<GeoI8S, false>, GeoI8S::THREADS, GeoI8S::LDS_BYTES, CFG[k], GeoI8S::BM);  \
+    default: return kErrNotSupported;                                                                                                  \
   }
+  if (p.seed) MM_I8_BATCHED(_batched_seeded, scfg)
+  MM_I8_BATCHED(_batched, bcfg)
+#undef MM_I8_BATCHED
 }
 
 }  // namespace mm

@@ -1,4 +1,5 @@
-// The kernels of mm_mfma_i8.hip, compiled twice by it: MM_BATCHED 0 the single-problem kernels, 1 their *_batched twins
+// The kernels of mm_mfma_i8.hip, compiled three times by it: MM_BATCHED 0 the single-problem kernels, 1 their *_batched twins,
+// MM_BATCHED 1 with MM_SEEDED 1 the *_batched_seeded forms that accumulate into C
 // (mm_batched_kernel.h).  Definitions that are not kernels appear in the first pass only.
 #include "mm_batched_kernel.h"
 template <typename G, bool AT>
@@ -174,7 +175,14 @@ __global__ __launch_bounds__(G::THREADS) void MM_KNAME(mfma_i8_kernel)(const sig
       const unsigned c = it * 64 + lane, row = c / 8, ch = c % 8;
       const u32x4 v = *(const u32x4 *)(slice + row * 128 + ch * 16);
       const unsigned grow = row0 + wm * ROWS + row, gcol = col0 + wn * 128 + ch * 16;
+#if MM_SEEDED
+      if (grow < N && gcol < M) {   // accumulate: low 8 bits of seed + sum, bytewise; the lane reads what it then writes
+        u32x4 *dst = (u32x4 *)(C + (size_t)grow * M + gcol);
+        *dst = add_bytes(v, *dst);
+      }
+#else
       if (grow < N && gcol < M) *(u32x4 *)(C + (size_t)grow * M + gcol) = v;
+#endif
     }
   }
 }
@@ -334,7 +342,14 @@ __global__ __launch_bounds__(GeoI8PP::THREADS) void MM_KNAME(mfma_i8_pp_kernel)(
       const unsigned c = it * 64 + lane, row = c / 4, ch = c % 4;
       const u32x4 v = *(const u32x4 *)(slice + row * 64 + ch * 16);
       const unsigned grow = row0 + wm * 128 + row, gcol = col0 + wn * 64 + ch * 16;
+#if MM_SEEDED
+      if (grow < N && gcol < M) {   // accumulate: low 8 bits of seed + sum, bytewise; the lane reads what it then writes
+        u32x4 *dst = (u32x4 *)(C + (size_t)grow * M + gcol);
+        *dst = add_bytes(v, *dst);
+      }
+#else
       if (grow < N && gcol < M) *(u32x4 *)(C + (size_t)grow * M + gcol) = v;
+#endif
     }
   }
 }
@@ -505,7 +520,14 @@ __global__ __launch_bounds__(GeoI8PP2::THREADS) void MM_KNAME(mfma_i8_pp2_kernel
       const unsigned c = it * 64 + lane, row = c / 4, ch = c % 4;
       const u32x4 v = *(const u32x4 *)(slice + row * 64 + ch * 16);
       const unsigned grow = row0 + wm * 128 + row, gcol = col0 + wn * 64 + ch * 16;
+#if MM_SEEDED
+      if (grow < N && gcol < M) {   // accumulate: low 8 bits of seed + sum, bytewise; the lane reads what it then writes
+        u32x4 *dst = (u32x4 *)(C + (size_t)grow * M + gcol);
+        *dst = add_bytes(v, *dst);
+      }
+#else
       if (grow < N && gcol < M) *(u32x4 *)(C + (size_t)grow * M + gcol) = v;
+#endif
     }
   }
 }
@@ -666,7 +688,14 @@ __global__ __launch_bounds__(GeoI8PP2::THREADS) void MM_KNAME(mfma_i8_pp2s_kerne
       const unsigned c = it * 64 + lane, row = c / 4, ch = c % 4;
       const u32x4 v = *(const u32x4 *)(slice + row * 64 + ch * 16);
       const unsigned grow = row0 + wm * 128 + row, gcol = col0 + wn * 64 + ch * 16;
+#if MM_SEEDED
+      if (grow < N && gcol < M) {   // accumulate: low 8 bits of seed + sum, bytewise; the lane reads what it then writes
+        u32x4 *dst = (u32x4 *)(C + (size_t)grow * M + gcol);
+        *dst = add_bytes(v, *dst);
+      }
+#else
       if (grow < N && gcol < M) *(u32x4 *)(C + (size_t)grow * M + gcol) = v;
+#endif
     }
   }
 }

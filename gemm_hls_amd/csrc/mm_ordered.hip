@@ -38,12 +38,33 @@ __global__ __launch_bounds__(256) void ordered_batched_kernel(const T *__restric
 #undef MM_ORDERED_BATCHED
 }
 
-// BATCHED: the p.batch elements of p (strides p.stride_*) in one launch of ordered_batched_kernel
+// accumulate (p.seed): ordered_batched_kernel whose chains start at the value C holds instead of identity()
+template <typename T, int MAP, int RED, bool AT, typename ACC = T>
+__global__ __launch_bounds__(256) void ordered_batched_seeded_kernel(const T *__restrict__ A, const T *__restrict__ B,
+                                                                     T *__restrict__ C, unsigned N, unsigned K, unsigned M,
+                                                                     size_t stride_a, size_t stride_b, size_t stride_c) {
+#define MM_ORDERED_BATCHED 1
+#define MM_ORDERED_SEEDED 1
+#include "mm_ordered_body.inc"
+#undef MM_ORDERED_SEEDED
+#undef MM_ORDERED_BATCHED
+}
+
+// BATCHED: the p.batch elements of p (strides p.stride_*) in one launch of ordered_batched_kernel (p.seed: its seeded form)
 template <typename T, int MAP, int RED, bool BATCHED, typename ACC = T>
 int launch_t(hipStream_t s, const Problem &p) {
   if (p.n == 0 || p.m == 0) return 0;
   if constexpr (BATCHED) {
     const unsigned tiles = ((p.m + kTile - 1) / kTile) * ((p.n + kTile - 1) / kTile);
+    if (p.seed) {
+      if (p.a_transposed)
+        hipLaunchKernelGGL((ordered_batched_seeded_kernel<T, MAP, RED, true, ACC>), dim3(tiles * p.batch), dim3(256), 0, s,
+                           (const T *)p.a, (const T *)p.b, (T *)p.c, p.n, p.k, p.m, p.stride_a, p.stride_b, p.stride_c);
+      else
+        hipLaunchKernelGGL((ordered_batched_seeded_kernel<T, MAP, RED, false, ACC>), dim3(tiles * p.batch), dim3(256), 0, s,
+                           (const T *)p.a, (const T *)p.b, (T *)p.c, p.n, p.k, p.m, p.stride_a, p.stride_b, p.stride_c);
+      return (int)hipGetLastError();
+    }
     if (p.a_transposed)
       hipLaunchKernelGGL((ordered_batched_kernel<T, MAP, RED, true, ACC>), dim3(tiles * p.batch), dim3(256), 0, s,
                          (const T *)p.a, (const T *)p.b, (T *)p.c, p.n, p.k, p.m, p.stride_a, p.stride_b, p.stride_c);

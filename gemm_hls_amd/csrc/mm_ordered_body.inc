@@ -1,5 +1,6 @@
-// Body of ordered_kernel (MM_ORDERED_BATCHED 0) and ordered_batched_kernel (MM_ORDERED_BATCHED 1): mm_ordered.hip includes
-// it once per form, so that the single-problem kernel is the same source, and the same machine code, it always was.
+// Body of ordered_kernel (MM_ORDERED_BATCHED 0), ordered_batched_kernel (MM_ORDERED_BATCHED 1) and
+// ordered_batched_seeded_kernel (MM_ORDERED_BATCHED 1, MM_ORDERED_SEEDED 1): mm_ordered.hip includes it once per form, so
+// that the single-problem kernel is the same source, and the same machine code, it always was.
   __shared__ T As[kBK][kTile + 1];  // [k][row], +1: column reads of a row-major source
   __shared__ T Bs[kBK][kTile];      // [k][col]
   const unsigned tid = threadIdx.x;
@@ -22,6 +23,19 @@
   for (int i = 0; i < kPerThread; ++i)
 #pragma unroll
     for (int j = 0; j < kPerThread; ++j) acc[i][j] = Op<RED, ACC>::identity();
+#if MM_ORDERED_SEEDED
+  // accumulate: the value C holds replaces identity() as the start of the chain (Naive with acc = C[i][j]); the loads are
+  // only consumed at the first k-step, so they are in flight while the first slab is staged
+#pragma unroll
+  for (int i = 0; i < kPerThread; ++i) {
+    const unsigned gr = row0 + ty * kPerThread + i;
+#pragma unroll
+    for (int j = 0; j < kPerThread; ++j) {
+      const unsigned gc = col0 + tx + 16 * j;
+      if (gr < N && gc < M) acc[i][j] = (ACC)C[(size_t)gr * M + gc];
+    }
+  }
+#endif
 
   for (unsigned k0 = 0; k0 < K; k0 += kBK) {
     // stage A: 64 rows x 16 k

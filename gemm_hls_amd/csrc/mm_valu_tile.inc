@@ -75,6 +75,18 @@ __global__ __launch_bounds__(256) void valu_tile_batched_kernel(const T *__restr
 #undef MM_VT_BATCHED
 }
 
+// accumulate (Problem::seed): valu_tile_batched_kernel with the acc tile loaded from C instead of set to identity()
+template <typename T, int MAP, int RED, bool AT>
+__global__ __launch_bounds__(256) void valu_tile_batched_seeded_kernel(const T *__restrict__ A, const T *__restrict__ B,
+                                                        T *__restrict__ C, unsigned N, unsigned K, unsigned M,
+                                                        unsigned tiles_n, unsigned tiles_m, unsigned kBand,
+    unsigned batch, size_t stride_a, size_t stride_b, size_t stride_c) {
+#define MM_VT_BATCHED 1
+#define MM_VT_SEEDED 1
+#include "mm_valu_tile_body.inc"
+#undef MM_VT_SEEDED
+#undef MM_VT_BATCHED
+}
 
 // -------------------------------------------------------------------------------------------------
 // DMA-staged variant, row-major A (round 2 for the 4-byte types, round 3 for every element size).  The kernel above
@@ -117,6 +129,18 @@ __global__ __launch_bounds__(TI == 8 ? 256 : 512, TI == 8 ? 1 : 4) void valu_til
 #include "mm_valu_tile_dma_body.inc"
 #undef MM_VT_BATCHED
 }
+
+template <typename T, int MAP, int RED, int TI>
+__global__ __launch_bounds__(TI == 8 ? 256 : 512, TI == 8 ? 1 : 4) void valu_tile_dma_batched_seeded_kernel(const T *__restrict__ A, const T *__restrict__ B,
+                                                            T *__restrict__ C, unsigned N, unsigned K, unsigned M,
+                                                            unsigned tiles_n, unsigned tiles_m, unsigned kBand,
+    unsigned batch, size_t stride_a, size_t stride_b, size_t stride_c) {
+#define MM_VT_BATCHED 1
+#define MM_VT_SEEDED 1
+#include "mm_valu_tile_dma_body.inc"
+#undef MM_VT_SEEDED
+#undef MM_VT_BATCHED
+}
 #undef MM_DMA_PIECE
 
 // The DMA-staged kernel addresses a tile's rows with 32-bit byte offsets from a uniform base (128 rows x K, BK k-rows x
@@ -133,13 +157,18 @@ template <typename T, int MAP, int RED, bool BATCHED>
 int vt_launch(hipStream_t s, const Problem &p) {
   const unsigned tiles_n = (p.n + VT_BM - 1) / VT_BM, tiles_m = (p.m + VT_BN - 1) / VT_BN;
   const unsigned grid = tiles_n * tiles_m * (BATCHED ? p.batch : 1u);
-  // the kernels' argument lists: the single problem's, plus the batch and the element strides for the batched forms
-#define MM_VT_LAUNCH(KERNEL, BATCHED_KERNEL, THREADS, BAND)                                                                   \
+  // the kernels' argument lists: the single problem's, plus the batch and the element strides for the batched forms (whose
+  // seeded twins, for p.seed, take the same arguments)
+#define MM_VT_LAUNCH(KERNEL, BATCHED_KERNEL, SEEDED_KERNEL, THREADS, BAND)                                                    \
   do {                                                                                                                      \
-    if constexpr (BATCHED)                                                                                                  \
-      hipLaunchKernelGGL(BATCHED_KERNEL, dim3(grid), dim3(THREADS), 0, s, (const T *)p.a, (const T *)p.b, (T *)p.c, p.n,   \
-                         p.k, p.m, tiles_n, tiles_m, BAND, p.batch, p.stride_a, p.stride_b, p.stride_c);                  \
-    else                                                                                                                    \
+    if constexpr (BATCHED) {                                                                                                \
+      if (p.seed)                                                                                                           \
+        hipLaunchKernelGGL(SEEDED_KERNEL, dim3(grid), dim3(THREADS), 0, s, (const T *)p.a, (const T *)p.b, (T *)p.c, p.n,  \
+                           p.k, p.m, tiles_n, tiles_m, BAND, p.batch, p.stride_a, p.stride_b, p.stride_c);                \
+      else                                                                                                                  \
+        hipLaunchKernelGGL(BATCHED_KERNEL, dim3(grid), dim3(THREADS), 0, s, (const T *)p.a, (const T *)p.b, (T *)p.c, p.n, \
+                           p.k, p.m, tiles_n, tiles_m, BAND, p.batch, p.stride_a, p.stride_b, p.stride_c);                \
+    } else                                                                                                                  \
       hipLaunchKernelGGL(KERNEL, dim3(grid), dim3(THREADS), 0, s, (const T *)p.a, (const T *)p.b, (T *)p.c, p.n, p.k, p.m, \
                          tiles_n, tiles_m, BAND);                                                                           \
   } while (0)
@@ -151,19 +180,23 @@ int vt_launch(hipStream_t s, const Problem &p) {
   if (vt_dma_serves<T>(p) && vv != 0) {
     if constexpr (sizeof(T) == 8) {
       if (vv != 2) {
-        MM_VT_LAUNCH((valu_tile_dma_kernel<T, MAP, RED, 4>), (valu_tile_dma_batched_kernel<T, MAP, RED, 4>), 512,
+        MM_VT_LAUNCH((valu_tile_dma_kernel<T, MAP, RED, 4>), (valu_tile_dma_batched_kernel<T, MAP, RED, 4>),
+                     (valu_tile_dma_batched_seeded_kernel<T, MAP, RED, 4>), 512,
                      band_rows(VT_BM, VT_BN, 2));
         return (int)hipGetLastError();
       }
     }
-    MM_VT_LAUNCH((valu_tile_dma_kernel<T, MAP, RED, 8>), (valu_tile_dma_batched_kernel<T, MAP, RED, 8>), 256,
+    MM_VT_LAUNCH((valu_tile_dma_kernel<T, MAP, RED, 8>), (valu_tile_dma_batched_kernel<T, MAP, RED, 8>),
+                 (valu_tile_dma_batched_seeded_kernel<T, MAP, RED, 8>), 256,
                  band_rows(VT_BM, VT_BN, 2));
     return (int)hipGetLastError();
   }
   if (p.a_transposed)
-    MM_VT_LAUNCH((valu_tile_kernel<T, MAP, RED, true>), (valu_tile_batched_kernel<T, MAP, RED, true>), 256, band_rows());
+    MM_VT_LAUNCH((valu_tile_kernel<T, MAP, RED, true>), (valu_tile_batched_kernel<T, MAP, RED, true>),
+                 (valu_tile_batched_seeded_kernel<T, MAP, RED, true>), 256, band_rows());
   else
-    MM_VT_LAUNCH((valu_tile_kernel<T, MAP, RED, false>), (valu_tile_batched_kernel<T, MAP, RED, false>), 256, band_rows());
+    MM_VT_LAUNCH((valu_tile_kernel<T, MAP, RED, false>), (valu_tile_batched_kernel<T, MAP, RED, false>),
+                 (valu_tile_batched_seeded_kernel<T, MAP, RED, false>), 256, band_rows());
 #undef MM_VT_LAUNCH
   return (int)hipGetLastError();
 }

@@ -1,5 +1,6 @@
-// Body of valu_tile_kernel (MM_VT_BATCHED 0) and valu_tile_batched_kernel (MM_VT_BATCHED 1): mm_valu_tile.inc includes it
-// once per form, so that the single-problem kernel is the same source, and the same machine code, it always was.
+// Body of valu_tile_kernel (MM_VT_BATCHED 0), valu_tile_batched_kernel (MM_VT_BATCHED 1) and valu_tile_batched_seeded_kernel
+// (MM_VT_BATCHED 1, MM_VT_SEEDED 1): mm_valu_tile.inc includes it once per form, so that the single-problem kernel is the
+// same source, and the same machine code, it always was.
   __shared__ __attribute__((aligned(16))) T As[VT_BK][VT_BM + VT_PAD];
   __shared__ __attribute__((aligned(16))) T Bs[VT_BK][VT_BN + VT_PAD];
   const unsigned tid = threadIdx.x, tx = tid % 16, ty = tid / 16;
@@ -19,6 +20,24 @@
     for (int j = 0; j < 8; ++j) acc[i][j] = Op<RED, T>::identity();
 
   using V = Vec4<T>;
+#if MM_VT_SEEDED
+  // accumulate: the acc tile starts from C, read with the Vec4 accesses the store below uses (a lane reads exactly what it
+  // later writes); the loads are consumed at the first k-step, so they are in flight while the first slab is staged
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    const unsigned r = row0 + (i < 4 ? ty * 4 + i : 64 + ty * 4 + (i - 4));
+    if (r >= N) continue;
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      const unsigned c = col0 + h * 64 + tx * 4;
+      if (c < M) {
+        const V v = *(const V *)(C + (size_t)r * M + c);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) acc[i][h * 4 + e] = v.v[e];
+      }
+    }
+  }
+#endif
   for (unsigned k0 = 0; k0 < K; k0 += VT_BK) {
     // ---- stage (K % 4 == 0, so a 4-wide k chunk is entirely inside or entirely outside) ----
 #pragma unroll

@@ -1,5 +1,6 @@
-// Body of valu_tile_dma_kernel (MM_VT_BATCHED 0) and valu_tile_dma_batched_kernel (MM_VT_BATCHED 1): mm_valu_tile.inc
-// includes it once per form, so that the single-problem kernel is the same source, and the same machine code, it always was.
+// Body of valu_tile_dma_kernel (MM_VT_BATCHED 0), valu_tile_dma_batched_kernel (MM_VT_BATCHED 1) and
+// valu_tile_dma_batched_seeded_kernel (MM_VT_BATCHED 1, MM_VT_SEEDED 1): mm_valu_tile.inc includes it once per form, so that
+// the single-problem kernel is the same source, and the same machine code, it always was.
   static_assert(TI == 8 || TI == 4, "rows per thread");
   constexpr unsigned ES = sizeof(T), EPC = 16 / ES, BK = 64 / ES;   // bytes, elements per 16-B chunk, slab depth
   constexpr unsigned LPR = 8 * ES, KRP = 64 / LPR;                  // lanes per B k-row (128 cols), k-rows per 1-KiB piece
@@ -67,6 +68,24 @@
   auto thread_row = [&](int i) -> unsigned { return TI == 8 ? (i < 4 ? ty * 4 + i : 64 + ty * 4 + (i - 4)) : ty * 4 + i; };
   const unsigned a_swz = ty & 3u;
   issue(0);
+#if MM_VT_SEEDED
+  // accumulate: the acc tile starts from C, read with the Vec4 accesses the store below uses (a lane reads exactly what it
+  // later writes), issued behind the first slab's DMA pieces; the loop's first vmcnt(0) waits for both
+#pragma unroll
+  for (int i = 0; i < TI; ++i) {
+    const unsigned r = row0 + thread_row(i);
+    if (r >= N) continue;
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      const unsigned c = col0 + h * 64 + tx * 4;
+      if (c < M) {
+        const V v = *(const V *)(C + (size_t)r * M + c);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) acc[i][h * 4 + e] = v.v[e];
+      }
+    }
+  }
+#endif
   for (unsigned t = 0; t < slabs; ++t) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // own pieces of slab t have landed
     __syncthreads();                                  // everybody's have; buffer (t+1)&1 is no longer being read

@@ -195,6 +195,37 @@ int mm_gemm_batched_launch(int device, const mm_config_t *cfg, const void *a_dev
                            unsigned size_n, unsigned size_k, unsigned size_m, unsigned batch,
                            size_t stride_a, size_t stride_b, size_t stride_c, double *elapsed_seconds);
 
+/* Accumulate: C <- C (+) (A (x) B) in place -- for each output the value C holds replaces identity() as the start of the
+ * reduction; nothing else about it changes (D <- min(D, A + B) of min-plus relaxation, BLAS beta = 1 / torch.addmm_ of
+ * (Multiply, Add), a K split the caller drives itself).
+ *   MM_PATH_ORDERED: Naive (include/Utility.h:18-42) with acc = C[i][j] in place of acc = identity(), bit for bit, every dtype
+ *     -- so a Min reduction seeded with +inf whose mapped values are all +inf returns +inf (not max()), and a NaN seed
+ *     follows from b < a ? b : a.
+ *   MM_PATH_AUTO, integer types and Min / Max / And reductions: the bits of the seeded MM_PATH_ORDERED result (floating Min /
+ *     Max for non-NaN operands, with the minNum / maxNum caveat above).  (Multiply, Add) on the matrix cores: float, double and
+ *     half (wide contract) keep the single launch's error bound with |C_in| + |A||B| in place of |A||B| (half: one rounding
+ *     on store); int8 / uint8 add the seed to the i32 sums and keep the low 8 bits (exact); half_contract = reference
+ *     accumulates in binary16 from the seed.
+ * Arguments as for mm_gemm_batched_* (strides in elements, 0 = broadcast, stride_c >= N * M when batch > 1, 16-byte
+ * alignment per element for the fast families under MM_PATH_AUTO, MM_PATH_SPLIT: MM_ERR_UNSUPPORTED; batch, N or M 0:
+ * MM_OK), all checked before any device is touched, with two differences: K = 0 is accepted and leaves C unchanged
+ * (MM_OK), and C must not overlap A or B -- a conservative span test, [base, base + ((batch - 1) * stride + extent)
+ * elements) per operand, else MM_ERR_BAD_ARGUMENT.  C is read and written by the same thread: in place is safe.
+ * An accumulating launch runs exactly the kernel mm_kernel_name_batched(cfg, n, k, m, batch) names, batch = 1 included: no
+ * workspace, no split of K, no stream-K (mid-size fp32 shapes run whole tiles -- slower than mm_gemm_launch there).
+ * _enqueue: asynchronous on a hipStream_t of the CURRENT device; _launch: blocking, *elapsed_seconds (may be NULL) timed
+ * with HIP events.  The single forms are the batched ones with batch = 1. */
+int mm_gemm_accumulate_enqueue(void *hip_stream, const mm_config_t *cfg, const void *a_dev, const void *b_dev, void *c_dev,
+                               unsigned size_n, unsigned size_k, unsigned size_m);
+int mm_gemm_accumulate_launch(int device, const mm_config_t *cfg, const void *a_dev, const void *b_dev, void *c_dev,
+                              unsigned size_n, unsigned size_k, unsigned size_m, double *elapsed_seconds);
+int mm_gemm_batched_accumulate_enqueue(void *hip_stream, const mm_config_t *cfg, const void *a_dev, const void *b_dev,
+                                       void *c_dev, unsigned size_n, unsigned size_k, unsigned size_m, unsigned batch,
+                                       size_t stride_a, size_t stride_b, size_t stride_c);
+int mm_gemm_batched_accumulate_launch(int device, const mm_config_t *cfg, const void *a_dev, const void *b_dev, void *c_dev,
+                                      unsigned size_n, unsigned size_k, unsigned size_m, unsigned batch, size_t stride_a,
+                                      size_t stride_b, size_t stride_c, double *elapsed_seconds);
+
 /* One node, `device_count` GPUs, rows of C split into contiguous slabs (device g gets the rows mm_row_slab() names), B
  * replicated, no collective: every outer tile of C is independent (kernel/Compute.cpp:53-60, kernel/Memory.cpp:114-127,
  * 272-286, 367-391).  Host pointers in, host pointer out; copies are outside the timed region exactly as in
