@@ -3,8 +3,8 @@
 
 N = 1 (default):  fp32 GEMM N=K=M=16384 on one MI355X ("float 16384x16384x16384 on 1 MI355X, MFMA
                   fp32, LDS-tiled outer product", BASELINE configs[1]): GFLOP/s and fraction of the
-                  fp32 MFMA peak.  The same JSON line carries a "workloads" array with the other
-                  single-GPU BASELINE configs (half 32768^3, double 16384^3, min-plus 8192^3, plus
+                  fp32 MFMA peak.  With --full the same JSON line carries a "workloads" array with the
+                  other single-GPU BASELINE configs (half 32768^3, double 16384^3, min-plus 8192^3, plus
                   uint8 32768^3 and the 65536 x 16384 x 16384 job on ONE GPU), a few steps each, so
                   that they are timed by the driver too.
 N > 1:            one process per GPU (python -m torch.distributed.run ...), rows of C split over
@@ -13,7 +13,7 @@ N > 1:            one process per GPU (python -m torch.distributed.run ...), row
                   communication).  --scaling strong (default): the FIXED job BASELINE configs[4]
                   names, float 65536 x 16384 x 16384, split along N across the G ranks (8192 rows
                   per GPU at G = 8).  --scaling weak: every rank owns a 16384-row slab (the job
-                  grows with G).  The strong run also reports the weak figure ("weak_scaling").
+                  grows with G).  With --full the strong run also reports the weak figure ("weak_scaling").
 
 A step = one pass of the hot path (one mm_gemm_enqueue through the C ABI) over operands that are
 already resident in HBM.  Timing = W untimed steps, barrier + synchronize, EXACTLY K steps,
@@ -24,10 +24,16 @@ float64 for double): C.npy holds a fixed, seeded sample of C's rows (all of them
 ranks), C_rows.npy the row numbers in the job (float64); rank r > 0 of an N > 1 run writes C_rank<r>*.npy.  The operands
 are generated on device from fixed seeds, so two builds run with the same arguments can be compared output for output.
 
-Besides the contract keys the line carries
-  roofline     the dominant kernel against its roof, from HIP events on the launch stream
+A plain run does only what the headline needs: set-up, the W + K steps, --dump-outputs, one JSON line whose roofline
+holds what the run's own HIP events measured.  --full adds everything else, after the timed region:
+  workloads[]  the other single-GPU BASELINE configs (N = 1, headline only), with scale_base
+  roofline     counters replayed from committed PMC files, counters measured by rocprofv3 child passes (headline
+               only) and the DRAM-side figure from sysfs mem_busy_percent (N = 1)
   cpu_baseline the reference's OWN hlslib CPU-simulation path (oracle/_ref, compiled from the
                reference's kernel sources) timed on this host's cores on float 1024^3 (BASELINE C1)
+  weak_scaling N > 1, --scaling strong: a second timed job with a 16384-row slab per rank
+  notes, context, baseline_summary (N = 1, headline only)
+--no-extra and --no-cpu-baseline drop parts of a --full run.
 """
 import argparse
 import ctypes
@@ -556,8 +562,11 @@ def main():
     ap.add_argument("--scale-base", type=float, default=float(os.environ.get("MM_SCALE_BASE", "0") or 0),
                     help="N > 1: GFLOP/s of the SAME job on one GPU (the N = 1 line's scale_base.value); the line then carries "
                          "strong_scaling_vs_scale_base = value / this.  Also read from MM_SCALE_BASE")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the workloads[] / weak_scaling extras")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region, also measure everything beyond the headline: workloads[], counters, the "
+                         "DRAM-side probe, cpu_baseline, weak_scaling (see the module docstring)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip cpu_baseline")
+    ap.add_argument("--no-extra", action="store_true", help="--full: skip the workloads[] / weak_scaling extras")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="write a seeded sample of the timed job's output C (its last step) to DIR as .npy")
     args = ap.parse_args()
@@ -680,7 +689,8 @@ def main():
         return g.row_slab(job_cfg, n_total, k, m, world_size, r)
 
     headline = args.workload == "float" and args.size == SIZE
-    hbm = HbmBusy(g, torch, dev, local_rank) if (world == 1 and not args.no_extra) else None
+    extras = args.full and not args.no_extra
+    hbm = HbmBusy(g, torch, dev, local_rank) if (world == 1 and extras) else None
     hbm_box = {}
 
     def dump_outputs(c, row0):
@@ -735,7 +745,7 @@ def main():
     rows, elapsed, launch_ms, rows_all, per_rank = run_job(n_total, 1000, dump=args.dump_outputs is not None)
 
     weak = None
-    if world > 1 and scaling == "strong" and not args.no_extra:
+    if world > 1 and scaling == "strong" and extras:
         w_rows, w_elapsed, w_launch, _, w_per_rank = run_job(args.size * world, 5000)
         weak = (w_rows, w_elapsed, w_launch, w_per_rank)
 
@@ -744,7 +754,7 @@ def main():
         value = 1e-9 * flops_job * args.steps / elapsed
         rl = roofline_obj(dtype, roof, peak, rows, k, m, launch_ms)
         rl.update(hbm_box)
-        if world == 1:
+        if world == 1 and args.full:
             attach_replayed(rl, g.kernel_name(g.make_config(dtype, map_op, reduce_op, PATHS.get(args.workload, 0)), rows, k, m),
                             (rows, k, m), dtype)
         if world == 1:
@@ -802,7 +812,7 @@ def main():
                 "value": round(1e-9 * 2.0 * args.size * world * k * m * args.steps / w_elapsed, 1), "unit": "GFLOP/s",
                 "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(1e3 * w_elapsed / args.steps, 4),
                 "roofline": roofline_obj(dtype, roof, peak, w_rows, k, m, w_launch), "per_rank": w_per_rank}
-        if world == 1 and headline and not args.no_extra:
+        if world == 1 and headline and extras:
             out["workloads"] = extra_workloads(g, torch, dev, local_rank, hbm=hbm)
             # the strong-scaling job (BASELINE configs[4], float 65536 x 16384 x 16384) on ONE GPU, already timed above:
             # an N = G line's value / scale_base.value is the strong-scaling factor of that job without a second run
@@ -812,9 +822,9 @@ def main():
                                          "steps": w["steps"], "warmup": w["warmup"], "ms_per_step": w["ms_per_step"],
                                          "note": "the job `bench.py --gpus G` (scaling strong) splits along N, run unsplit on this GPU: "
                                                  "strong-scaling factor at G = that line's value / this value"}
-        if world == 1 and not args.no_cpu_baseline and headline:
+        if world == 1 and args.full and not args.no_cpu_baseline and headline:
             out["cpu_baseline"] = cpu_baseline()
-        if world == 1 and headline and not args.no_extra:
+        if world == 1 and headline and extras:
             # counters measured in this run, after every timed leg: the headline kernel, BASELINE's C3 / C4 / C5b kernels and the two extras
             targets = [("float", rl, out["config"]["kernel"], (rows, k, m))]
             targets += [(w["key"], w["roofline"], w["kernel"], (WORKLOADS[w["key"]][3],) * 3) for w in out["workloads"]
@@ -825,7 +835,7 @@ def main():
                     for stale in ("traffic_source", "mfma_util_source", "l2_hit_rate", "profiled_clock_GHz", "mfma_util_pct"):
                         obj.pop(stale, None)
                     obj.update(live)
-        if world == 1 and headline:
+        if world == 1 and headline and args.full:
             out["notes"] = {
                 "counters": "roofline objects with counters_measured_in_this_run = true carry rocprofv3 PMC figures collected by this run: child passes "
                             "(--pmc X --kernel-trace) of tools/sweep.py on the same shape after the timed legs; traffic = FETCH_SIZE x2 (gfx950 correction) + "

@@ -342,6 +342,31 @@ def test_bench_dump_outputs_writes_the_timed_jobs_result(tmp_path):
     assert np.array_equal(c, want)
 
 
+def test_bench_plain_run_is_the_headline_job_alone():
+    """A plain `bench.py` run at the headline shape times its steps and prints the contract keys; the extra legs (other
+    workloads, counters, the DRAM-side probe, cpu_baseline) and what describes them appear only under --full."""
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1"]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    out = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+    assert {"metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"} <= set(out)
+    assert out["steps"] == 2 and out["warmup"] == 1 and out["value"] > 0 and "16384" in out["metric"]
+    assert not {"workloads", "scale_base", "cpu_baseline", "notes", "context", "hbm_calibration", "baseline_summary"} & set(out)
+    assert out["roofline"]["avg_launch_ms"] > 0 and out["roofline"]["frac"] > 0
+    assert not {"counters_measured_in_this_run", "traffic_note", "hbm_busy_pct"} & set(out["roofline"])
+
+
+def test_bench_full_adds_the_replayed_counters():
+    """--full off the headline shape: the roofline says where its counters come from (no committed PMC file profiled this
+    shape, so none are replayed from another kernel)."""
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--size", "4096", "--full"]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    out = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+    assert out["steps"] == 2 and out["value"] > 0
+    assert "not replayed from another kernel" in out["roofline"]["traffic_note"]
+
+
 def test_race_screen_of_the_hand_synchronised_kernels():
     """tools/soak.py: every DMA-ring kernel repeated under an uneven background load gives the same bits
     every time and equals an independently scheduled kernel of the same arithmetic (a few seconds)."""

@@ -195,7 +195,7 @@ def test_multi_device_run_hardware_env_split(tmp_path):
 
 
 def test_multi_device_bench_eight_ranks_on_one_device_dry_run():
-    """The driver's exact N = 8 command shape, `python bench.py --gpus 8 --steps 20 --warmup 5`, launched plainly, one rank
+    """The driver's N = 8 command shape, `python bench.py --gpus 8 --steps 20 --warmup 5` (+ --full for weak_scaling), launched plainly, one rank
     per device and gloo as the control plane: the BASELINE configs[4] job, 8192 rows per rank, the large fp32 default
     kernel, one JSON line.  Eight ranks time-sharing one device would hold it from nine processes at once (the ranks and
     this one), more than a shared GPU host admits, so the test needs eight devices and skips on a smaller box."""
@@ -206,7 +206,7 @@ def test_multi_device_bench_eight_ranks_on_one_device_dry_run():
     env = {k: v for k, v in os.environ.items()
            if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "MM_BENCH_DEVICE_MOD")}
     env.update(MM_BENCH_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "20", "--warmup", "5", "--scale-base", "150000"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "20", "--warmup", "5", "--scale-base", "150000", "--full"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=1500, cwd=ROOT)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
