@@ -26,7 +26,8 @@ EXPORTS = ["mm_init", "mm_alloc", "mm_free", "mm_copy_to_device", "mm_copy_to_ho
            "mm_gemm_host", "mm_tuning_set", "mm_tuning_get", "mm_release_workspace", "mm_device_pci_bus_id",
            "mm_row_slab", "mm_gemm_multi_device_timed", "mm_gemm_batched_enqueue", "mm_gemm_batched_launch",
            "mm_kernel_name_batched", "mm_gemm_accumulate_enqueue", "mm_gemm_accumulate_launch",
-           "mm_gemm_batched_accumulate_enqueue", "mm_gemm_batched_accumulate_launch"]
+           "mm_gemm_batched_accumulate_enqueue", "mm_gemm_batched_accumulate_launch", "mm_gemm_argreduce_enqueue",
+           "mm_gemm_argreduce_launch", "mm_kernel_name_argreduce"]
 
 
 class MMError(RuntimeError):
@@ -104,6 +105,11 @@ def lib():
         L.mm_gemm_batched_accumulate_enqueue.argtypes = [vp, cfgp, vp, vp, vp, u, u, u, u, sz, sz, sz]
         L.mm_gemm_batched_accumulate_launch.argtypes = [i, cfgp, vp, vp, vp, u, u, u, u, sz, sz, sz,
                                                         ctypes.POINTER(ctypes.c_double)]
+        L.mm_gemm_argreduce_enqueue.argtypes = [vp, cfgp, vp, vp, vp, vp, u, u, u, u, sz, sz, sz, i, i]
+        L.mm_gemm_argreduce_launch.argtypes = [i, cfgp, vp, vp, vp, vp, u, u, u, u, sz, sz, sz, i, i,
+                                               ctypes.POINTER(ctypes.c_double)]
+        L.mm_kernel_name_argreduce.argtypes = [cfgp, u, u, u, u]
+        L.mm_kernel_name_argreduce.restype = ctypes.c_char_p
         _lib = L
     return _lib
 
@@ -129,6 +135,10 @@ def kernel_name(cfg, n, k, m):
 
 def kernel_name_batched(cfg, n, k, m, batch):
     return lib().mm_kernel_name_batched(ctypes.byref(cfg), n, k, m, batch).decode()
+
+
+def kernel_name_argreduce(cfg, n, k, m, batch=1):
+    return lib().mm_kernel_name_argreduce(ctypes.byref(cfg), n, k, m, batch).decode()
 
 
 def set_tuning(name, value):
@@ -318,6 +328,85 @@ def baddbmm_(c, a, b, dtype="float", map_op="Multiply", reduce_op="Add", path=PA
         _check(lib().mm_gemm_batched_accumulate_enqueue(ctypes.c_void_p(stream), ctypes.byref(cfg), a.data_ptr(),
                                                         b.data_ptr(), c.data_ptr(), n, k, m, batch, sa, sb, sc))
     return c
+
+
+def _argreduce_shapes(a, b, transposed_a):
+    """(n, k, m, batch, stride_a, stride_b) of bmm-style operands: 2-D, 3-D, or expanded with batch stride 0."""
+    if a.dim() not in (2, 3) or b.dim() not in (2, 3):
+        raise MMError("argreduce takes 2-D or 3-D operands")
+    k, m = b.shape[-2], b.shape[-1]
+    n = a.shape[-1] if transposed_a else a.shape[-2]
+    if (a.shape[-2] if transposed_a else a.shape[-1]) != k:
+        raise MMError(f"inner dimensions differ: A {tuple(a.shape)}{' (K x N)' if transposed_a else ''}, B {tuple(b.shape)}")
+    ba, sa = _batched_operand(a, "a", *((k, n) if transposed_a else (n, k)))
+    bb, sb = _batched_operand(b, "b", k, m)
+    batches = {x for x in (ba, bb) if x is not None and x != 1}
+    if len(batches) > 1:
+        raise MMError(f"batch sizes differ: {ba} and {bb}")
+    return n, k, m, (batches.pop() if batches else 1), sa, sb
+
+
+def _argreduce_enqueue(a, b, c, c_index, n, k, m, batch, sa, sb, sc, cfg, index_base, accumulate):
+    import torch
+    with torch.cuda.device(a.device):
+        stream = torch.cuda.current_stream(a.device).cuda_stream
+        _check(lib().mm_gemm_argreduce_enqueue(ctypes.c_void_p(stream), ctypes.byref(cfg), a.data_ptr(), b.data_ptr(),
+                                               c.data_ptr(), c_index.data_ptr(), n, k, m, batch, sa, sb, sc,
+                                               int(index_base), int(accumulate)))
+
+
+def matmul_argreduce(a, b, dtype="float", map_op="Add", reduce_op="Min", path=PATH_AUTO, transposed_a=False, index_base=0,
+                     out=None, out_index=None):
+    """(values, indices) of a Min- or Max-reduced product on torch's current stream (mm_gemm_argreduce_enqueue): values is
+    what matmul / bmm return with path=PATH_ORDERED, bit for bit; indices (torch.int32) holds, per output, index_base + the
+    first k whose mapped value is the result, or -1 where no k improved on identity() -- torch.min(x, dim)'s pair.
+    a and b as for bmm (2-D, 3-D, or expanded with batch stride 0); the outputs are (N, M) when both operands are 2-D,
+    else (B, N, M).  out / out_index: contiguous tensors of that shape (values' dtype, torch.int32).  Asynchronous."""
+    import torch
+    tdt = torch_dtype(dtype)
+    _device_operands("matmul_argreduce", tdt, a, b)
+    n, k, m, batch, sa, sb = _argreduce_shapes(a, b, transposed_a)
+    shape = (n, m) if a.dim() == 2 and b.dim() == 2 else (batch, n, m)
+    if out is None:
+        out = torch.empty(shape, dtype=tdt, device=a.device)
+    if out_index is None:
+        out_index = torch.empty(shape, dtype=torch.int32, device=a.device)
+    for x, name, want in ((out, "out", tdt), (out_index, "out_index", torch.int32)):
+        if tuple(x.shape) != shape or x.dtype != want or x.device != a.device or not x.is_contiguous():
+            raise MMError(f"{name} must be a contiguous {want} tensor of shape {shape} on {a.device}; got "
+                          f"{tuple(x.shape)}, {x.dtype}, {x.device}, contiguous={x.is_contiguous()}")
+    cfg = make_config(dtype, map_op, reduce_op, path, transposed_a)
+    _argreduce_enqueue(a, b, out, out_index, n, k, m, batch, sa, sb, n * m, cfg, index_base, False)
+    return out, out_index
+
+
+def addmm_argreduce_(c, c_index, a, b, dtype="float", map_op="Add", reduce_op="Min", path=PATH_AUTO, transposed_a=False,
+                     index_base=0):
+    """In place (C, I) <- argreduce seeded with (C, I) on torch's current stream (mm_gemm_argreduce_enqueue, accumulate):
+    each output's chain starts at the value C holds and the index I holds; a k that improves on it records index_base + k,
+    an output whose seed survives keeps its index exactly.  D <- min(D, A + B) of min-plus relaxation with the predecessor
+    alongside.  2-D operands as for addmm_, 3-D (and broadcast) as for baddbmm_; c_index: torch.int32 with c's shape and
+    strides.  Returns (c, c_index).  Asynchronous, like any torch op."""
+    import torch
+    tdt = torch_dtype(dtype)
+    _device_operands("addmm_argreduce_", tdt, c, a, b)
+    if not c_index.is_cuda or c_index.device != c.device or c_index.dtype != torch.int32:
+        raise MMError(f"c_index must be a torch.int32 tensor on {c.device}; got {c_index.dtype} on {c_index.device}")
+    if c.dim() not in (2, 3):
+        raise MMError("addmm_argreduce_ takes 2-D or 3-D operands")
+    if tuple(c_index.shape) != tuple(c.shape) or c_index.stride() != c.stride():
+        raise MMError(f"c_index must have c's shape and strides: {tuple(c.shape)} {c.stride()}, got "
+                      f"{tuple(c_index.shape)} {c_index.stride()}")
+    n, k, m, batch, sa, sb = _argreduce_shapes(a, b, transposed_a)
+    bc, sc = _batched_operand(c, "c", n, m)
+    if batch not in (1, bc or 1):   # a 2-D (or one-matrix) A and B broadcast over every matrix of c
+        raise MMError(f"c has shape {tuple(c.shape)}, expected ({batch}, {n}, {m})")
+    batch = bc or 1
+    if batch > 1 and sc == 0:
+        raise MMError(f"c has batch stride 0: the {batch} outputs would overlap")
+    cfg = make_config(dtype, map_op, reduce_op, path, transposed_a)
+    _argreduce_enqueue(a, b, c, c_index, n, k, m, batch, sa, sb, sc, cfg, index_base, True)
+    return c, c_index
 
 
 def row_slab(cfg, n, k, m, world_size, rank):

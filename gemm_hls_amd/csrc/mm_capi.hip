@@ -361,6 +361,74 @@ int check_accumulate(const mm_config_t *cfg, const mm::Problem &p, Family *fam) 
   return MM_OK;
 }
 
+// ---- argreduce (mm_gemm_argreduce_*): Min / Max with the winning k ----------------------------------------------------
+enum ArKernel { AR_NONE, AR_PLAIN, AR_TILE };
+
+// The kernel by configuration and shape alone (mm_kernel_name_argreduce); alignment may still demote AR_TILE at launch.
+ArKernel argreduce_kernel_for(const mm_config_t &cfg, const mm::Problem &p) {
+  if (cfg.reduce_op != MM_OP_MIN && cfg.reduce_op != MM_OP_MAX) return AR_NONE;
+  if (cfg.path == MM_PATH_SPLIT) return AR_NONE;
+  if (cfg.path == MM_PATH_ORDERED) return AR_PLAIN;
+  // the tile holds 8 x 8 values per thread: instantiated for elements of at most 4 bytes (mm_argreduce.inc)
+  return mm::valu_tile_serves(cfg, p) && mm_dtype_size(cfg.dtype) <= 4 ? AR_TILE : AR_PLAIN;
+}
+
+// All argument checks of an argreduce call, before any device is touched.  *ker = AR_NONE: nothing to launch (an empty
+// batch, or K = 0 when accumulating).
+int check_argreduce(const mm_config_t *cfg, const mm::Problem &p, const int *index, int index_base, ArKernel *ker) {
+  *ker = AR_NONE;
+  if (!valid_cfg(cfg)) return fail(MM_ERR_BAD_ARGUMENT, "invalid mm_config_t");
+  if (cfg->reduce_op != MM_OP_MIN && cfg->reduce_op != MM_OP_MAX)
+    return fail(MM_ERR_UNSUPPORTED, "argreduce needs a Min or Max reduction (got reduce %d)", (int)cfg->reduce_op);
+  if (cfg->path == MM_PATH_SPLIT) return fail(MM_ERR_UNSUPPORTED, "MM_PATH_SPLIT has no argreduce form");
+  if (p.k == 0 && !p.seed) return fail(MM_ERR_BAD_ARGUMENT, "size_k must be positive");
+  if (index_base < 0) return fail(MM_ERR_BAD_ARGUMENT, "index_base %d is negative", index_base);
+  if (p.k > 0 && (long long)index_base + p.k - 1 > (long long)INT32_MAX)
+    return fail(MM_ERR_BAD_ARGUMENT, "index_base %d + K - 1 (K = %u) does not fit an int32 index", index_base, p.k);
+  if (p.batch == 0 || p.n == 0 || p.m == 0) return MM_OK;   // nothing to write
+  if (!p.a || !p.b || !p.c || !index) return fail(MM_ERR_BAD_ARGUMENT, "null matrix or index pointer");
+  if (p.batch > 1 && p.stride_c < (size_t)p.n * p.m)
+    return fail(MM_ERR_BAD_ARGUMENT, "stride_c %zu < N * M = %zu: the outputs of the batch would overlap", p.stride_c,
+                (size_t)p.n * p.m);
+  const size_t es = mm_dtype_size(cfg->dtype), nm = (size_t)p.n * p.m;
+  const size_t a_bytes = batch_span((size_t)p.n * p.k, p.stride_a, p.batch, es);
+  const size_t b_bytes = batch_span((size_t)p.k * p.m, p.stride_b, p.batch, es);
+  const size_t c_bytes = batch_span(nm, p.stride_c, p.batch, es), i_bytes = batch_span(nm, p.stride_c, p.batch, sizeof(int));
+  if (spans_overlap(p.c, c_bytes, p.a, a_bytes) || spans_overlap(p.c, c_bytes, p.b, b_bytes) ||
+      spans_overlap(index, i_bytes, p.a, a_bytes) || spans_overlap(index, i_bytes, p.b, b_bytes) ||
+      spans_overlap(index, i_bytes, p.c, c_bytes))
+    return fail(MM_ERR_BAD_ARGUMENT, "c or c_index overlaps a, b or each other (bases %p, %p, %p, %p)", p.a, p.b, p.c,
+                (const void *)index);
+  if (p.k == 0) return MM_OK;   // accumulating over no k: C and I keep their values
+  *ker = argreduce_kernel_for(*cfg, p);
+  // the tile kernel moves 16 bytes per lane: every element's a, b, c and index 16-byte aligned, else the predicated kernel
+  if (*ker == AR_TILE && (!batch_aligned16(p, es) || ((uintptr_t)index & 15u) != 0 ||
+                          (p.batch > 1 && (p.stride_c * sizeof(int)) % 16 != 0)))
+    *ker = AR_PLAIN;
+  return MM_OK;
+}
+
+// Launches the batch as consecutive launches of at most batch_chunk() elements on `s`, C and I advancing together.
+int dispatch_argreduce(hipStream_t s, const mm_config_t &cfg, const mm::Problem &p, int *index, int index_base,
+                       ArKernel ker) {
+  const size_t es = mm_dtype_size(cfg.dtype);
+  const unsigned chunk = batch_chunk(p);
+  (void)hipGetLastError();   // a stale error of the application's own calls must not be reported as this launch's
+  for (unsigned e0 = 0; e0 < p.batch; e0 += chunk) {
+    mm::Problem q = p;
+    q.batch = std::min(chunk, p.batch - e0);
+    q.a = (const char *)p.a + (size_t)e0 * p.stride_a * es;
+    q.b = (const char *)p.b + (size_t)e0 * p.stride_b * es;
+    q.c = (char *)p.c + (size_t)e0 * p.stride_c * es;
+    const int e = mm::launch_argreduce(s, cfg, q, index + (size_t)e0 * p.stride_c, index_base, ker == AR_TILE);
+    if (e == mm::kErrNotSupported)
+      return fail(MM_ERR_UNSUPPORTED, "argreduce configuration (dtype %d, map %d, reduce %d) is not compiled into this library",
+                  (int)cfg.dtype, (int)cfg.map_op, (int)cfg.reduce_op);
+    if (e != 0) return hip_fail((hipError_t)e, "argreduce kernel launch");
+  }
+  return MM_OK;
+}
+
 // hipEvent_t with a destructor: no exit path of the timed launch can leak one
 struct Event {
   hipEvent_t e = nullptr;
@@ -676,6 +744,48 @@ int mm_gemm_accumulate_enqueue(void *hip_stream, const mm_config_t *cfg, const v
 int mm_gemm_accumulate_launch(int device, const mm_config_t *cfg, const void *a, const void *b, void *c, unsigned n,
                               unsigned k, unsigned m, double *elapsed_seconds) {
   return mm_gemm_batched_accumulate_launch(device, cfg, a, b, c, n, k, m, 1, 0, 0, 0, elapsed_seconds);
+}
+
+int mm_gemm_argreduce_enqueue(void *hip_stream, const mm_config_t *cfg, const void *a, const void *b, void *c, int *c_index,
+                              unsigned n, unsigned k, unsigned m, unsigned batch, size_t stride_a, size_t stride_b,
+                              size_t stride_c, int index_base, int accumulate) {
+  mm::Problem p = batched_problem(cfg, a, b, c, n, k, m, batch, stride_a, stride_b, stride_c);
+  p.seed = accumulate != 0;
+  ArKernel ker;
+  int rc = check_argreduce(cfg, p, c_index, index_base, &ker);
+  if (rc || ker == AR_NONE) return rc;   // (AR_NONE: an empty batch or K = 0 accumulating, nothing to do)
+  if ((rc = ensure_init())) return rc;
+  return dispatch_argreduce((hipStream_t)hip_stream, *cfg, p, c_index, index_base, ker);
+}
+
+int mm_gemm_argreduce_launch(int device, const mm_config_t *cfg, const void *a, const void *b, void *c, int *c_index,
+                             unsigned n, unsigned k, unsigned m, unsigned batch, size_t stride_a, size_t stride_b,
+                             size_t stride_c, int index_base, int accumulate, double *elapsed_seconds) {
+  mm::Problem p = batched_problem(cfg, a, b, c, n, k, m, batch, stride_a, stride_b, stride_c);
+  p.seed = accumulate != 0;
+  ArKernel ker;
+  int rc = check_argreduce(cfg, p, c_index, index_base, &ker);
+  if (rc) return rc;
+  if (ker == AR_NONE) {   // nothing to launch or time
+    if (elapsed_seconds) *elapsed_seconds = 0.0;
+    return MM_OK;
+  }
+  if ((rc = check_device(device))) return rc;
+  MM_HIP(hipSetDevice(device));
+  Event start, stop;
+  MM_HIP(hipEventCreate(&start.e));
+  MM_HIP(hipEventCreate(&stop.e));
+  MM_HIP(hipEventRecord(start.e, nullptr));
+  rc = dispatch_argreduce(nullptr, *cfg, p, c_index, index_base, ker);
+  if (rc != MM_OK) return rc;
+  MM_HIP(hipEventRecord(stop.e, nullptr));
+  MM_HIP(hipEventSynchronize(stop.e));
+  if (elapsed_seconds) {
+    float ms = 0.f;
+    MM_HIP(hipEventElapsedTime(&ms, start.e, stop.e));
+    *elapsed_seconds = 1e-3 * (double)ms;
+  }
+  return MM_OK;
 }
 
 // Rows per device of the N split: ceil(N / G) rounded up to whole tile rows of the kernel that will run on a slab of that
@@ -1026,6 +1136,16 @@ const char *mm_kernel_name_batched(const mm_config_t *cfg, unsigned n, unsigned 
     case FAM_ORDERED_TILE: return "ordered_tile";
     case FAM_NONE: return "unsupported";
     default: return "ordered";
+  }
+}
+
+const char *mm_kernel_name_argreduce(const mm_config_t *cfg, unsigned n, unsigned k, unsigned m, unsigned batch) {
+  if (!valid_cfg(cfg)) return "invalid";
+  const mm::Problem p = batched_problem(cfg, nullptr, nullptr, nullptr, n, k, m, batch ? batch : 1, 0, 0, 0);
+  switch (argreduce_kernel_for(*cfg, p)) {   // the choice check_argreduce makes, before alignment
+    case AR_TILE: return "argreduce_tile";
+    case AR_PLAIN: return "argreduce";
+    default: return "unsupported";
   }
 }
 

@@ -129,6 +129,10 @@ bool valu_tile_serves(const mm_config_t &cfg, const Problem &p);
 // with contraction off and Op<> to the letter (mm_valu_tile_fp_exact.hip); the integer types' kernels are bit-identical to
 // Naive as they are.  Serves whenever valu_tile_serves() and the operands are 16-byte aligned.
 int launch_valu_tile_exact(hipStream_t s, const mm_config_t &cfg, const Problem &p);
+// Min / Max reductions with the winning k (mm_gemm_argreduce_*, mm_argreduce_*.hip): the p.batch elements of p, C and the
+// int32 index matrix `index` with the same element strides (p.stride_c); p.seed starts from C and `index`.  tile: the
+// register-tiled argreduce_tile kernel (valu_tile_serves() and 16-byte aligned operands), else the predicated argreduce.
+int launch_argreduce(hipStream_t s, const mm_config_t &cfg, const Problem &p, int *index, int index_base, bool tile);
 int launch_mfma_f32(hipStream_t s, const Problem &p, int variant);
 int launch_mfma_f64(hipStream_t s, const Problem &p);
 int launch_mfma_f16(hipStream_t s, const Problem &p);

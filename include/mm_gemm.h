@@ -226,6 +226,45 @@ int mm_gemm_batched_accumulate_launch(int device, const mm_config_t *cfg, const 
                                       unsigned size_n, unsigned size_k, unsigned size_m, unsigned batch, size_t stride_a,
                                       size_t stride_b, size_t stride_c, double *elapsed_seconds);
 
+/* Argmin / argmax: a Min- or Max-reduced product that also returns, per output, the k that produced it (the witness:
+ * predecessor matrices of shortest paths, Viterbi backpointers, bottleneck paths) -- torch.min(x, dim)'s (values, indices).
+ * For output (e, i, j) of the batch, with Reduce = cfg->reduce_op in {Min, Max}:
+ *     acc = accumulate ? C[e,i,j] : Reduce::identity();   idx = accumulate ? I[e,i,j] : -1
+ *     for k = 0 .. K-1 ascending:
+ *         s = Map(A[e,i,k], B[e,k,j])                     (Op<MAP, T>::apply; integers wrap as everywhere)
+ *         if (Min: s < acc  /  Max: acc < s) { acc = s; idx = index_base + k; }
+ *     C[e,i,j] = acc;  I[e,i,j] = idx
+ * So C is bit for bit what MM_PATH_ORDERED's mm_gemm_batched_launch (plain) / mm_gemm_batched_accumulate_launch
+ * (accumulate) returns, NaN, +-inf and +-0 included, under MM_PATH_AUTO too (no minNum / maxNum here, and
+ * MM_HALF_CONTRACT does not apply); ties keep the smallest k; a NaN mapped value is never taken; -1 = no k improved on
+ * the identity (e.g. every path +inf, or max()); when accumulating, an index whose seed survives is left exactly as it was.
+ * c_index: int32, the same shape and element strides (stride_c) as C.  index_base >= 0 shifts the recorded k (a blocked
+ * or K-split caller records global k: A[:, K1:], B[K1:] with index_base = K1); index_base + K - 1 must not exceed
+ * INT32_MAX.  Every other argument as for mm_gemm_batched_* (strides in elements, 0 = broadcast, stride_c >= N * M when
+ * batch > 1; batch, N or M 0: MM_OK).  K = 0: MM_ERR_BAD_ARGUMENT in the plain form, MM_OK (nothing changes) when
+ * accumulating.  Refused before any device is touched: a reduction other than Min / Max and MM_PATH_SPLIT
+ * (MM_ERR_UNSUPPORTED); a null pointer, a bad index_base, and the span of C or of I overlapping A, B or each other (the
+ * span test of the accumulating calls; MM_ERR_BAD_ARGUMENT).
+ * Kernels (mm_kernel_name_argreduce): "argreduce_tile" (register-tiled, 128 x 128 outputs per workgroup) under
+ * MM_PATH_AUTO where valu_tile serves -- K % 4 == 0, M % 4 == 0 (and N % 4 == 0 for a K x N A), a map other than And --
+ * for elements of at most 4 bytes; "argreduce" (fully predicated, any shape, any element-aligned pointer) otherwise --
+ * double, long and unsigned long always -- and always under MM_PATH_ORDERED.
+ * The name is decided by shape and path alone: a launch whose a, b, c, c_index (or element strides) are not 16-byte
+ * aligned runs "argreduce" instead -- the same bits, no error.  The batch is split into launches as for the batched calls.
+ * _enqueue: asynchronous on a hipStream_t of the CURRENT device; _launch: blocking, *elapsed_seconds (may be NULL) timed
+ * with HIP events.  A single problem is batch = 1. */
+int mm_gemm_argreduce_enqueue(void *hip_stream, const mm_config_t *cfg, const void *a_dev, const void *b_dev, void *c_dev,
+                              int *c_index, unsigned size_n, unsigned size_k, unsigned size_m, unsigned batch,
+                              size_t stride_a, size_t stride_b, size_t stride_c, int index_base, int accumulate);
+int mm_gemm_argreduce_launch(int device, const mm_config_t *cfg, const void *a_dev, const void *b_dev, void *c_dev,
+                             int *c_index, unsigned size_n, unsigned size_k, unsigned size_m, unsigned batch,
+                             size_t stride_a, size_t stride_b, size_t stride_c, int index_base, int accumulate,
+                             double *elapsed_seconds);
+/* Name of the kernel mm_gemm_argreduce_* runs for this shape ("argreduce_tile", "argreduce"; "unsupported" for a reduction
+ * other than Min / Max or MM_PATH_SPLIT; "invalid" for a bad configuration).  Static string, pure arithmetic. */
+const char *mm_kernel_name_argreduce(const mm_config_t *cfg, unsigned size_n, unsigned size_k, unsigned size_m,
+                                     unsigned batch);
+
 /* One node, `device_count` GPUs, rows of C split into contiguous slabs (device g gets the rows mm_row_slab() names), B
  * replicated, no collective: every outer tile of C is independent (kernel/Compute.cpp:53-60, kernel/Memory.cpp:114-127,
  * 272-286, 367-391).  Host pointers in, host pointer out; copies are outside the timed region exactly as in
