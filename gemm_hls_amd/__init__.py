@@ -27,7 +27,8 @@ EXPORTS = ["mm_init", "mm_alloc", "mm_free", "mm_copy_to_device", "mm_copy_to_ho
            "mm_row_slab", "mm_gemm_multi_device_timed", "mm_gemm_batched_enqueue", "mm_gemm_batched_launch",
            "mm_kernel_name_batched", "mm_gemm_accumulate_enqueue", "mm_gemm_accumulate_launch",
            "mm_gemm_batched_accumulate_enqueue", "mm_gemm_batched_accumulate_launch", "mm_gemm_argreduce_enqueue",
-           "mm_gemm_argreduce_launch", "mm_kernel_name_argreduce"]
+           "mm_gemm_argreduce_launch", "mm_kernel_name_argreduce", "mm_closure_enqueue", "mm_closure_launch",
+           "mm_kernel_name_closure"]
 
 
 class MMError(RuntimeError):
@@ -110,6 +111,10 @@ def lib():
                                                ctypes.POINTER(ctypes.c_double)]
         L.mm_kernel_name_argreduce.argtypes = [cfgp, u, u, u, u]
         L.mm_kernel_name_argreduce.restype = ctypes.c_char_p
+        L.mm_closure_enqueue.argtypes = [vp, cfgp, vp, vp, u, u, sz]
+        L.mm_closure_launch.argtypes = [i, cfgp, vp, vp, u, u, sz, ctypes.POINTER(ctypes.c_double)]
+        L.mm_kernel_name_closure.argtypes = [cfgp, u, u, i]
+        L.mm_kernel_name_closure.restype = ctypes.c_char_p
         _lib = L
     return _lib
 
@@ -139,6 +144,10 @@ def kernel_name_batched(cfg, n, k, m, batch):
 
 def kernel_name_argreduce(cfg, n, k, m, batch=1):
     return lib().mm_kernel_name_argreduce(ctypes.byref(cfg), n, k, m, batch).decode()
+
+
+def kernel_name_closure(cfg, n, batch=1, with_witness=False):
+    return lib().mm_kernel_name_closure(ctypes.byref(cfg), n, batch, int(bool(with_witness))).decode()
 
 
 def set_tuning(name, value):
@@ -407,6 +416,36 @@ def addmm_argreduce_(c, c_index, a, b, dtype="float", map_op="Add", reduce_op="M
     cfg = make_config(dtype, map_op, reduce_op, path, transposed_a)
     _argreduce_enqueue(a, b, c, c_index, n, k, m, batch, sa, sb, sc, cfg, index_base, True)
     return c, c_index
+
+
+def closure_(d, d_witness=None, dtype="float", map_op="Add", reduce_op="Min", path=PATH_AUTO):
+    """In place D <- the closure of D (mm_closure_enqueue) on torch's current stream: blocked Floyd-Warshall,
+    D[i][j] <- D[i][j] (+) D[i][v] (x) D[v][j] over every v -- all-pairs shortest paths for (Add, Min), widest paths for
+    (Min, Max), reachability for (And, Max).  No identity is added to the diagonal (paths of one or more edges).
+    d: a contiguous (n, n) or (batch, n, n) device tensor of `dtype`; d_witness (optional): a contiguous torch.int32 tensor
+    of d's shape, fully written with the intermediate vertex of each entry's last strict improvement, -1 where the entry
+    kept its input value.  Returns d.  Asynchronous, like any torch op."""
+    import torch
+    tdt = torch_dtype(dtype)
+    _device_operands("closure_", tdt, d)
+    if d.dim() not in (2, 3) or d.shape[-1] != d.shape[-2]:
+        raise MMError(f"closure_ takes an (n, n) or (batch, n, n) tensor; got shape {tuple(d.shape)}")
+    if not d.is_contiguous():
+        raise MMError("closure_ needs a contiguous (row-major) d")
+    n, batch = d.shape[-1], (d.shape[0] if d.dim() == 3 else 1)
+    w = 0
+    if d_witness is not None:
+        if (not d_witness.is_cuda or d_witness.device != d.device or d_witness.dtype != torch.int32
+                or tuple(d_witness.shape) != tuple(d.shape) or not d_witness.is_contiguous()):
+            raise MMError(f"d_witness must be a contiguous torch.int32 tensor of shape {tuple(d.shape)} on {d.device}; got "
+                          f"{tuple(d_witness.shape)}, {d_witness.dtype}, {d_witness.device}, "
+                          f"contiguous={d_witness.is_contiguous()}")
+        w = d_witness.data_ptr()
+    cfg = make_config(dtype, map_op, reduce_op, path)
+    with torch.cuda.device(d.device):
+        stream = torch.cuda.current_stream(d.device).cuda_stream
+        _check(lib().mm_closure_enqueue(ctypes.c_void_p(stream), ctypes.byref(cfg), d.data_ptr(), w, n, batch, n * n))
+    return d
 
 
 def row_slab(cfg, n, k, m, world_size, rank):

@@ -92,10 +92,12 @@ std::once_flag g_tuning_once;
 std::atomic<int> g_tuning[mm::TUNE_COUNT];
 const char *const kTuneName[mm::TUNE_COUNT] = {"f32_variant", "f64_variant", "f16_variant", "i8_variant", "band_rows",
                                                "valu_variant", "split_variant", "f32_splitk", "ablations", "debug_poison", "kxn_prepass_min_m",
-                                               "md_virtual_devices", "ordered_variant", "half_contract", "batch_chunk"};
+                                               "md_virtual_devices", "ordered_variant", "half_contract", "batch_chunk",
+                                               "closure_block"};
 const char *const kTuneEnv[mm::TUNE_COUNT] = {"MM_F32_VARIANT", "MM_F64_VARIANT", "MM_F16_VARIANT", "MM_I8_VARIANT",
                                               "MM_BAND_ROWS", "MM_VALU_VARIANT", "MM_SPLIT_VARIANT", "MM_F32_SPLITK", "MM_ABLATIONS", "MM_DEBUG_POISON", "MM_KXN_PREPASS_MIN_M",
-                                              "MM_MD_VIRTUAL_DEVICES", "MM_ORDERED_VARIANT", "MM_HALF_CONTRACT", "MM_BATCH_CHUNK"};
+                                              "MM_MD_VIRTUAL_DEVICES", "MM_ORDERED_VARIANT", "MM_HALF_CONTRACT", "MM_BATCH_CHUNK",
+                                              "MM_CLOSURE_BLOCK"};
 void tuning_init() {
   for (int i = 0; i < mm::TUNE_COUNT; ++i) {
     const char *e = getenv(kTuneEnv[i]);
@@ -427,6 +429,129 @@ int dispatch_argreduce(hipStream_t s, const mm_config_t &cfg, const mm::Problem 
     if (e != 0) return hip_fail((hipError_t)e, "argreduce kernel launch");
   }
   return MM_OK;
+}
+
+// ---- closure (mm_closure_*): blocked Floyd-Warshall in place -------------------------------------------------------
+// Block size B: the closure_block knob -- 64, 128, or 256 for the value-only form of elements of at most 4 bytes (the
+// kernels' register sub-blocks, mm_closure.inc) -- else 256 for that form and 128 for the others.  0: the knob holds a value
+// this form does not take.
+unsigned closure_block(const mm_config_t &cfg, bool witness) {
+  const bool big = !witness && mm_dtype_size(cfg.dtype) <= 4;
+  const int knob = mm::tuning(mm::TUNE_CLOSURE_BLOCK);
+  if (knob == -1) return big ? 256 : 128;
+  return (knob == 64 || knob == 128 || (knob == 256 && big)) ? (unsigned)knob : 0;
+}
+
+// All argument checks of a closure call, before any device is touched.  *block = 0: nothing to do (n or batch 0).
+int check_closure(const mm_config_t *cfg, const void *d, const int *w, unsigned n, unsigned batch, size_t stride_d,
+                  unsigned *block) {
+  *block = 0;
+  if (!valid_cfg(cfg)) return fail(MM_ERR_BAD_ARGUMENT, "invalid mm_config_t");
+  if (cfg->reduce_op != MM_OP_MIN && cfg->reduce_op != MM_OP_MAX)
+    return fail(MM_ERR_UNSUPPORTED, "a closure needs an idempotent reduction, Min or Max (got reduce %d)", (int)cfg->reduce_op);
+  if (cfg->path == MM_PATH_SPLIT) return fail(MM_ERR_UNSUPPORTED, "MM_PATH_SPLIT has no closure form");
+  if (cfg->layout_a == MM_A_TRANSPOSED) return fail(MM_ERR_BAD_ARGUMENT, "a closure has no A operand to transpose");
+  const unsigned b = closure_block(*cfg, w != nullptr);
+  if (!b)
+    return fail(MM_ERR_BAD_ARGUMENT, "closure_block %d is not a block size of this form (64, 128%s)",
+                mm::tuning(mm::TUNE_CLOSURE_BLOCK), !w && mm_dtype_size(cfg->dtype) <= 4 ? " or 256" : "");
+  if (n == 0 || batch == 0) return MM_OK;   // nothing to do
+  if (!d) return fail(MM_ERR_BAD_ARGUMENT, "null matrix pointer");
+  const size_t nn = (size_t)n * n;
+  if (batch > 1 && stride_d < nn)
+    return fail(MM_ERR_BAD_ARGUMENT, "stride_d %zu < n * n = %zu: the graphs of the batch would overlap", stride_d, nn);
+  if (w && spans_overlap(d, batch_span(nn, stride_d, batch, mm_dtype_size(cfg->dtype)), w,
+                         batch_span(nn, stride_d, batch, sizeof(int))))
+    return fail(MM_ERR_BAD_ARGUMENT, "witness overlaps d (bases %p, %p)", d, (const void *)w);
+  *block = b;
+  return MM_OK;
+}
+
+// Snapshot workspace of one chunk of the batch stays below this; a graph that alone needs more runs alone.
+constexpr size_t kClosureWorkspaceCap = 256ull << 20;
+
+// Step 3 of a round: D <- D (+) Cc (x) Rc over every graph of the chunk, seeded, on the existing kernels.  Value-only: the
+// accumulating batched call's kernel (a D that is not 16-byte aligned per graph runs the k-ordered one under
+// MM_PATH_AUTO: the same values); with witnesses: the seeded argreduce kernel, index_base = k0.
+int closure_rank_update(hipStream_t s, const mm_config_t &cfg, mm::Problem q, int *w, unsigned k0) {
+  q.seed = true;
+  if (w) {
+    ArKernel ker;
+    int rc = check_argreduce(&cfg, q, w, (int)k0, &ker);
+    return rc ? rc : dispatch_argreduce(s, cfg, q, w, (int)k0, ker);
+  }
+  mm_config_t c3 = cfg;
+  if (cfg.path == MM_PATH_AUTO && !batch_aligned16(q, mm_dtype_size(cfg.dtype))) c3.path = MM_PATH_ORDERED;
+  Family fam;
+  int rc = check_accumulate(&c3, q, &fam);
+  return rc ? rc : dispatch_batched(s, c3, q, fam);
+}
+
+int closure_step(hipStream_t s, const mm_config_t &cfg, const mm::ClosureStep &st) {
+  const int e = mm::launch_closure(s, cfg, st);
+  if (e == mm::kErrNotSupported)
+    return fail(MM_ERR_UNSUPPORTED, "closure configuration (dtype %d, map %d, reduce %d, block %u) is not compiled into this "
+                "library", (int)cfg.dtype, (int)cfg.map_op, (int)cfg.reduce_op, st.bt);
+  return e ? hip_fail((hipError_t)e, st.panels ? "closure panel kernel launch" : "closure diagonal kernel launch") : MM_OK;
+}
+
+// The closure on stream `s`, never synchronising the host.  n <= B: one on-chip launch per chunk of graphs.  Otherwise, per
+// chunk of graphs, rounds of (diagonal, panels, rank-B update) with the snapshots in stream-ordered workspace.
+int dispatch_closure(hipStream_t s, const mm_config_t &cfg, void *d, int *w, unsigned n, unsigned batch, size_t stride_d,
+                     unsigned B) {
+  const size_t es = mm_dtype_size(cfg.dtype), nn = (size_t)n * n;
+  if (batch == 1) stride_d = nn;
+  (void)hipGetLastError();   // a stale error of the application's own calls must not be reported as this launch's
+  mm::ClosureStep st{};
+  st.n = n;
+  st.stride_d = stride_d;
+  if (n <= B) {
+    const unsigned chunk = 1u << 20;   // workgroups per launch (of up to 1024 threads)
+    for (unsigned e0 = 0; e0 < batch; e0 += chunk) {
+      st.d = (char *)d + (size_t)e0 * stride_d * es;
+      st.w = w ? w + (size_t)e0 * stride_d : nullptr;
+      st.graphs = std::min(chunk, batch - e0);
+      st.bt = n;
+      st.w_fresh = 1;
+      if (int rc = closure_step(s, cfg, st)) return rc;
+    }
+    return MM_OK;
+  }
+  const size_t sn = ((size_t)n * B + 63) & ~(size_t)63;   // elements of one snapshot: 16-byte aligned for every element size
+  const unsigned chunk = (unsigned)std::min<size_t>(batch, std::max<size_t>(1, kClosureWorkspaceCap / (2 * sn * es)));
+  int dev = 0;
+  MM_HIP(hipGetDevice(&dev));
+  hipMemPool_t pool = nullptr;
+  if (int e = mm::workspace_pool(dev, &pool)) return hip_fail((hipError_t)e, "workspace pool");
+  void *ws = nullptr;
+  MM_HIP(hipMallocFromPoolAsync(&ws, 2 * sn * chunk * es, pool, s));
+  st.cc = ws;
+  st.rc = (char *)ws + sn * chunk * es;
+  st.stride_ws = sn;
+  int rc = MM_OK;
+  for (unsigned e0 = 0; e0 < batch && rc == MM_OK; e0 += chunk) {
+    st.graphs = std::min(chunk, batch - e0);
+    st.d = (char *)d + (size_t)e0 * stride_d * es;
+    st.w = w ? w + (size_t)e0 * stride_d : nullptr;
+    if (st.w) {   // every witness starts at -1
+      const hipError_t e = hipMemset2DAsync(st.w, stride_d * sizeof(int), 0xFF, nn * sizeof(int), st.graphs, s);
+      if (e != hipSuccess) rc = hip_fail(e, "hipMemset2DAsync (witness)");
+    }
+    for (unsigned k0 = 0; k0 < n && rc == MM_OK; k0 += B) {
+      st.k0 = k0;
+      st.bt = std::min(B, n - k0);
+      st.panels = false;
+      st.w_fresh = 0;
+      if ((rc = closure_step(s, cfg, st))) break;
+      st.panels = true;
+      if ((rc = closure_step(s, cfg, st))) break;
+      const mm::Problem q = batched_problem(&cfg, st.cc, st.rc, st.d, n, st.bt, n, st.graphs, sn, sn, stride_d);
+      rc = closure_rank_update(s, cfg, q, st.w, k0);
+    }
+  }
+  const hipError_t f = hipFreeAsync(ws, s);
+  if (rc == MM_OK && f != hipSuccess) rc = hip_fail(f, "hipFreeAsync (closure workspace)");
+  return rc;
 }
 
 // hipEvent_t with a destructor: no exit path of the timed launch can leak one
@@ -777,6 +902,42 @@ int mm_gemm_argreduce_launch(int device, const mm_config_t *cfg, const void *a, 
   MM_HIP(hipEventCreate(&stop.e));
   MM_HIP(hipEventRecord(start.e, nullptr));
   rc = dispatch_argreduce(nullptr, *cfg, p, c_index, index_base, ker);
+  if (rc != MM_OK) return rc;
+  MM_HIP(hipEventRecord(stop.e, nullptr));
+  MM_HIP(hipEventSynchronize(stop.e));
+  if (elapsed_seconds) {
+    float ms = 0.f;
+    MM_HIP(hipEventElapsedTime(&ms, start.e, stop.e));
+    *elapsed_seconds = 1e-3 * (double)ms;
+  }
+  return MM_OK;
+}
+
+int mm_closure_enqueue(void *hip_stream, const mm_config_t *cfg, void *d, int *witness, unsigned n, unsigned batch,
+                       size_t stride_d) {
+  unsigned block;
+  int rc = check_closure(cfg, d, witness, n, batch, stride_d, &block);
+  if (rc || block == 0) return rc;   // (block 0: n or batch 0, nothing to do)
+  if ((rc = ensure_init())) return rc;
+  return dispatch_closure((hipStream_t)hip_stream, *cfg, d, witness, n, batch, stride_d, block);
+}
+
+int mm_closure_launch(int device, const mm_config_t *cfg, void *d, int *witness, unsigned n, unsigned batch, size_t stride_d,
+                      double *elapsed_seconds) {
+  unsigned block;
+  int rc = check_closure(cfg, d, witness, n, batch, stride_d, &block);
+  if (rc) return rc;
+  if (block == 0) {   // nothing to launch or time
+    if (elapsed_seconds) *elapsed_seconds = 0.0;
+    return MM_OK;
+  }
+  if ((rc = check_device(device))) return rc;
+  MM_HIP(hipSetDevice(device));
+  Event start, stop;
+  MM_HIP(hipEventCreate(&start.e));
+  MM_HIP(hipEventCreate(&stop.e));
+  MM_HIP(hipEventRecord(start.e, nullptr));
+  rc = dispatch_closure(nullptr, *cfg, d, witness, n, batch, stride_d, block);
   if (rc != MM_OK) return rc;
   MM_HIP(hipEventRecord(stop.e, nullptr));
   MM_HIP(hipEventSynchronize(stop.e));
@@ -1147,6 +1308,15 @@ const char *mm_kernel_name_argreduce(const mm_config_t *cfg, unsigned n, unsigne
     case AR_PLAIN: return "argreduce";
     default: return "unsupported";
   }
+}
+
+const char *mm_kernel_name_closure(const mm_config_t *cfg, unsigned n, unsigned batch, int with_witness) {
+  (void)batch;   // the batch is chunked, never a different kernel
+  if (!valid_cfg(cfg)) return "invalid";
+  if ((cfg->reduce_op != MM_OP_MIN && cfg->reduce_op != MM_OP_MAX) || cfg->path == MM_PATH_SPLIT) return "unsupported";
+  const unsigned b = closure_block(*cfg, with_witness != 0);   // the choice check_closure makes
+  if (cfg->layout_a == MM_A_TRANSPOSED || b == 0) return "invalid";
+  return n <= b ? "closure_onchip" : "closure_blocked";
 }
 
 int mm_kernel_info(const mm_config_t *cfg, unsigned n, unsigned k, unsigned m, mm_kernel_info_t *info) {

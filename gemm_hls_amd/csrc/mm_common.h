@@ -133,6 +133,22 @@ int launch_valu_tile_exact(hipStream_t s, const mm_config_t &cfg, const Problem 
 // int32 index matrix `index` with the same element strides (p.stride_c); p.seed starts from C and `index`.  tile: the
 // register-tiled argreduce_tile kernel (valu_tile_serves() and 16-byte aligned operands), else the predicated argreduce.
 int launch_argreduce(hipStream_t s, const mm_config_t &cfg, const Problem &p, int *index, int index_base, bool tile);
+// One launch of a closure round (mm_closure_*.hip): block K = [k0, k0 + bt) of `graphs` graphs at d + e * stride_d, n x n
+// each; w (int32, D's strides) null for the value-only form.  panels = false: step 1 (closure_diag_kernel, one workgroup per
+// graph; w_fresh: start the witnesses at -1 instead of reading w); true: step 2 (closure_panel_kernel).  cc / rc: the
+// snapshots D[:,K] (n x bt) and D[K,:] (bt x n) at cc + e * stride_ws, rc + e * stride_ws (null in step 1 of an on-chip
+// closure).  bt <= 128, or <= 256 for value-only elements of at most 4 bytes.
+struct ClosureStep {
+  void *d;
+  int *w;
+  unsigned n, graphs, k0, bt;
+  size_t stride_d;
+  void *cc, *rc;
+  size_t stride_ws;
+  bool panels;
+  int w_fresh;
+};
+int launch_closure(hipStream_t s, const mm_config_t &cfg, const ClosureStep &st);
 int launch_mfma_f32(hipStream_t s, const Problem &p, int variant);
 int launch_mfma_f64(hipStream_t s, const Problem &p);
 int launch_mfma_f16(hipStream_t s, const Problem &p);
@@ -208,6 +224,7 @@ enum Tunable {
                            //                 (binary16 products and binary16 accumulation, k ascending: kernel/Compute.cpp:129-133) on the
                            //                 k-ordered tile kernel instead of the matrix cores' f32 accumulation; 0 / "wide" / unset: f32
   TUNE_BATCH_CHUNK,        // MM_BATCH_CHUNK  mm_gemm_batched_*: at most this many elements per launch (tests); -1: only the grid limits
+  TUNE_CLOSURE_BLOCK,      // MM_CLOSURE_BLOCK  block size B of mm_closure_* (64, 128, or 256 where the form allows it); -1: the default
   TUNE_COUNT
 };
 int tuning(Tunable t);  // mm_capi.hip

@@ -265,6 +265,45 @@ int mm_gemm_argreduce_launch(int device, const mm_config_t *cfg, const void *a_d
 const char *mm_kernel_name_argreduce(const mm_config_t *cfg, unsigned size_n, unsigned size_k, unsigned size_m,
                                      unsigned batch);
 
+/* Closure: all-pairs shortest / widest / longest paths and transitive closure -- blocked Floyd-Warshall, in place.
+ * D is n x n, row-major; graph e of the batch starts at d_dev + e * stride_d (elements; stride_d >= n * n when batch > 1).
+ * The call runs the recurrence D[i][j] <- D[i][j] (+) D[i][v] (x) D[v][j] over every v, with Reduce = cfg->reduce_op in
+ * {Min, Max} and Map = cfg->map_op (every dtype, every map: 110 configurations).  No identity is added to the diagonal, so the
+ * result is A+ (paths of one or more edges); for A* the caller first sets the diagonal to the map's identity (0 for Add, 1 for
+ * Multiply and And, ...).
+ * The caller's obligation: the result equals plain Floyd-Warshall only where the semiring is absorptive on the input,
+ * x (+) (d_kk (x) x) == x.  Min-plus needs no negative cycles; integer sums must not overflow, so "no edge" is a sentinel such
+ * as max() / 2, not max(); max-plus needs no positive cycles (a DAG); (Min, Max), (Max, Min) are always absorptive, and so is
+ * (And, Max) on 0 / 1.  Outside that, the result is still fully defined by the blocked algorithm, bit for bit:
+ *   block t covers K = [tB, min(n, (t + 1)B)); for t ascending:
+ *   1. for v in K ascending: D[K,K] <- D[K,K] (+) D[K,v] (x) D[v,K] (row v and column v read before the step) -- call it P;
+ *   2. row panel D[K,J] <- D[K,J] (+) P (x) D[K,J]_old for J outside K, column panel D[I,K] <- D[I,K] (+) D[I,K]_old (x) P for
+ *      I outside K: reductions over v in K from the old value as seed;
+ *   3. D <- D (+) Cc (x) Rc over the whole matrix, Cc = D[:,K] and Rc = D[K,:] as steps 1 and 2 left them.
+ *   With n <= B only step 1 runs (one workgroup per graph, on chip: many small graphs in one launch).
+ * A winner is always a strict improvement (Min: s < acc, Max: acc < s, the select of the k-ordered contract), ties keep the
+ * first v.  Min / Max are exact and each map value is rounded once in the element type, so D's bits follow (NaN and signed
+ * zeros aside: step 3 under MM_PATH_AUTO, value-only, runs valu_tile's minNum / maxNum) and are the same from run to run.
+ * witness_dev (int32, D's shape and strides; may be NULL): fully written; the intermediate vertex v of the last strict
+ * improvement of (i, j), or -1 where D[i][j] kept its input value.  Expanding (i, w, j) recursively gives the path.
+ * B: 256 for the value-only form of elements of at most 4 bytes, 128 otherwise; the tuning knob "closure_block" (-1 =
+ * default) takes 64, 128, and 256 where the form allows it -- any other value makes the call return MM_ERR_BAD_ARGUMENT.
+ * Step 3 runs what mm_kernel_name_batched (value-only, accumulating; under MM_PATH_AUTO a D not 16-byte aligned per graph runs
+ * the k-ordered kernel, the same values) or mm_kernel_name_argreduce (witnesses, index_base = tB) names for (n, B, n); the
+ * snapshots live in the library's stream-ordered workspace pool (2 n B elements per graph, the batch chunked to stay near
+ * 256 MiB).  Refused before any device is touched: reductions other than Min / Max (Add, Multiply and And are not idempotent:
+ * no closure) and MM_PATH_SPLIT (MM_ERR_UNSUPPORTED); MM_A_TRANSPOSED, a null d_dev, stride_d < n * n with batch > 1 and a
+ * witness span overlapping D's (MM_ERR_BAD_ARGUMENT).  n or batch 0: MM_OK, nothing done (_launch reports 0 s).
+ * _enqueue: asynchronous on a hipStream_t of the CURRENT device, never synchronises the host; _launch: blocking,
+ * *elapsed_seconds (may be NULL) timed with HIP events. */
+int mm_closure_enqueue(void *hip_stream, const mm_config_t *cfg, void *d_dev, int *witness_dev, unsigned n, unsigned batch,
+                       size_t stride_d);
+int mm_closure_launch(int device, const mm_config_t *cfg, void *d_dev, int *witness_dev, unsigned n, unsigned batch,
+                      size_t stride_d, double *elapsed_seconds);
+/* "closure_onchip" (n <= B) or "closure_blocked"; "unsupported" for a reduction other than Min / Max or MM_PATH_SPLIT;
+ * "invalid" for a bad configuration, MM_A_TRANSPOSED or a closure_block this form does not take.  Pure arithmetic. */
+const char *mm_kernel_name_closure(const mm_config_t *cfg, unsigned n, unsigned batch, int with_witness);
+
 /* One node, `device_count` GPUs, rows of C split into contiguous slabs (device g gets the rows mm_row_slab() names), B
  * replicated, no collective: every outer tile of C is independent (kernel/Compute.cpp:53-60, kernel/Memory.cpp:114-127,
  * 272-286, 367-391).  Host pointers in, host pointer out; copies are outside the timed region exactly as in
@@ -359,6 +398,7 @@ int mm_kernel_info(const mm_config_t *cfg, unsigned size_n, unsigned size_k, uns
  * read-modify-write per part on a per-tile counter, the last ticket gathers: correct by the language's memory model alone, the bits of 0,
  * 0.2-30 % slower (its release fence writes the L2 back; profiles/r06d_*), kept as the cross-check of the shipped flag protocol; 9 stream-K in
  * single ranges with its own fix-up kernel (cross-check, its own bits).
+ * "closure_block": the block size of mm_closure_* (see there).
  * "debug_poison" = 1 fills the scratch that kernels hand partial tiles through, and C itself (pure output), with NaN before
  * every stream-K launch: a read of anything the launch did not write, or a tile nobody finished, then shows in C (tests only).  "md_virtual_devices": see mm_gemm_multi_device.  Any
  * other id is refused: the retired schedules and the work-skipping ablations of the measurement history exist only in the
