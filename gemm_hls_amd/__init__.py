@@ -28,7 +28,7 @@ EXPORTS = ["mm_init", "mm_alloc", "mm_free", "mm_copy_to_device", "mm_copy_to_ho
            "mm_kernel_name_batched", "mm_gemm_accumulate_enqueue", "mm_gemm_accumulate_launch",
            "mm_gemm_batched_accumulate_enqueue", "mm_gemm_batched_accumulate_launch", "mm_gemm_argreduce_enqueue",
            "mm_gemm_argreduce_launch", "mm_kernel_name_argreduce", "mm_closure_enqueue", "mm_closure_launch",
-           "mm_kernel_name_closure"]
+           "mm_kernel_name_closure", "mm_gemm_logsumexp_enqueue", "mm_gemm_logsumexp_launch", "mm_kernel_name_logsumexp"]
 
 
 class MMError(RuntimeError):
@@ -115,6 +115,10 @@ def lib():
         L.mm_closure_launch.argtypes = [i, cfgp, vp, vp, u, u, sz, ctypes.POINTER(ctypes.c_double)]
         L.mm_kernel_name_closure.argtypes = [cfgp, u, u, i]
         L.mm_kernel_name_closure.restype = ctypes.c_char_p
+        L.mm_gemm_logsumexp_enqueue.argtypes = [vp, cfgp, vp, vp, vp, u, u, u, u, sz, sz, sz, i]
+        L.mm_gemm_logsumexp_launch.argtypes = [i, cfgp, vp, vp, vp, u, u, u, u, sz, sz, sz, i, ctypes.POINTER(ctypes.c_double)]
+        L.mm_kernel_name_logsumexp.argtypes = [cfgp, u, u, u, u]
+        L.mm_kernel_name_logsumexp.restype = ctypes.c_char_p
         _lib = L
     return _lib
 
@@ -148,6 +152,10 @@ def kernel_name_argreduce(cfg, n, k, m, batch=1):
 
 def kernel_name_closure(cfg, n, batch=1, with_witness=False):
     return lib().mm_kernel_name_closure(ctypes.byref(cfg), n, batch, int(bool(with_witness))).decode()
+
+
+def kernel_name_logsumexp(cfg, n, k, m, batch=1):
+    return lib().mm_kernel_name_logsumexp(ctypes.byref(cfg), n, k, m, batch).decode()
 
 
 def set_tuning(name, value):
@@ -416,6 +424,53 @@ def addmm_argreduce_(c, c_index, a, b, dtype="float", map_op="Add", reduce_op="M
     cfg = make_config(dtype, map_op, reduce_op, path, transposed_a)
     _argreduce_enqueue(a, b, c, c_index, n, k, m, batch, sa, sb, sc, cfg, index_base, True)
     return c, c_index
+
+
+def matmul_logsumexp(a, b, dtype="float", reduce_op="Max", path=PATH_AUTO, transposed_a=False, out=None):
+    """Log-semiring product on torch's current stream (mm_gemm_logsumexp_enqueue): C = log sum_k exp(A[i,k] + B[k,j]) for
+    reduce_op="Max" (the HMM forward step, the smooth max-plus product), -log sum_k exp(-(A[i,k] + B[k,j])) for "Min" (the
+    soft-min).  dtype: "half", "float" or "double".  a and b as for bmm (2-D, 3-D, or expanded with batch stride 0); the
+    output is (N, M) when both operands are 2-D, else (B, N, M); out: a contiguous tensor of that shape.  Asynchronous."""
+    import torch
+    tdt = torch_dtype(dtype)
+    _device_operands("matmul_logsumexp", tdt, a, b)
+    n, k, m, batch, sa, sb = _argreduce_shapes(a, b, transposed_a)
+    shape = (n, m) if a.dim() == 2 and b.dim() == 2 else (batch, n, m)
+    if out is None:
+        out = torch.empty(shape, dtype=tdt, device=a.device)
+    elif tuple(out.shape) != shape or out.dtype != tdt or out.device != a.device or not out.is_contiguous():
+        raise MMError(f"out must be a contiguous {tdt} tensor of shape {shape} on {a.device}; got "
+                      f"{tuple(out.shape)}, {out.dtype}, {out.device}, contiguous={out.is_contiguous()}")
+    cfg = make_config(dtype, "Add", reduce_op, path, transposed_a)
+    with torch.cuda.device(a.device):
+        stream = torch.cuda.current_stream(a.device).cuda_stream
+        _check(lib().mm_gemm_logsumexp_enqueue(ctypes.c_void_p(stream), ctypes.byref(cfg), a.data_ptr(), b.data_ptr(),
+                                               out.data_ptr(), n, k, m, batch, sa, sb, n * m, 0))
+    return out
+
+
+def addmm_logsumexp_(c, a, b, dtype="float", reduce_op="Max", path=PATH_AUTO, transposed_a=False):
+    """In place C <- log(exp(C) + sum_k exp(A[i,k] + B[k,j])) (Min: the soft-min) on torch's current stream
+    (mm_gemm_logsumexp_enqueue, accumulate): C's value is one more term, so two calls on the halves of K compose to one
+    call on all of it.  2-D operands as for addmm_, 3-D (and broadcast) as for baddbmm_.  Returns c.  Asynchronous."""
+    import torch
+    tdt = torch_dtype(dtype)
+    _device_operands("addmm_logsumexp_", tdt, c, a, b)
+    if c.dim() not in (2, 3):
+        raise MMError("addmm_logsumexp_ takes 2-D or 3-D operands")
+    n, k, m, batch, sa, sb = _argreduce_shapes(a, b, transposed_a)
+    bc, sc = _batched_operand(c, "c", n, m)
+    if batch not in (1, bc or 1):   # a 2-D (or one-matrix) A and B broadcast over every matrix of c
+        raise MMError(f"c has shape {tuple(c.shape)}, expected ({batch}, {n}, {m})")
+    batch = bc or 1
+    if batch > 1 and sc == 0:
+        raise MMError(f"c has batch stride 0: the {batch} outputs would overlap")
+    cfg = make_config(dtype, "Add", reduce_op, path, transposed_a)
+    with torch.cuda.device(a.device):
+        stream = torch.cuda.current_stream(a.device).cuda_stream
+        _check(lib().mm_gemm_logsumexp_enqueue(ctypes.c_void_p(stream), ctypes.byref(cfg), a.data_ptr(), b.data_ptr(),
+                                               c.data_ptr(), n, k, m, batch, sa, sb, sc, 1))
+    return c
 
 
 def closure_(d, d_witness=None, dtype="float", map_op="Add", reduce_op="Min", path=PATH_AUTO):

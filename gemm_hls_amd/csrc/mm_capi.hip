@@ -93,11 +93,11 @@ std::atomic<int> g_tuning[mm::TUNE_COUNT];
 const char *const kTuneName[mm::TUNE_COUNT] = {"f32_variant", "f64_variant", "f16_variant", "i8_variant", "band_rows",
                                                "valu_variant", "split_variant", "f32_splitk", "ablations", "debug_poison", "kxn_prepass_min_m",
                                                "md_virtual_devices", "ordered_variant", "half_contract", "batch_chunk",
-                                               "closure_block"};
+                                               "closure_block", "lse_variant"};
 const char *const kTuneEnv[mm::TUNE_COUNT] = {"MM_F32_VARIANT", "MM_F64_VARIANT", "MM_F16_VARIANT", "MM_I8_VARIANT",
                                               "MM_BAND_ROWS", "MM_VALU_VARIANT", "MM_SPLIT_VARIANT", "MM_F32_SPLITK", "MM_ABLATIONS", "MM_DEBUG_POISON", "MM_KXN_PREPASS_MIN_M",
                                               "MM_MD_VIRTUAL_DEVICES", "MM_ORDERED_VARIANT", "MM_HALF_CONTRACT", "MM_BATCH_CHUNK",
-                                              "MM_CLOSURE_BLOCK"};
+                                              "MM_CLOSURE_BLOCK", "MM_LSE_VARIANT"};
 void tuning_init() {
   for (int i = 0; i < mm::TUNE_COUNT; ++i) {
     const char *e = getenv(kTuneEnv[i]);
@@ -554,6 +554,173 @@ int dispatch_closure(hipStream_t s, const mm_config_t &cfg, void *d, int *w, uns
   return rc;
 }
 
+// ---- log semiring (mm_gemm_logsumexp_*): log sum exp (A + B) -------------------------------------------------------------
+enum LseKernel { LSE_NONE, LSE_EXACT, LSE_HYBRID };
+
+// The kernel by configuration and knob alone (mm_kernel_name_logsumexp).  *bad_knob: lse_variant holds a value it does not take.
+LseKernel lse_kernel_for(const mm_config_t &cfg, bool *bad_knob) {
+  const int v = mm::tuning(mm::TUNE_LSE_VARIANT);
+  *bad_knob = v < -1 || v > 2;
+  if (cfg.dtype != MM_DTYPE_F32 && cfg.dtype != MM_DTYPE_F64 && cfg.dtype != MM_DTYPE_F16) return LSE_NONE;
+  if (cfg.map_op != MM_OP_ADD || (cfg.reduce_op != MM_OP_MIN && cfg.reduce_op != MM_OP_MAX)) return LSE_NONE;
+  if (cfg.path == MM_PATH_SPLIT) return LSE_NONE;
+  if (cfg.path == MM_PATH_ORDERED || v == 0) return LSE_EXACT;
+  return LSE_HYBRID;
+}
+
+// All argument checks of a logsumexp call, before any device is touched.  *ker = LSE_NONE: nothing to launch (an empty
+// batch, or K = 0 when accumulating).
+int check_lse(const mm_config_t *cfg, const mm::Problem &p, LseKernel *ker) {
+  *ker = LSE_NONE;
+  if (!valid_cfg(cfg)) return fail(MM_ERR_BAD_ARGUMENT, "invalid mm_config_t");
+  bool bad_knob;
+  const LseKernel k = lse_kernel_for(*cfg, &bad_knob);
+  if (k == LSE_NONE)
+    return fail(MM_ERR_UNSUPPORTED, "logsumexp serves half, float and double with map Add and reduce Min or Max, under "
+                "MM_PATH_AUTO or MM_PATH_ORDERED (got dtype %d, map %d, reduce %d, path %d)", (int)cfg->dtype,
+                (int)cfg->map_op, (int)cfg->reduce_op, (int)cfg->path);
+  if (bad_knob)
+    return fail(MM_ERR_BAD_ARGUMENT, "lse_variant %d is not one of -1, 0, 1, 2", mm::tuning(mm::TUNE_LSE_VARIANT));
+  if (p.k == 0 && !p.seed) return fail(MM_ERR_BAD_ARGUMENT, "size_k must be positive");
+  if (p.batch == 0 || p.n == 0 || p.m == 0) return MM_OK;   // nothing to write
+  if (!p.c || (p.k && (!p.a || !p.b))) return fail(MM_ERR_BAD_ARGUMENT, "null matrix pointer");   // (K = 0: A, B unread)
+  if (p.batch > 1 && p.stride_c < (size_t)p.n * p.m)
+    return fail(MM_ERR_BAD_ARGUMENT, "stride_c %zu < N * M = %zu: the outputs of the batch would overlap", p.stride_c,
+                (size_t)p.n * p.m);
+  const size_t es = mm_dtype_size(cfg->dtype);
+  const size_t c_bytes = batch_span((size_t)p.n * p.m, p.stride_c, p.batch, es);
+  if (spans_overlap(p.c, c_bytes, p.a, batch_span((size_t)p.n * p.k, p.stride_a, p.batch, es)) ||
+      spans_overlap(p.c, c_bytes, p.b, batch_span((size_t)p.k * p.m, p.stride_b, p.batch, es)))
+    return fail(MM_ERR_BAD_ARGUMENT, "c overlaps a or b (bases %p, %p, %p)", p.a, p.b, p.c);
+  if (p.k == 0) return MM_OK;   // accumulating over no k: C keeps its value
+  *ker = k;
+  return MM_OK;
+}
+
+int lse_status(int e, const mm_config_t &cfg, const char *what) {
+  if (e == mm::kErrNotSupported)
+    return fail(MM_ERR_UNSUPPORTED, "logsumexp configuration (dtype %d, map %d, reduce %d) is not compiled into this library",
+                (int)cfg.dtype, (int)cfg.map_op, (int)cfg.reduce_op);
+  return e ? hip_fail((hipError_t)e, what) : MM_OK;
+}
+
+// The exact kernel over the batch, in launches of at most batch_chunk() elements; flags (per element: the 64 x 64 tiles of
+// one element) restrict it to the flagged tiles.
+int lse_exact_chunks(hipStream_t s, const mm_config_t &cfg, const mm::Problem &p, const int *flags) {
+  const size_t es = mm_dtype_size(cfg.dtype);
+  const size_t tiles = (size_t)((p.n + 63) / 64) * ((p.m + 63) / 64);
+  const unsigned chunk = batch_chunk(p);
+  for (unsigned e0 = 0; e0 < p.batch; e0 += chunk) {
+    mm::Problem q = p;
+    q.batch = std::min(chunk, p.batch - e0);
+    q.a = (const char *)p.a + (size_t)e0 * p.stride_a * es;
+    q.b = (const char *)p.b + (size_t)e0 * p.stride_b * es;
+    q.c = (char *)p.c + (size_t)e0 * p.stride_c * es;
+    if (int rc = lse_status(mm::launch_lse_exact(s, cfg, q, flags ? flags + e0 * tiles : nullptr), cfg, "logsumexp kernel launch"))
+      return rc;
+  }
+  return MM_OK;
+}
+
+// Workspace of one chunk of the hybrid stays near this; an element that alone needs more runs alone.
+constexpr size_t kLseWorkspaceCap = 256ull << 20;
+
+// The hybrid, never synchronising the host: per chunk of the batch, prepass (row maxima of A, column maxima of B, EA and EB
+// zero-padded to multiples of 64 in f32 / f64), S = EA @ EB on the matrix cores, the epilogue (C and one flag per tile) and
+// the exact kernel over the flagged tiles.  A broadcast operand is transformed once.  The product's kernel is resolved once on
+// the whole batch, so an element's bits do not depend on the chunk it falls in.
+int dispatch_lse_hybrid(hipStream_t s, const mm_config_t &cfg, const mm::Problem &p) {
+  const bool dbl = cfg.dtype == MM_DTYPE_F64;
+  const size_t fs = dbl ? 8 : 4, es = mm_dtype_size(cfg.dtype);
+  const auto up = [](size_t x) { return (x + 63) & ~(size_t)63; };
+  const unsigned np = (unsigned)up(p.n), kp = (unsigned)up(p.k), mp = (unsigned)up(p.m);
+  const size_t tiles = (size_t)(np / 64) * (mp / 64);
+  const bool a_shared = p.batch > 1 && p.stride_a == 0, b_shared = p.batch > 1 && p.stride_b == 0;
+  const size_t ea = up((size_t)np * kp), eb = up((size_t)kp * mp), sz = up((size_t)np * mp), ra = up(np), rb = up(mp);
+  const size_t per = (a_shared ? 0 : ea + ra) + (b_shared ? 0 : eb + rb) + sz;   // F elements per element of the batch
+  const size_t fixed = (a_shared ? ea + ra : 0) + (b_shared ? eb + rb : 0);
+  unsigned chunk = (unsigned)std::min<size_t>(p.batch, std::max<size_t>(1, kLseWorkspaceCap / ((per + tiles) * fs)));
+  chunk = std::min(chunk, batch_chunk(p));
+  const size_t fl = up(tiles * chunk);                                          // int32 flags, one per tile
+  const size_t bytes = (fixed + per * chunk) * fs + fl * sizeof(int);
+  int dev = 0;
+  MM_HIP(hipGetDevice(&dev));
+  hipMemPool_t pool = nullptr;
+  if (int e = mm::workspace_pool(dev, &pool)) return hip_fail((hipError_t)e, "workspace pool");
+  char *ws = nullptr;
+  MM_HIP(hipMallocFromPoolAsync((void **)&ws, bytes, pool, s));
+  int rc = MM_OK;
+  if (mm::tuning(mm::TUNE_DEBUG_POISON) == 1) {   // every F of the workspace NaN: a read of an unwritten element shows up
+    const hipError_t e = hipMemsetAsync(ws, 0xFF, bytes, s);
+    if (e != hipSuccess) rc = hip_fail(e, "hipMemsetAsync (logsumexp workspace)");
+  }
+  // layout: [EA][EB][S][ra][rb] in F, then the flags
+  char *const pea = ws, *const peb = pea + (a_shared ? ea : ea * chunk) * fs, *const ps = peb + (b_shared ? eb : eb * chunk) * fs;
+  char *const pra = ps + sz * chunk * fs, *const prb = pra + (a_shared ? ra : ra * chunk) * fs;
+  int *const flags = (int *)(prb + (b_shared ? rb : rb * chunk) * fs);
+  const size_t sea = a_shared ? 0 : ea, seb = b_shared ? 0 : eb, sra = a_shared ? 0 : ra, srb = b_shared ? 0 : rb;
+  mm::LseOperand opa{}, opb{};
+  opa.rows = p.n; opa.k = p.k; opa.rows_p = np; opa.k_p = kp; opa.x_kmajor = p.a_transposed; opa.out_kmajor = false;
+  opa.e = pea; opa.r = pra; opa.stride_x = p.stride_a; opa.stride_e = ea; opa.stride_r = ra;
+  opb.rows = p.m; opb.k = p.k; opb.rows_p = mp; opb.k_p = kp; opb.x_kmajor = true; opb.out_kmajor = true;
+  opb.e = peb; opb.r = prb; opb.stride_x = p.stride_b; opb.stride_e = eb; opb.stride_r = rb;
+  if (rc == MM_OK && a_shared) {
+    opa.x = p.a; opa.count = 1;
+    rc = lse_status(mm::launch_lse_prepass(s, cfg, opa), cfg, "logsumexp prepass launch");
+  }
+  if (rc == MM_OK && b_shared) {
+    opb.x = p.b; opb.count = 1;
+    rc = lse_status(mm::launch_lse_prepass(s, cfg, opb), cfg, "logsumexp prepass launch");
+  }
+  // S = EA @ EB: (Multiply, Add) in F on the matrix cores; one element: the single launch's kernel, else the batched one
+  // resolved on the whole batch
+  const mm_config_t gcfg{dbl ? MM_DTYPE_F64 : MM_DTYPE_F32, MM_OP_MULTIPLY, MM_OP_ADD, MM_PATH_AUTO, MM_A_ROW_MAJOR};
+  mm::Problem whole = batched_problem(&gcfg, pea, peb, ps, np, kp, mp, p.batch, sea, seb, sz);
+  const int gk = dbl ? mm::mfma_f64_batched_resolve(whole) : mm::mfma_f32_batched_resolve(whole, f32_variant());
+  if (rc == MM_OK && p.batch > 1 && gk < 0) rc = fail(MM_ERR_UNSUPPORTED, "no batched matrix-core kernel for the logsumexp product");
+  (void)hipGetLastError();   // a stale error of the application's own calls must not be reported as this launch's
+  for (unsigned e0 = 0; e0 < p.batch && rc == MM_OK; e0 += chunk) {
+    const unsigned ce = std::min(chunk, p.batch - e0);
+    if (!a_shared) {
+      opa.x = (const char *)p.a + (size_t)e0 * p.stride_a * es; opa.count = ce;
+      if ((rc = lse_status(mm::launch_lse_prepass(s, cfg, opa), cfg, "logsumexp prepass launch"))) break;
+    }
+    if (!b_shared) {
+      opb.x = (const char *)p.b + (size_t)e0 * p.stride_b * es; opb.count = ce;
+      if ((rc = lse_status(mm::launch_lse_prepass(s, cfg, opb), cfg, "logsumexp prepass launch"))) break;
+    }
+    mm::Problem g = batched_problem(&gcfg, pea, peb, ps, np, kp, mp, ce, sea, seb, sz);
+    if (p.batch == 1) {
+      if ((rc = dispatch(s, gcfg, g))) break;
+    } else {
+      const int e = dbl ? mm::launch_mfma_f64_batched(s, g, gk) : mm::launch_mfma_f32_batched(s, g, gk);
+      if ((rc = lse_status(e, gcfg, "logsumexp product launch"))) break;
+    }
+    mm::LseEpilogue ep{};
+    ep.s = ps; ep.ra = pra; ep.rb = prb; ep.c = (char *)p.c + (size_t)e0 * p.stride_c * es; ep.flags = flags;
+    ep.n = p.n; ep.m = p.m; ep.m_p = mp; ep.batch = ce;
+    ep.stride_s = sz; ep.stride_ra = sra; ep.stride_rb = srb; ep.stride_c = p.stride_c;
+    ep.seed = p.seed; ep.force = mm::tuning(mm::TUNE_LSE_VARIANT) == 2;
+    if ((rc = lse_status(mm::launch_lse_epilogue(s, cfg, ep), cfg, "logsumexp epilogue launch"))) break;
+    mm::Problem q = p;   // the fallback: the exact kernel over the flagged tiles of this chunk
+    q.batch = ce;
+    q.a = (const char *)p.a + (size_t)e0 * p.stride_a * es;
+    q.b = (const char *)p.b + (size_t)e0 * p.stride_b * es;
+    q.c = ep.c;
+    if ((rc = lse_status(mm::launch_lse_exact(s, cfg, q, flags), cfg, "logsumexp fallback launch"))) break;
+  }
+  const hipError_t f = hipFreeAsync(ws, s);
+  if (rc == MM_OK && f != hipSuccess) rc = hip_fail(f, "hipFreeAsync (logsumexp workspace)");
+  return rc;
+}
+
+int dispatch_lse(hipStream_t s, const mm_config_t &cfg, const mm::Problem &p, LseKernel ker) {
+  (void)hipGetLastError();   // a stale error of the application's own calls must not be reported as this launch's
+  mm::Problem q = p;
+  if (q.batch == 1) q.stride_a = q.stride_b = q.stride_c = 0;
+  return ker == LSE_HYBRID ? dispatch_lse_hybrid(s, cfg, q) : lse_exact_chunks(s, cfg, q, nullptr);
+}
+
 // hipEvent_t with a destructor: no exit path of the timed launch can leak one
 struct Event {
   hipEvent_t e = nullptr;
@@ -902,6 +1069,48 @@ int mm_gemm_argreduce_launch(int device, const mm_config_t *cfg, const void *a, 
   MM_HIP(hipEventCreate(&stop.e));
   MM_HIP(hipEventRecord(start.e, nullptr));
   rc = dispatch_argreduce(nullptr, *cfg, p, c_index, index_base, ker);
+  if (rc != MM_OK) return rc;
+  MM_HIP(hipEventRecord(stop.e, nullptr));
+  MM_HIP(hipEventSynchronize(stop.e));
+  if (elapsed_seconds) {
+    float ms = 0.f;
+    MM_HIP(hipEventElapsedTime(&ms, start.e, stop.e));
+    *elapsed_seconds = 1e-3 * (double)ms;
+  }
+  return MM_OK;
+}
+
+int mm_gemm_logsumexp_enqueue(void *hip_stream, const mm_config_t *cfg, const void *a, const void *b, void *c, unsigned n,
+                              unsigned k, unsigned m, unsigned batch, size_t stride_a, size_t stride_b, size_t stride_c,
+                              int accumulate) {
+  mm::Problem p = batched_problem(cfg, a, b, c, n, k, m, batch, stride_a, stride_b, stride_c);
+  p.seed = accumulate != 0;
+  LseKernel ker;
+  int rc = check_lse(cfg, p, &ker);
+  if (rc || ker == LSE_NONE) return rc;   // (LSE_NONE: an empty batch or K = 0 accumulating, nothing to do)
+  if ((rc = ensure_init())) return rc;
+  return dispatch_lse((hipStream_t)hip_stream, *cfg, p, ker);
+}
+
+int mm_gemm_logsumexp_launch(int device, const mm_config_t *cfg, const void *a, const void *b, void *c, unsigned n,
+                             unsigned k, unsigned m, unsigned batch, size_t stride_a, size_t stride_b, size_t stride_c,
+                             int accumulate, double *elapsed_seconds) {
+  mm::Problem p = batched_problem(cfg, a, b, c, n, k, m, batch, stride_a, stride_b, stride_c);
+  p.seed = accumulate != 0;
+  LseKernel ker;
+  int rc = check_lse(cfg, p, &ker);
+  if (rc) return rc;
+  if (ker == LSE_NONE) {   // nothing to launch or time
+    if (elapsed_seconds) *elapsed_seconds = 0.0;
+    return MM_OK;
+  }
+  if ((rc = check_device(device))) return rc;
+  MM_HIP(hipSetDevice(device));
+  Event start, stop;
+  MM_HIP(hipEventCreate(&start.e));
+  MM_HIP(hipEventCreate(&stop.e));
+  MM_HIP(hipEventRecord(start.e, nullptr));
+  rc = dispatch_lse(nullptr, *cfg, p, ker);
   if (rc != MM_OK) return rc;
   MM_HIP(hipEventRecord(stop.e, nullptr));
   MM_HIP(hipEventSynchronize(stop.e));
@@ -1308,6 +1517,16 @@ const char *mm_kernel_name_argreduce(const mm_config_t *cfg, unsigned n, unsigne
     case AR_PLAIN: return "argreduce";
     default: return "unsupported";
   }
+}
+
+const char *mm_kernel_name_logsumexp(const mm_config_t *cfg, unsigned n, unsigned k, unsigned m, unsigned batch) {
+  (void)n, (void)k, (void)m, (void)batch;   // the choice is the configuration's and the knob's, not the shape's
+  if (!valid_cfg(cfg)) return "invalid";
+  bool bad_knob;
+  const LseKernel ker = lse_kernel_for(*cfg, &bad_knob);   // the choice check_lse makes
+  if (ker == LSE_NONE) return "unsupported";
+  if (bad_knob) return "invalid";
+  return ker == LSE_HYBRID ? "lse_hybrid" : "lse_exact";
 }
 
 const char *mm_kernel_name_closure(const mm_config_t *cfg, unsigned n, unsigned batch, int with_witness) {

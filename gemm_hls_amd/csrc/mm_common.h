@@ -149,6 +149,31 @@ struct ClosureStep {
   int w_fresh;
 };
 int launch_closure(hipStream_t s, const mm_config_t &cfg, const ClosureStep &st);
+// Log-semiring product (mm_gemm_logsumexp_*, mm_lse_fp.hip).  launch_lse_exact: the exact kernel over the p.batch elements of
+// p (p.seed: C's input is one more term); flags != null: the hybrid's fallback, tile t of element e runs only where
+// flags[e * tiles + t] != 0 (64 x 64 tiles).  The hybrid's prepass transforms `count` elements of one operand: r = the
+// per-line maxima (NaN-propagating; Min: of the negated operand) and e = exp(X - r), zero-padded to rows_p x k_p
+// (out_kmajor: k_p x rows_p), in f32 (f64 for double).  X is rows x k row-major, or k x rows when x_kmajor.
+struct LseOperand {
+  const void *x;
+  size_t stride_x;
+  unsigned count, rows, k, rows_p, k_p;
+  bool x_kmajor, out_kmajor;
+  void *e, *r;
+  size_t stride_e, stride_r;
+};
+// The epilogue: C from S (n_p x m_p per element, row stride m_p), ra and rb; one flag per 64 x 64 tile of each element.
+struct LseEpilogue {
+  const void *s, *ra, *rb;
+  void *c;
+  int *flags;
+  unsigned n, m, m_p, batch;
+  size_t stride_s, stride_ra, stride_rb, stride_c;
+  bool seed, force;
+};
+int launch_lse_exact(hipStream_t s, const mm_config_t &cfg, const Problem &p, const int *flags);
+int launch_lse_prepass(hipStream_t s, const mm_config_t &cfg, const LseOperand &op);
+int launch_lse_epilogue(hipStream_t s, const mm_config_t &cfg, const LseEpilogue &ep);
 int launch_mfma_f32(hipStream_t s, const Problem &p, int variant);
 int launch_mfma_f64(hipStream_t s, const Problem &p);
 int launch_mfma_f16(hipStream_t s, const Problem &p);
@@ -225,6 +250,8 @@ enum Tunable {
                            //                 k-ordered tile kernel instead of the matrix cores' f32 accumulation; 0 / "wide" / unset: f32
   TUNE_BATCH_CHUNK,        // MM_BATCH_CHUNK  mm_gemm_batched_*: at most this many elements per launch (tests); -1: only the grid limits
   TUNE_CLOSURE_BLOCK,      // MM_CLOSURE_BLOCK  block size B of mm_closure_* (64, 128, or 256 where the form allows it); -1: the default
+  TUNE_LSE_VARIANT,        // MM_LSE_VARIANT  mm_gemm_logsumexp_*: 0 exact kernel only, 1 hybrid, 2 hybrid with every tile sent to
+                           //                 the fallback (the cross-check); -1: the default (hybrid)
   TUNE_COUNT
 };
 int tuning(Tunable t);  // mm_capi.hip

@@ -265,6 +265,48 @@ int mm_gemm_argreduce_launch(int device, const mm_config_t *cfg, const void *a_d
 const char *mm_kernel_name_argreduce(const mm_config_t *cfg, unsigned size_n, unsigned size_k, unsigned size_m,
                                      unsigned batch);
 
+/* Log semiring: the smooth form of the (Add, Max) product -- HMM forward algorithm, CRF partition functions, CTC,
+ * inside-outside; with Min, the soft-min of soft-DTW and smoothed shortest paths.  For output (e, i, j) of a strided batch
+ * the terms are s_k = A[e,i,k] + B[e,k,j], k < K, each one rounded sum in the computation type (f32 for half and float, f64
+ * for double); when accumulating, C's input value is one more term.  cfg->reduce_op picks
+ *     MM_OP_MAX:  C = log sum_k exp(s_k)          MM_OP_MIN:  C = -log sum_k exp(-s_k)
+ * Special values follow torch.logsumexp over the terms, exactly.  Max: a NaN term (a NaN operand in a pair, or +inf + -inf)
+ * gives NaN; otherwise a +inf term gives +inf; otherwise all terms -inf give -inf.  Min is the mirror image.  A finite result
+ * beyond the output type's range (half) becomes +-inf.  Terms of magnitude beyond 2^127 / log2(e) (float and half) or
+ * 2^1023 / log2(e) (double) lie outside the contract: their exponent shift is clamped and the result may overflow.
+ * Finite outputs: with ra_i = max_k A[i,k], rb_j = max_k B[k,j] (Min: of the negated operands), u = 2^-24 (half, float) or
+ * 2^-53 (double) and C* the exact value,
+ *     |C - C*| <= u (4 (|ra_i| + |rb_j|) + 4 |C*| + 2 K + 512)        (+ 2^-11 |C*| for half: the rounding on store)
+ * on both kernels (derivation: DESIGN.md 3.9).  A call gives the same bits on every run, and an element's bits depend on
+ * neither its position in the batch nor the other elements.
+ * Kernels (mm_kernel_name_logsumexp):
+ *   "lse_exact"  a register-tiled VALU kernel: every output keeps a running (max, scaled sum) pair; exp2 on v_exp_f32 (f64:
+ *                one library exp2 per term, slow).  MM_PATH_ORDERED, and the knob "lse_variant" = 0.
+ *   "lse_hybrid" MM_PATH_AUTO: a prepass takes ra, rb and EA = exp(A - ra), EB = exp(B - rb) (zero-padded to multiples of 64,
+ *                f32 / f64) into the library's stream-ordered workspace; S = EA @ EB runs on the fp32 / fp64 matrix cores;
+ *                an epilogue writes C = ra_i + rb_j + log S and flags every 64 x 64 tile holding an output with S < 2^-64
+ *                (f64: 2^-512), a non-finite shift or result; the exact kernel then recomputes the flagged tiles only.  No
+ *                host synchronisation, no atomics; the batch is chunked to keep the workspace near 256 MiB.
+ * Knob "lse_variant" (MM_LSE_VARIANT): -1 default, 0 exact kernel only, 1 hybrid, 2 hybrid with every tile sent to the
+ * fallback (the cross-check); any other value makes the calls return MM_ERR_BAD_ARGUMENT.
+ * Arguments as for mm_gemm_argreduce_* without the index: strides in elements, 0 = broadcast, stride_c >= N * M when
+ * batch > 1, any element-aligned pointer or stride.  Refused before any device is touched: a dtype other than half, float
+ * and double, a map other than Add, a reduction other than Min / Max, MM_PATH_SPLIT (MM_ERR_UNSUPPORTED); a bad knob value,
+ * a null pointer, overlapping outputs and C's span overlapping A's or B's (MM_ERR_BAD_ARGUMENT).  batch, N or M 0: MM_OK;
+ * K = 0: MM_ERR_BAD_ARGUMENT in the plain form, MM_OK (C unchanged) when accumulating.
+ * _enqueue: asynchronous on a hipStream_t of the CURRENT device, never synchronises the host; _launch: blocking,
+ * *elapsed_seconds (may be NULL) timed with HIP events. */
+int mm_gemm_logsumexp_enqueue(void *hip_stream, const mm_config_t *cfg, const void *a_dev, const void *b_dev, void *c_dev,
+                              unsigned size_n, unsigned size_k, unsigned size_m, unsigned batch,
+                              size_t stride_a, size_t stride_b, size_t stride_c, int accumulate);
+int mm_gemm_logsumexp_launch(int device, const mm_config_t *cfg, const void *a_dev, const void *b_dev, void *c_dev,
+                             unsigned size_n, unsigned size_k, unsigned size_m, unsigned batch,
+                             size_t stride_a, size_t stride_b, size_t stride_c, int accumulate, double *elapsed_seconds);
+/* "lse_hybrid", "lse_exact"; "unsupported" for a configuration the calls refuse with MM_ERR_UNSUPPORTED; "invalid" for a bad
+ * configuration or knob value.  Pure arithmetic. */
+const char *mm_kernel_name_logsumexp(const mm_config_t *cfg, unsigned size_n, unsigned size_k, unsigned size_m,
+                                     unsigned batch);
+
 /* Closure: all-pairs shortest / widest / longest paths and transitive closure -- blocked Floyd-Warshall, in place.
  * D is n x n, row-major; graph e of the batch starts at d_dev + e * stride_d (elements; stride_d >= n * n when batch > 1).
  * The call runs the recurrence D[i][j] <- D[i][j] (+) D[i][v] (x) D[v][j] over every v, with Reduce = cfg->reduce_op in
@@ -398,7 +440,7 @@ int mm_kernel_info(const mm_config_t *cfg, unsigned size_n, unsigned size_k, uns
  * read-modify-write per part on a per-tile counter, the last ticket gathers: correct by the language's memory model alone, the bits of 0,
  * 0.2-30 % slower (its release fence writes the L2 back; profiles/r06d_*), kept as the cross-check of the shipped flag protocol; 9 stream-K in
  * single ranges with its own fix-up kernel (cross-check, its own bits).
- * "closure_block": the block size of mm_closure_* (see there).
+ * "closure_block": the block size of mm_closure_* (see there).  "lse_variant": the kernels of mm_gemm_logsumexp_* (see there).
  * "debug_poison" = 1 fills the scratch that kernels hand partial tiles through, and C itself (pure output), with NaN before
  * every stream-K launch: a read of anything the launch did not write, or a tile nobody finished, then shows in C (tests only).  "md_virtual_devices": see mm_gemm_multi_device.  Any
  * other id is refused: the retired schedules and the work-skipping ablations of the measurement history exist only in the
