@@ -128,6 +128,20 @@ def _check(rc):
         raise MMError(f"mm_gemm status {rc}: {lib().mm_last_error().decode()}")
 
 
+def _enqueue(device, fn, *args):
+    """fn(stream, *args) on torch's current stream of `device`, with `device` current: the C ABI's enqueue forms launch on
+    the current device."""
+    import torch
+    with torch.cuda.device(device):
+        _check(fn(ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream), *args))
+
+
+def _check_out(x, name, shape, dtype, device):
+    if tuple(x.shape) != shape or x.dtype != dtype or x.device != device or not x.is_contiguous():
+        raise MMError(f"{name} must be a contiguous {dtype} tensor of shape {shape} on {device}; got "
+                      f"{tuple(x.shape)}, {x.dtype}, {x.device}, contiguous={x.is_contiguous()}")
+
+
 def make_config(dtype="float", map_op="Multiply", reduce_op="Add", path=PATH_AUTO, transposed_a=False):
     return Config(DTYPES[dtype], OPS[map_op], OPS[reduce_op], path, int(transposed_a))
 
@@ -212,15 +226,10 @@ def matmul(a, b, dtype="float", map_op="Multiply", reduce_op="Add", path=PATH_AU
         raise MMError(f"inner dimensions differ: A {tuple(a.shape)}{' (K x N)' if transposed_a else ''}, B {tuple(b.shape)}")
     if out is None:
         out = torch.empty((n, m), dtype=tdt, device=a.device)
-    elif (tuple(out.shape) != (n, m) or out.dtype != tdt or out.device != a.device or not out.is_contiguous()):
-        raise MMError(f"out must be a contiguous {tdt} tensor of shape {(n, m)} on {a.device}; got "
-                      f"{tuple(out.shape)}, {out.dtype}, {out.device}, contiguous={out.is_contiguous()}")
+    else:
+        _check_out(out, "out", (n, m), tdt, a.device)
     cfg = make_config(dtype, map_op, reduce_op, path, transposed_a)
-    # mm_gemm_enqueue launches on the CURRENT device: make that the operands' device
-    with torch.cuda.device(a.device):
-        stream = torch.cuda.current_stream(a.device).cuda_stream
-        _check(lib().mm_gemm_enqueue(ctypes.c_void_p(stream), ctypes.byref(cfg), a.data_ptr(), b.data_ptr(),
-                                     out.data_ptr(), n, k, m))
+    _enqueue(a.device, lib().mm_gemm_enqueue, ctypes.byref(cfg), a.data_ptr(), b.data_ptr(), out.data_ptr(), n, k, m)
     return out
 
 
@@ -241,6 +250,34 @@ def _batched_operand(x, name, rows, cols):
     return x.shape[0], (0 if x.shape[0] == 1 else x.stride(0))
 
 
+def _bmm_shapes(what, a, b, transposed_a):
+    """(n, k, m, batch, stride_a, stride_b) of bmm-style operands: 2-D, 3-D, or expanded with batch stride 0."""
+    if a.dim() not in (2, 3) or b.dim() not in (2, 3):
+        raise MMError(f"{what} takes 2-D or 3-D operands")
+    k, m = b.shape[-2], b.shape[-1]
+    n = a.shape[-1] if transposed_a else a.shape[-2]
+    if (a.shape[-2] if transposed_a else a.shape[-1]) != k:
+        raise MMError(f"inner dimensions differ: A {tuple(a.shape)}{' (K x N)' if transposed_a else ''}, B {tuple(b.shape)}")
+    ba, sa = _batched_operand(a, "a", *((k, n) if transposed_a else (n, k)))
+    bb, sb = _batched_operand(b, "b", k, m)
+    batches = {x for x in (ba, bb) if x is not None and x != 1}
+    if len(batches) > 1:
+        raise MMError(f"batch sizes differ: {ba} and {bb}")
+    return n, k, m, (batches.pop() if batches else 1), sa, sb
+
+
+def _inplace_batch(c, n, m, batch):
+    """(batch, stride_c) of an in-place C over bmm-style operands of `batch`: C's own batch, over which a one-matrix A and
+    B broadcast."""
+    bc, sc = _batched_operand(c, "c", n, m)
+    if batch not in (1, bc or 1):
+        raise MMError(f"c has shape {tuple(c.shape)}, expected ({batch}, {n}, {m})")
+    batch = bc or 1
+    if batch > 1 and sc == 0:
+        raise MMError(f"c has batch stride 0: the {batch} outputs would overlap")
+    return batch, sc
+
+
 def bmm(a, b, dtype="float", map_op="Multiply", reduce_op="Add", path=PATH_AUTO, transposed_a=False, out=None):
     """Strided-batched C[e] = A[e] (map, reduce) B[e] on torch's current stream (mm_gemm_batched_enqueue).
     a: (B, N, K) -- or (B, K, N) with transposed_a -- b: (B, K, M); either may be 2-D or expanded with batch stride 0
@@ -254,28 +291,14 @@ def bmm(a, b, dtype="float", map_op="Multiply", reduce_op="Add", path=PATH_AUTO,
     tdt = torch_dtype(dtype)
     if a.dtype != tdt or b.dtype != tdt:
         raise MMError(f"operand dtypes {a.dtype}, {b.dtype} do not match Data_t={dtype} ({tdt})")
-    if a.dim() not in (2, 3) or b.dim() not in (2, 3):
-        raise MMError("bmm takes 2-D or 3-D operands")
-    k, m = b.shape[-2], b.shape[-1]
-    n = a.shape[-1] if transposed_a else a.shape[-2]
-    if (a.shape[-2] if transposed_a else a.shape[-1]) != k:
-        raise MMError(f"inner dimensions differ: A {tuple(a.shape)}{' (K x N)' if transposed_a else ''}, B {tuple(b.shape)}")
-    ba, sa = _batched_operand(a, "a", *((k, n) if transposed_a else (n, k)))
-    bb, sb = _batched_operand(b, "b", k, m)
-    batches = {x for x in (ba, bb) if x is not None and x != 1}
-    if len(batches) > 1:
-        raise MMError(f"batch sizes differ: {ba} and {bb}")
-    batch = batches.pop() if batches else 1
+    n, k, m, batch, sa, sb = _bmm_shapes("bmm", a, b, transposed_a)
     if out is None:
         out = torch.empty((batch, n, m), dtype=tdt, device=a.device)
-    elif (tuple(out.shape) != (batch, n, m) or out.dtype != tdt or out.device != a.device or not out.is_contiguous()):
-        raise MMError(f"out must be a contiguous {tdt} tensor of shape {(batch, n, m)} on {a.device}; got "
-                      f"{tuple(out.shape)}, {out.dtype}, {out.device}, contiguous={out.is_contiguous()}")
+    else:
+        _check_out(out, "out", (batch, n, m), tdt, a.device)
     cfg = make_config(dtype, map_op, reduce_op, path, transposed_a)
-    with torch.cuda.device(a.device):
-        stream = torch.cuda.current_stream(a.device).cuda_stream
-        _check(lib().mm_gemm_batched_enqueue(ctypes.c_void_p(stream), ctypes.byref(cfg), a.data_ptr(), b.data_ptr(),
-                                             out.data_ptr(), n, k, m, batch, sa, sb, n * m))
+    _enqueue(a.device, lib().mm_gemm_batched_enqueue, ctypes.byref(cfg), a.data_ptr(), b.data_ptr(), out.data_ptr(),
+             n, k, m, batch, sa, sb, n * m)
     return out
 
 
@@ -306,12 +329,8 @@ def addmm_(c, a, b, dtype="float", map_op="Multiply", reduce_op="Add", path=PATH
         raise MMError(f"inner dimensions differ: A {tuple(a.shape)}{' (K x N)' if transposed_a else ''}, B {tuple(b.shape)}")
     if tuple(c.shape) != (n, m):
         raise MMError(f"c has shape {tuple(c.shape)}, expected {(n, m)}")
-    import torch
     cfg = make_config(dtype, map_op, reduce_op, path, transposed_a)
-    with torch.cuda.device(a.device):
-        stream = torch.cuda.current_stream(a.device).cuda_stream
-        _check(lib().mm_gemm_accumulate_enqueue(ctypes.c_void_p(stream), ctypes.byref(cfg), a.data_ptr(), b.data_ptr(),
-                                                c.data_ptr(), n, k, m))
+    _enqueue(a.device, lib().mm_gemm_accumulate_enqueue, ctypes.byref(cfg), a.data_ptr(), b.data_ptr(), c.data_ptr(), n, k, m)
     return c
 
 
@@ -320,56 +339,16 @@ def baddbmm_(c, a, b, dtype="float", map_op="Multiply", reduce_op="Add", path=PA
     (mm_gemm_batched_accumulate_enqueue) -- torch.baddbmm_ for (Multiply, Add).  a and b as for bmm (2-D, 3-D, or expanded
     with batch stride 0); c: (B, N, M) with dense row-major matrices and a batch stride of at least N * M (2-D when B is 1),
     not overlapping A or B.  Returns c.  Asynchronous, like any torch op."""
-    import torch
     tdt = torch_dtype(dtype)
     _device_operands("baddbmm_", tdt, c, a, b)
-    if a.dim() not in (2, 3) or b.dim() not in (2, 3) or c.dim() not in (2, 3):
+    if c.dim() not in (2, 3):
         raise MMError("baddbmm_ takes 2-D or 3-D operands")
-    k, m = b.shape[-2], b.shape[-1]
-    n = a.shape[-1] if transposed_a else a.shape[-2]
-    if (a.shape[-2] if transposed_a else a.shape[-1]) != k:
-        raise MMError(f"inner dimensions differ: A {tuple(a.shape)}{' (K x N)' if transposed_a else ''}, B {tuple(b.shape)}")
-    ba, sa = _batched_operand(a, "a", *((k, n) if transposed_a else (n, k)))
-    bb, sb = _batched_operand(b, "b", k, m)
-    bc, sc = _batched_operand(c, "c", n, m)
-    batches = {x for x in (ba, bb) if x is not None and x != 1}
-    if len(batches) > 1:
-        raise MMError(f"batch sizes differ: {ba} and {bb}")
-    batch = batches.pop() if batches else (bc or 1)
-    if (bc or 1) != batch or (batch > 1 and sc == 0):
-        raise MMError(f"c has shape {tuple(c.shape)} (batch stride {c.stride(0) if c.dim() == 3 else None}), expected "
-                      f"{batch} distinct ({n}, {m}) matrices")
+    n, k, m, batch, sa, sb = _bmm_shapes("baddbmm_", a, b, transposed_a)
+    batch, sc = _inplace_batch(c, n, m, batch)
     cfg = make_config(dtype, map_op, reduce_op, path, transposed_a)
-    with torch.cuda.device(a.device):
-        stream = torch.cuda.current_stream(a.device).cuda_stream
-        _check(lib().mm_gemm_batched_accumulate_enqueue(ctypes.c_void_p(stream), ctypes.byref(cfg), a.data_ptr(),
-                                                        b.data_ptr(), c.data_ptr(), n, k, m, batch, sa, sb, sc))
+    _enqueue(a.device, lib().mm_gemm_batched_accumulate_enqueue, ctypes.byref(cfg), a.data_ptr(), b.data_ptr(), c.data_ptr(),
+             n, k, m, batch, sa, sb, sc)
     return c
-
-
-def _argreduce_shapes(a, b, transposed_a):
-    """(n, k, m, batch, stride_a, stride_b) of bmm-style operands: 2-D, 3-D, or expanded with batch stride 0."""
-    if a.dim() not in (2, 3) or b.dim() not in (2, 3):
-        raise MMError("argreduce takes 2-D or 3-D operands")
-    k, m = b.shape[-2], b.shape[-1]
-    n = a.shape[-1] if transposed_a else a.shape[-2]
-    if (a.shape[-2] if transposed_a else a.shape[-1]) != k:
-        raise MMError(f"inner dimensions differ: A {tuple(a.shape)}{' (K x N)' if transposed_a else ''}, B {tuple(b.shape)}")
-    ba, sa = _batched_operand(a, "a", *((k, n) if transposed_a else (n, k)))
-    bb, sb = _batched_operand(b, "b", k, m)
-    batches = {x for x in (ba, bb) if x is not None and x != 1}
-    if len(batches) > 1:
-        raise MMError(f"batch sizes differ: {ba} and {bb}")
-    return n, k, m, (batches.pop() if batches else 1), sa, sb
-
-
-def _argreduce_enqueue(a, b, c, c_index, n, k, m, batch, sa, sb, sc, cfg, index_base, accumulate):
-    import torch
-    with torch.cuda.device(a.device):
-        stream = torch.cuda.current_stream(a.device).cuda_stream
-        _check(lib().mm_gemm_argreduce_enqueue(ctypes.c_void_p(stream), ctypes.byref(cfg), a.data_ptr(), b.data_ptr(),
-                                               c.data_ptr(), c_index.data_ptr(), n, k, m, batch, sa, sb, sc,
-                                               int(index_base), int(accumulate)))
 
 
 def matmul_argreduce(a, b, dtype="float", map_op="Add", reduce_op="Min", path=PATH_AUTO, transposed_a=False, index_base=0,
@@ -382,18 +361,17 @@ def matmul_argreduce(a, b, dtype="float", map_op="Add", reduce_op="Min", path=PA
     import torch
     tdt = torch_dtype(dtype)
     _device_operands("matmul_argreduce", tdt, a, b)
-    n, k, m, batch, sa, sb = _argreduce_shapes(a, b, transposed_a)
+    n, k, m, batch, sa, sb = _bmm_shapes("matmul_argreduce", a, b, transposed_a)
     shape = (n, m) if a.dim() == 2 and b.dim() == 2 else (batch, n, m)
     if out is None:
         out = torch.empty(shape, dtype=tdt, device=a.device)
     if out_index is None:
         out_index = torch.empty(shape, dtype=torch.int32, device=a.device)
-    for x, name, want in ((out, "out", tdt), (out_index, "out_index", torch.int32)):
-        if tuple(x.shape) != shape or x.dtype != want or x.device != a.device or not x.is_contiguous():
-            raise MMError(f"{name} must be a contiguous {want} tensor of shape {shape} on {a.device}; got "
-                          f"{tuple(x.shape)}, {x.dtype}, {x.device}, contiguous={x.is_contiguous()}")
+    _check_out(out, "out", shape, tdt, a.device)
+    _check_out(out_index, "out_index", shape, torch.int32, a.device)
     cfg = make_config(dtype, map_op, reduce_op, path, transposed_a)
-    _argreduce_enqueue(a, b, out, out_index, n, k, m, batch, sa, sb, n * m, cfg, index_base, False)
+    _enqueue(a.device, lib().mm_gemm_argreduce_enqueue, ctypes.byref(cfg), a.data_ptr(), b.data_ptr(), out.data_ptr(),
+             out_index.data_ptr(), n, k, m, batch, sa, sb, n * m, int(index_base), 0)
     return out, out_index
 
 
@@ -414,15 +392,11 @@ def addmm_argreduce_(c, c_index, a, b, dtype="float", map_op="Add", reduce_op="M
     if tuple(c_index.shape) != tuple(c.shape) or c_index.stride() != c.stride():
         raise MMError(f"c_index must have c's shape and strides: {tuple(c.shape)} {c.stride()}, got "
                       f"{tuple(c_index.shape)} {c_index.stride()}")
-    n, k, m, batch, sa, sb = _argreduce_shapes(a, b, transposed_a)
-    bc, sc = _batched_operand(c, "c", n, m)
-    if batch not in (1, bc or 1):   # a 2-D (or one-matrix) A and B broadcast over every matrix of c
-        raise MMError(f"c has shape {tuple(c.shape)}, expected ({batch}, {n}, {m})")
-    batch = bc or 1
-    if batch > 1 and sc == 0:
-        raise MMError(f"c has batch stride 0: the {batch} outputs would overlap")
+    n, k, m, batch, sa, sb = _bmm_shapes("addmm_argreduce_", a, b, transposed_a)
+    batch, sc = _inplace_batch(c, n, m, batch)
     cfg = make_config(dtype, map_op, reduce_op, path, transposed_a)
-    _argreduce_enqueue(a, b, c, c_index, n, k, m, batch, sa, sb, sc, cfg, index_base, True)
+    _enqueue(a.device, lib().mm_gemm_argreduce_enqueue, ctypes.byref(cfg), a.data_ptr(), b.data_ptr(), c.data_ptr(),
+             c_index.data_ptr(), n, k, m, batch, sa, sb, sc, int(index_base), 1)
     return c, c_index
 
 
@@ -434,18 +408,15 @@ def matmul_logsumexp(a, b, dtype="float", reduce_op="Max", path=PATH_AUTO, trans
     import torch
     tdt = torch_dtype(dtype)
     _device_operands("matmul_logsumexp", tdt, a, b)
-    n, k, m, batch, sa, sb = _argreduce_shapes(a, b, transposed_a)
+    n, k, m, batch, sa, sb = _bmm_shapes("matmul_logsumexp", a, b, transposed_a)
     shape = (n, m) if a.dim() == 2 and b.dim() == 2 else (batch, n, m)
     if out is None:
         out = torch.empty(shape, dtype=tdt, device=a.device)
-    elif tuple(out.shape) != shape or out.dtype != tdt or out.device != a.device or not out.is_contiguous():
-        raise MMError(f"out must be a contiguous {tdt} tensor of shape {shape} on {a.device}; got "
-                      f"{tuple(out.shape)}, {out.dtype}, {out.device}, contiguous={out.is_contiguous()}")
+    else:
+        _check_out(out, "out", shape, tdt, a.device)
     cfg = make_config(dtype, "Add", reduce_op, path, transposed_a)
-    with torch.cuda.device(a.device):
-        stream = torch.cuda.current_stream(a.device).cuda_stream
-        _check(lib().mm_gemm_logsumexp_enqueue(ctypes.c_void_p(stream), ctypes.byref(cfg), a.data_ptr(), b.data_ptr(),
-                                               out.data_ptr(), n, k, m, batch, sa, sb, n * m, 0))
+    _enqueue(a.device, lib().mm_gemm_logsumexp_enqueue, ctypes.byref(cfg), a.data_ptr(), b.data_ptr(), out.data_ptr(),
+             n, k, m, batch, sa, sb, n * m, 0)
     return out
 
 
@@ -453,23 +424,15 @@ def addmm_logsumexp_(c, a, b, dtype="float", reduce_op="Max", path=PATH_AUTO, tr
     """In place C <- log(exp(C) + sum_k exp(A[i,k] + B[k,j])) (Min: the soft-min) on torch's current stream
     (mm_gemm_logsumexp_enqueue, accumulate): C's value is one more term, so two calls on the halves of K compose to one
     call on all of it.  2-D operands as for addmm_, 3-D (and broadcast) as for baddbmm_.  Returns c.  Asynchronous."""
-    import torch
     tdt = torch_dtype(dtype)
     _device_operands("addmm_logsumexp_", tdt, c, a, b)
     if c.dim() not in (2, 3):
         raise MMError("addmm_logsumexp_ takes 2-D or 3-D operands")
-    n, k, m, batch, sa, sb = _argreduce_shapes(a, b, transposed_a)
-    bc, sc = _batched_operand(c, "c", n, m)
-    if batch not in (1, bc or 1):   # a 2-D (or one-matrix) A and B broadcast over every matrix of c
-        raise MMError(f"c has shape {tuple(c.shape)}, expected ({batch}, {n}, {m})")
-    batch = bc or 1
-    if batch > 1 and sc == 0:
-        raise MMError(f"c has batch stride 0: the {batch} outputs would overlap")
+    n, k, m, batch, sa, sb = _bmm_shapes("addmm_logsumexp_", a, b, transposed_a)
+    batch, sc = _inplace_batch(c, n, m, batch)
     cfg = make_config(dtype, "Add", reduce_op, path, transposed_a)
-    with torch.cuda.device(a.device):
-        stream = torch.cuda.current_stream(a.device).cuda_stream
-        _check(lib().mm_gemm_logsumexp_enqueue(ctypes.c_void_p(stream), ctypes.byref(cfg), a.data_ptr(), b.data_ptr(),
-                                               c.data_ptr(), n, k, m, batch, sa, sb, sc, 1))
+    _enqueue(a.device, lib().mm_gemm_logsumexp_enqueue, ctypes.byref(cfg), a.data_ptr(), b.data_ptr(), c.data_ptr(),
+             n, k, m, batch, sa, sb, sc, 1)
     return c
 
 
@@ -497,9 +460,7 @@ def closure_(d, d_witness=None, dtype="float", map_op="Add", reduce_op="Min", pa
                           f"contiguous={d_witness.is_contiguous()}")
         w = d_witness.data_ptr()
     cfg = make_config(dtype, map_op, reduce_op, path)
-    with torch.cuda.device(d.device):
-        stream = torch.cuda.current_stream(d.device).cuda_stream
-        _check(lib().mm_closure_enqueue(ctypes.c_void_p(stream), ctypes.byref(cfg), d.data_ptr(), w, n, batch, n * n))
+    _enqueue(d.device, lib().mm_closure_enqueue, ctypes.byref(cfg), d.data_ptr(), w, n, batch, n * n)
     return d
 
 

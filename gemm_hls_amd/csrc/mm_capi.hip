@@ -170,6 +170,19 @@ bool aligned16(const mm::Problem &p) {
   return (((uintptr_t)p.a | (uintptr_t)p.b | (uintptr_t)p.c) & 15u) == 0;
 }
 
+// A launcher's status as this library's: kErrNotSupported (the configuration's kernel is not compiled in) is
+// MM_ERR_UNSUPPORTED, any other non-zero value the HIP error of `what`.  `family` ("", "argreduce ", ...) and, when
+// non-zero, `block` name the kernel in the message.
+int launch_status(int e, const mm_config_t &cfg, const char *family, const char *what, unsigned block = 0) {
+  if (e == mm::kErrNotSupported) {
+    char b[32] = "";
+    if (block) snprintf(b, sizeof(b), ", block %u", block);
+    return fail(MM_ERR_UNSUPPORTED, "%sconfiguration (dtype %d, map %d, reduce %d%s) is not compiled into this library", family,
+                (int)cfg.dtype, (int)cfg.map_op, (int)cfg.reduce_op, b);
+  }
+  return e ? hip_fail((hipError_t)e, what) : MM_OK;
+}
+
 int dispatch(hipStream_t s, const mm_config_t &cfg, const mm::Problem &p) {
   if (p.n == 0 || p.m == 0) return MM_OK;  // nothing to write
   Family fam = choose(cfg, p);
@@ -201,11 +214,7 @@ int dispatch(hipStream_t s, const mm_config_t &cfg, const mm::Problem &p) {
       break;
     default: e = mm::launch_ordered(s, cfg, p); break;
   }
-  if (e == mm::kErrNotSupported)
-    return fail(MM_ERR_UNSUPPORTED, "configuration (dtype %d, map %d, reduce %d) is not compiled into this library",
-                (int)cfg.dtype, (int)cfg.map_op, (int)cfg.reduce_op);
-  if (e != 0) return hip_fail((hipError_t)e, "kernel launch");
-  return MM_OK;
+  return launch_status(e, cfg, "", "kernel launch");
 }
 
 int check_problem(const mm_config_t *cfg, const void *a, const void *b, void *c, unsigned n, unsigned k, unsigned m) {
@@ -240,6 +249,54 @@ bool batch_aligned16(const mm::Problem &p, size_t es) {
   return aligned16(p) && (strides & 15u) == 0;
 }
 
+// ---- the rules every batched call shares --------------------------------------------------------------------------------
+bool empty_batch(const mm::Problem &p) { return p.batch == 0 || p.n == 0 || p.m == 0; }   // nothing to write
+
+int check_stride_c(const mm::Problem &p) {
+  if (p.batch > 1 && p.stride_c < (size_t)p.n * p.m)
+    return fail(MM_ERR_BAD_ARGUMENT, "stride_c %zu < N * M = %zu: the outputs of the batch would overlap", p.stride_c,
+                (size_t)p.n * p.m);
+  return MM_OK;
+}
+
+// Bytes an operand of the batch can touch: [base, base + ((batch - 1) * stride + extent) * es), extent = its elements.
+size_t batch_span(size_t extent, size_t stride, unsigned batch, size_t es) {
+  return extent ? ((size_t)(batch - 1) * stride + extent) * es : 0;
+}
+bool spans_overlap(const void *x, size_t xbytes, const void *y, size_t ybytes) {
+  const uintptr_t x0 = (uintptr_t)x, y0 = (uintptr_t)y;
+  return xbytes && ybytes && x0 < y0 + ybytes && y0 < x0 + xbytes;
+}
+
+// Whether C overlaps A or B, or (given) the int32 index I, laid out as C, overlaps A, B or C -- over the bytes the whole
+// batch can touch.  A conservative test: the kernels read A and B while other workgroups already write C and I.
+bool outputs_overlap(const mm::Problem &p, size_t es, const int *index = nullptr) {
+  const size_t nm = (size_t)p.n * p.m;
+  const size_t a_bytes = batch_span((size_t)p.n * p.k, p.stride_a, p.batch, es);
+  const size_t b_bytes = batch_span((size_t)p.k * p.m, p.stride_b, p.batch, es);
+  const size_t c_bytes = batch_span(nm, p.stride_c, p.batch, es), i_bytes = batch_span(nm, p.stride_c, p.batch, sizeof(int));
+  return spans_overlap(p.c, c_bytes, p.a, a_bytes) || spans_overlap(p.c, c_bytes, p.b, b_bytes) ||
+         (index && (spans_overlap(index, i_bytes, p.a, a_bytes) || spans_overlap(index, i_bytes, p.b, b_bytes) ||
+                    spans_overlap(index, i_bytes, p.c, c_bytes)));
+}
+
+// Elements [e0, e0 + count) of the batch.
+mm::Problem batch_slice(const mm::Problem &p, unsigned e0, unsigned count, size_t es) {
+  mm::Problem q = p;
+  q.batch = count;
+  q.a = (const char *)p.a + (size_t)e0 * p.stride_a * es;
+  q.b = (const char *)p.b + (size_t)e0 * p.stride_b * es;
+  q.c = (char *)p.c + (size_t)e0 * p.stride_c * es;
+  return q;
+}
+
+// fn(slice, e0) over consecutive slices of at most `chunk` elements; stops at the first non-zero status.
+template <class F> int for_each_chunk(const mm::Problem &p, size_t es, unsigned chunk, F &&fn) {
+  for (unsigned e0 = 0; e0 < p.batch; e0 += chunk)
+    if (int rc = fn(batch_slice(p, e0, std::min(chunk, p.batch - e0), es), e0)) return rc;
+  return MM_OK;
+}
+
 // All argument checks of a batched call, before any device is touched.  *fam: the family that will run (FAM_NONE: an empty
 // batch, a no-op).
 int check_batched(const mm_config_t *cfg, const mm::Problem &p, Family *fam) {
@@ -247,11 +304,9 @@ int check_batched(const mm_config_t *cfg, const mm::Problem &p, Family *fam) {
   if (p.k == 0) return fail(MM_ERR_BAD_ARGUMENT, "size_k must be positive");
   if (cfg->path == MM_PATH_SPLIT) return fail(MM_ERR_UNSUPPORTED, "MM_PATH_SPLIT has no batched form (it needs workspace)");
   *fam = FAM_NONE;
-  if (p.batch == 0 || p.n == 0 || p.m == 0) return MM_OK;   // nothing to write
+  if (empty_batch(p)) return MM_OK;
   if (!p.a || !p.b || !p.c) return fail(MM_ERR_BAD_ARGUMENT, "null matrix pointer");
-  if (p.batch > 1 && p.stride_c < (size_t)p.n * p.m)
-    return fail(MM_ERR_BAD_ARGUMENT, "stride_c %zu < N * M = %zu: the outputs of the batch would overlap", p.stride_c,
-                (size_t)p.n * p.m);
+  if (int rc = check_stride_c(p)) return rc;
   Family f = choose_batched(*cfg, p);
   if (f == FAM_NONE) return fail(MM_ERR_UNSUPPORTED, "no batched kernel serves this configuration");
   const bool aligned = batch_aligned16(p, mm_dtype_size(cfg->dtype));
@@ -277,20 +332,13 @@ unsigned batch_chunk(const mm::Problem &p) {
 // Launches the batch as consecutive launches of at most batch_chunk() elements on `s`.  The family and the fp32 geometry
 // are decided once, on the whole batch, so that an element's kernel does not depend on how the batch was chunked.
 int dispatch_batched(hipStream_t s, const mm_config_t &cfg, const mm::Problem &p, Family fam) {
-  if (p.batch == 0 || p.n == 0 || p.m == 0) return MM_OK;
-  const size_t es = mm_dtype_size(cfg.dtype);
+  if (empty_batch(p)) return MM_OK;
   const int kernel = fam == FAM_MFMA_F32 ? mm::mfma_f32_batched_resolve(p, f32_variant())
                    : fam == FAM_MFMA_F64 ? mm::mfma_f64_batched_resolve(p)
                    : fam == FAM_MFMA_F16 ? mm::mfma_f16_batched_resolve(p)
                    : fam == FAM_MFMA_I8 ? mm::mfma_i8_batched_resolve(p) : -1;
-  const unsigned chunk = batch_chunk(p);
   (void)hipGetLastError();   // a stale error of the application's own calls must not be reported as this launch's
-  for (unsigned e0 = 0; e0 < p.batch; e0 += chunk) {
-    mm::Problem q = p;
-    q.batch = std::min(chunk, p.batch - e0);
-    q.a = (const char *)p.a + (size_t)e0 * p.stride_a * es;
-    q.b = (const char *)p.b + (size_t)e0 * p.stride_b * es;
-    q.c = (char *)p.c + (size_t)e0 * p.stride_c * es;
+  return for_each_chunk(p, mm_dtype_size(cfg.dtype), batch_chunk(p), [&](const mm::Problem &q, unsigned) {
     int e;
     switch (fam) {
       case FAM_MFMA_F32: e = mm::launch_mfma_f32_batched(s, q, kernel); break;
@@ -308,12 +356,8 @@ int dispatch_batched(hipStream_t s, const mm_config_t &cfg, const mm::Problem &p
         break;
       default: e = mm::launch_ordered_batched(s, cfg, q); break;
     }
-    if (e == mm::kErrNotSupported)
-      return fail(MM_ERR_UNSUPPORTED, "configuration (dtype %d, map %d, reduce %d) is not compiled into this library",
-                  (int)cfg.dtype, (int)cfg.map_op, (int)cfg.reduce_op);
-    if (e != 0) return hip_fail((hipError_t)e, "batched kernel launch");
-  }
-  return MM_OK;
+    return launch_status(e, cfg, "", "batched kernel launch");
+  });
 }
 
 mm::Problem batched_problem(const mm_config_t *cfg, const void *a, const void *b, void *c, unsigned n, unsigned k,
@@ -327,18 +371,8 @@ mm::Problem batched_problem(const mm_config_t *cfg, const void *a, const void *b
 }
 
 // ---- accumulate (mm_gemm_*accumulate_*): C <- C (+) (A (x) B) -------------------------------------------------------
-// Bytes an operand of the batch can touch: [base, base + ((batch - 1) * stride + extent) * es), extent = its elements.
-size_t batch_span(size_t extent, size_t stride, unsigned batch, size_t es) {
-  return extent ? ((size_t)(batch - 1) * stride + extent) * es : 0;
-}
-bool spans_overlap(const void *x, size_t xbytes, const void *y, size_t ybytes) {
-  const uintptr_t x0 = (uintptr_t)x, y0 = (uintptr_t)y;
-  return xbytes && ybytes && x0 < y0 + ybytes && y0 < x0 + xbytes;
-}
-
-// The batched call's checks (check_batched), K = 0 accepted, and C refused where its span overlaps A's or B's (a
-// conservative test: the kernels read A and B while other workgroups already write C).  *fam = FAM_NONE: nothing to
-// launch (an empty batch, or K = 0: C keeps its value).
+// The batched call's checks (check_batched), K = 0 accepted, and C refused where it overlaps A or B.  *fam = FAM_NONE:
+// nothing to launch (an empty batch, or K = 0: C keeps its value).
 int check_accumulate(const mm_config_t *cfg, const mm::Problem &p, Family *fam) {
   *fam = FAM_NONE;
   if (!valid_cfg(cfg)) return fail(MM_ERR_BAD_ARGUMENT, "invalid mm_config_t");
@@ -352,10 +386,7 @@ int check_accumulate(const mm_config_t *cfg, const mm::Problem &p, Family *fam) 
     if (int rc = check_batched(cfg, q, &f)) return rc;
     if (f == FAM_NONE) return MM_OK;
   }
-  const size_t es = mm_dtype_size(cfg->dtype);
-  const size_t c_bytes = batch_span((size_t)p.n * p.m, p.stride_c, p.batch, es);
-  if (spans_overlap(p.c, c_bytes, p.a, batch_span((size_t)p.n * p.k, p.stride_a, p.batch, es)) ||
-      spans_overlap(p.c, c_bytes, p.b, batch_span((size_t)p.k * p.m, p.stride_b, p.batch, es))) {
+  if (outputs_overlap(p, mm_dtype_size(cfg->dtype))) {
     *fam = FAM_NONE;
     return fail(MM_ERR_BAD_ARGUMENT, "c overlaps a or b (bases %p, %p, %p): an accumulating call updates C in place and reads "
                 "A and B meanwhile; pass a copy", p.a, p.b, p.c);
@@ -387,18 +418,11 @@ int check_argreduce(const mm_config_t *cfg, const mm::Problem &p, const int *ind
   if (index_base < 0) return fail(MM_ERR_BAD_ARGUMENT, "index_base %d is negative", index_base);
   if (p.k > 0 && (long long)index_base + p.k - 1 > (long long)INT32_MAX)
     return fail(MM_ERR_BAD_ARGUMENT, "index_base %d + K - 1 (K = %u) does not fit an int32 index", index_base, p.k);
-  if (p.batch == 0 || p.n == 0 || p.m == 0) return MM_OK;   // nothing to write
+  if (empty_batch(p)) return MM_OK;
   if (!p.a || !p.b || !p.c || !index) return fail(MM_ERR_BAD_ARGUMENT, "null matrix or index pointer");
-  if (p.batch > 1 && p.stride_c < (size_t)p.n * p.m)
-    return fail(MM_ERR_BAD_ARGUMENT, "stride_c %zu < N * M = %zu: the outputs of the batch would overlap", p.stride_c,
-                (size_t)p.n * p.m);
-  const size_t es = mm_dtype_size(cfg->dtype), nm = (size_t)p.n * p.m;
-  const size_t a_bytes = batch_span((size_t)p.n * p.k, p.stride_a, p.batch, es);
-  const size_t b_bytes = batch_span((size_t)p.k * p.m, p.stride_b, p.batch, es);
-  const size_t c_bytes = batch_span(nm, p.stride_c, p.batch, es), i_bytes = batch_span(nm, p.stride_c, p.batch, sizeof(int));
-  if (spans_overlap(p.c, c_bytes, p.a, a_bytes) || spans_overlap(p.c, c_bytes, p.b, b_bytes) ||
-      spans_overlap(index, i_bytes, p.a, a_bytes) || spans_overlap(index, i_bytes, p.b, b_bytes) ||
-      spans_overlap(index, i_bytes, p.c, c_bytes))
+  if (int rc = check_stride_c(p)) return rc;
+  const size_t es = mm_dtype_size(cfg->dtype);
+  if (outputs_overlap(p, es, index))
     return fail(MM_ERR_BAD_ARGUMENT, "c or c_index overlaps a, b or each other (bases %p, %p, %p, %p)", p.a, p.b, p.c,
                 (const void *)index);
   if (p.k == 0) return MM_OK;   // accumulating over no k: C and I keep their values
@@ -413,22 +437,11 @@ int check_argreduce(const mm_config_t *cfg, const mm::Problem &p, const int *ind
 // Launches the batch as consecutive launches of at most batch_chunk() elements on `s`, C and I advancing together.
 int dispatch_argreduce(hipStream_t s, const mm_config_t &cfg, const mm::Problem &p, int *index, int index_base,
                        ArKernel ker) {
-  const size_t es = mm_dtype_size(cfg.dtype);
-  const unsigned chunk = batch_chunk(p);
   (void)hipGetLastError();   // a stale error of the application's own calls must not be reported as this launch's
-  for (unsigned e0 = 0; e0 < p.batch; e0 += chunk) {
-    mm::Problem q = p;
-    q.batch = std::min(chunk, p.batch - e0);
-    q.a = (const char *)p.a + (size_t)e0 * p.stride_a * es;
-    q.b = (const char *)p.b + (size_t)e0 * p.stride_b * es;
-    q.c = (char *)p.c + (size_t)e0 * p.stride_c * es;
-    const int e = mm::launch_argreduce(s, cfg, q, index + (size_t)e0 * p.stride_c, index_base, ker == AR_TILE);
-    if (e == mm::kErrNotSupported)
-      return fail(MM_ERR_UNSUPPORTED, "argreduce configuration (dtype %d, map %d, reduce %d) is not compiled into this library",
-                  (int)cfg.dtype, (int)cfg.map_op, (int)cfg.reduce_op);
-    if (e != 0) return hip_fail((hipError_t)e, "argreduce kernel launch");
-  }
-  return MM_OK;
+  return for_each_chunk(p, mm_dtype_size(cfg.dtype), batch_chunk(p), [&](const mm::Problem &q, unsigned e0) {
+    return launch_status(mm::launch_argreduce(s, cfg, q, index + (size_t)e0 * p.stride_c, index_base, ker == AR_TILE), cfg,
+                         "argreduce ", "argreduce kernel launch");
+  });
 }
 
 // ---- closure (mm_closure_*): blocked Floyd-Warshall in place -------------------------------------------------------
@@ -488,11 +501,8 @@ int closure_rank_update(hipStream_t s, const mm_config_t &cfg, mm::Problem q, in
 }
 
 int closure_step(hipStream_t s, const mm_config_t &cfg, const mm::ClosureStep &st) {
-  const int e = mm::launch_closure(s, cfg, st);
-  if (e == mm::kErrNotSupported)
-    return fail(MM_ERR_UNSUPPORTED, "closure configuration (dtype %d, map %d, reduce %d, block %u) is not compiled into this "
-                "library", (int)cfg.dtype, (int)cfg.map_op, (int)cfg.reduce_op, st.bt);
-  return e ? hip_fail((hipError_t)e, st.panels ? "closure panel kernel launch" : "closure diagonal kernel launch") : MM_OK;
+  return launch_status(mm::launch_closure(s, cfg, st), cfg, "closure ",
+                       st.panels ? "closure panel kernel launch" : "closure diagonal kernel launch", st.bt);
 }
 
 // The closure on stream `s`, never synchronising the host.  n <= B: one on-chip launch per chunk of graphs.  Otherwise, per
@@ -582,44 +592,24 @@ int check_lse(const mm_config_t *cfg, const mm::Problem &p, LseKernel *ker) {
   if (bad_knob)
     return fail(MM_ERR_BAD_ARGUMENT, "lse_variant %d is not one of -1, 0, 1, 2", mm::tuning(mm::TUNE_LSE_VARIANT));
   if (p.k == 0 && !p.seed) return fail(MM_ERR_BAD_ARGUMENT, "size_k must be positive");
-  if (p.batch == 0 || p.n == 0 || p.m == 0) return MM_OK;   // nothing to write
+  if (empty_batch(p)) return MM_OK;
   if (!p.c || (p.k && (!p.a || !p.b))) return fail(MM_ERR_BAD_ARGUMENT, "null matrix pointer");   // (K = 0: A, B unread)
-  if (p.batch > 1 && p.stride_c < (size_t)p.n * p.m)
-    return fail(MM_ERR_BAD_ARGUMENT, "stride_c %zu < N * M = %zu: the outputs of the batch would overlap", p.stride_c,
-                (size_t)p.n * p.m);
-  const size_t es = mm_dtype_size(cfg->dtype);
-  const size_t c_bytes = batch_span((size_t)p.n * p.m, p.stride_c, p.batch, es);
-  if (spans_overlap(p.c, c_bytes, p.a, batch_span((size_t)p.n * p.k, p.stride_a, p.batch, es)) ||
-      spans_overlap(p.c, c_bytes, p.b, batch_span((size_t)p.k * p.m, p.stride_b, p.batch, es)))
+  if (int rc = check_stride_c(p)) return rc;
+  if (outputs_overlap(p, mm_dtype_size(cfg->dtype)))
     return fail(MM_ERR_BAD_ARGUMENT, "c overlaps a or b (bases %p, %p, %p)", p.a, p.b, p.c);
   if (p.k == 0) return MM_OK;   // accumulating over no k: C keeps its value
   *ker = k;
   return MM_OK;
 }
 
-int lse_status(int e, const mm_config_t &cfg, const char *what) {
-  if (e == mm::kErrNotSupported)
-    return fail(MM_ERR_UNSUPPORTED, "logsumexp configuration (dtype %d, map %d, reduce %d) is not compiled into this library",
-                (int)cfg.dtype, (int)cfg.map_op, (int)cfg.reduce_op);
-  return e ? hip_fail((hipError_t)e, what) : MM_OK;
-}
-
 // The exact kernel over the batch, in launches of at most batch_chunk() elements; flags (per element: the 64 x 64 tiles of
 // one element) restrict it to the flagged tiles.
 int lse_exact_chunks(hipStream_t s, const mm_config_t &cfg, const mm::Problem &p, const int *flags) {
-  const size_t es = mm_dtype_size(cfg.dtype);
   const size_t tiles = (size_t)((p.n + 63) / 64) * ((p.m + 63) / 64);
-  const unsigned chunk = batch_chunk(p);
-  for (unsigned e0 = 0; e0 < p.batch; e0 += chunk) {
-    mm::Problem q = p;
-    q.batch = std::min(chunk, p.batch - e0);
-    q.a = (const char *)p.a + (size_t)e0 * p.stride_a * es;
-    q.b = (const char *)p.b + (size_t)e0 * p.stride_b * es;
-    q.c = (char *)p.c + (size_t)e0 * p.stride_c * es;
-    if (int rc = lse_status(mm::launch_lse_exact(s, cfg, q, flags ? flags + e0 * tiles : nullptr), cfg, "logsumexp kernel launch"))
-      return rc;
-  }
-  return MM_OK;
+  return for_each_chunk(p, mm_dtype_size(cfg.dtype), batch_chunk(p), [&](const mm::Problem &q, unsigned e0) {
+    return launch_status(mm::launch_lse_exact(s, cfg, q, flags ? flags + e0 * tiles : nullptr), cfg, "logsumexp ",
+                         "logsumexp kernel launch");
+  });
 }
 
 // Workspace of one chunk of the hybrid stays near this; an element that alone needs more runs alone.
@@ -666,11 +656,11 @@ int dispatch_lse_hybrid(hipStream_t s, const mm_config_t &cfg, const mm::Problem
   opb.e = peb; opb.r = prb; opb.stride_x = p.stride_b; opb.stride_e = eb; opb.stride_r = rb;
   if (rc == MM_OK && a_shared) {
     opa.x = p.a; opa.count = 1;
-    rc = lse_status(mm::launch_lse_prepass(s, cfg, opa), cfg, "logsumexp prepass launch");
+    rc = launch_status(mm::launch_lse_prepass(s, cfg, opa), cfg, "logsumexp ", "logsumexp prepass launch");
   }
   if (rc == MM_OK && b_shared) {
     opb.x = p.b; opb.count = 1;
-    rc = lse_status(mm::launch_lse_prepass(s, cfg, opb), cfg, "logsumexp prepass launch");
+    rc = launch_status(mm::launch_lse_prepass(s, cfg, opb), cfg, "logsumexp ", "logsumexp prepass launch");
   }
   // S = EA @ EB: (Multiply, Add) in F on the matrix cores; one element: the single launch's kernel, else the batched one
   // resolved on the whole batch
@@ -678,36 +668,32 @@ int dispatch_lse_hybrid(hipStream_t s, const mm_config_t &cfg, const mm::Problem
   mm::Problem whole = batched_problem(&gcfg, pea, peb, ps, np, kp, mp, p.batch, sea, seb, sz);
   const int gk = dbl ? mm::mfma_f64_batched_resolve(whole) : mm::mfma_f32_batched_resolve(whole, f32_variant());
   if (rc == MM_OK && p.batch > 1 && gk < 0) rc = fail(MM_ERR_UNSUPPORTED, "no batched matrix-core kernel for the logsumexp product");
-  (void)hipGetLastError();   // a stale error of the application's own calls must not be reported as this launch's
   for (unsigned e0 = 0; e0 < p.batch && rc == MM_OK; e0 += chunk) {
     const unsigned ce = std::min(chunk, p.batch - e0);
+    const mm::Problem q = batch_slice(p, e0, ce, es);   // this chunk's elements
     if (!a_shared) {
-      opa.x = (const char *)p.a + (size_t)e0 * p.stride_a * es; opa.count = ce;
-      if ((rc = lse_status(mm::launch_lse_prepass(s, cfg, opa), cfg, "logsumexp prepass launch"))) break;
+      opa.x = q.a; opa.count = ce;
+      if ((rc = launch_status(mm::launch_lse_prepass(s, cfg, opa), cfg, "logsumexp ", "logsumexp prepass launch"))) break;
     }
     if (!b_shared) {
-      opb.x = (const char *)p.b + (size_t)e0 * p.stride_b * es; opb.count = ce;
-      if ((rc = lse_status(mm::launch_lse_prepass(s, cfg, opb), cfg, "logsumexp prepass launch"))) break;
+      opb.x = q.b; opb.count = ce;
+      if ((rc = launch_status(mm::launch_lse_prepass(s, cfg, opb), cfg, "logsumexp ", "logsumexp prepass launch"))) break;
     }
     mm::Problem g = batched_problem(&gcfg, pea, peb, ps, np, kp, mp, ce, sea, seb, sz);
     if (p.batch == 1) {
       if ((rc = dispatch(s, gcfg, g))) break;
     } else {
       const int e = dbl ? mm::launch_mfma_f64_batched(s, g, gk) : mm::launch_mfma_f32_batched(s, g, gk);
-      if ((rc = lse_status(e, gcfg, "logsumexp product launch"))) break;
+      if ((rc = launch_status(e, gcfg, "logsumexp ", "logsumexp product launch"))) break;
     }
     mm::LseEpilogue ep{};
-    ep.s = ps; ep.ra = pra; ep.rb = prb; ep.c = (char *)p.c + (size_t)e0 * p.stride_c * es; ep.flags = flags;
+    ep.s = ps; ep.ra = pra; ep.rb = prb; ep.c = q.c; ep.flags = flags;
     ep.n = p.n; ep.m = p.m; ep.m_p = mp; ep.batch = ce;
     ep.stride_s = sz; ep.stride_ra = sra; ep.stride_rb = srb; ep.stride_c = p.stride_c;
     ep.seed = p.seed; ep.force = mm::tuning(mm::TUNE_LSE_VARIANT) == 2;
-    if ((rc = lse_status(mm::launch_lse_epilogue(s, cfg, ep), cfg, "logsumexp epilogue launch"))) break;
-    mm::Problem q = p;   // the fallback: the exact kernel over the flagged tiles of this chunk
-    q.batch = ce;
-    q.a = (const char *)p.a + (size_t)e0 * p.stride_a * es;
-    q.b = (const char *)p.b + (size_t)e0 * p.stride_b * es;
-    q.c = ep.c;
-    if ((rc = lse_status(mm::launch_lse_exact(s, cfg, q, flags), cfg, "logsumexp fallback launch"))) break;
+    if ((rc = launch_status(mm::launch_lse_epilogue(s, cfg, ep), cfg, "logsumexp ", "logsumexp epilogue launch"))) break;
+    // the fallback: the exact kernel over the flagged tiles of this chunk
+    if ((rc = launch_status(mm::launch_lse_exact(s, cfg, q, flags), cfg, "logsumexp ", "logsumexp fallback launch"))) break;
   }
   const hipError_t f = hipFreeAsync(ws, s);
   if (rc == MM_OK && f != hipSuccess) rc = hip_fail(f, "hipFreeAsync (logsumexp workspace)");
@@ -721,11 +707,54 @@ int dispatch_lse(hipStream_t s, const mm_config_t &cfg, const mm::Problem &p, Ls
   return ker == LSE_HYBRID ? dispatch_lse_hybrid(s, cfg, q) : lse_exact_chunks(s, cfg, q, nullptr);
 }
 
+// The kernel of a family that is one kernel whatever the shape (the matrix-core families name theirs by shape)
+const char *family_name(Family f) {
+  switch (f) {
+    case FAM_HALF_WIDE: return "ordered_wide_f16";
+    case FAM_VALU_TILE: return "valu_tile";
+    case FAM_ORDERED_TILE: return "ordered_tile";   // k ascending, one accumulator, unfused: Naive's bits on 128 x 128 register tiles
+    case FAM_NONE: return "unsupported";
+    default: return "ordered";
+  }
+}
+
 // hipEvent_t with a destructor: no exit path of the timed launch can leak one
 struct Event {
   hipEvent_t e = nullptr;
   ~Event() { if (e) (void)hipEventDestroy(e); }
 };
+
+// The enqueue forms, once their arguments are checked: `nothing` to do returns without initialising the library, else
+// dispatch(stream).
+template <class F> int enqueue_on(void *stream, bool nothing, F &&dispatch) {
+  if (nothing) return MM_OK;
+  if (int rc = ensure_init()) return rc;
+  return dispatch((hipStream_t)stream);
+}
+
+// The blocking forms (mm_*_launch), once their arguments are checked: `nothing` to do reports 0 s and touches no device,
+// else dispatch(null stream) on `device` between two HIP events, synchronised; *elapsed = the time between them.
+template <class F> int launch_timed(int device, bool nothing, double *elapsed, F &&dispatch) {
+  if (nothing) {
+    if (elapsed) *elapsed = 0.0;
+    return MM_OK;
+  }
+  if (int rc = check_device(device)) return rc;
+  MM_HIP(hipSetDevice(device));
+  Event start, stop;
+  MM_HIP(hipEventCreate(&start.e));
+  MM_HIP(hipEventCreate(&stop.e));
+  MM_HIP(hipEventRecord(start.e, nullptr));
+  if (int rc = dispatch((hipStream_t)nullptr)) return rc;
+  MM_HIP(hipEventRecord(stop.e, nullptr));
+  MM_HIP(hipEventSynchronize(stop.e));
+  if (elapsed) {
+    float ms = 0.f;
+    MM_HIP(hipEventElapsedTime(&ms, start.e, stop.e));
+    *elapsed = 1e-3 * (double)ms;
+  }
+  return MM_OK;
+}
 
 }  // namespace
 
@@ -924,36 +953,20 @@ int mm_gemm_enqueue(void *hip_stream, const mm_config_t *cfg, const void *a, con
 
 int mm_gemm_launch(int device, const mm_config_t *cfg, const void *a, const void *b, void *c, unsigned n, unsigned k,
                    unsigned m, double *elapsed_seconds) {
-  int rc = check_device(device);
+  int rc = check_device(device);   // the device first, then the arguments
   if (rc) return rc;
   rc = check_problem(cfg, a, b, c, n, k, m);
   if (rc) return rc;
-  MM_HIP(hipSetDevice(device));
-  Event start, stop;
-  MM_HIP(hipEventCreate(&start.e));
-  MM_HIP(hipEventCreate(&stop.e));
-  mm::Problem p{a, b, c, n, k, m, cfg->layout_a == MM_A_TRANSPOSED};
-  MM_HIP(hipEventRecord(start.e, nullptr));
-  rc = dispatch(nullptr, *cfg, p);
-  if (rc != MM_OK) return rc;
-  MM_HIP(hipEventRecord(stop.e, nullptr));
-  MM_HIP(hipEventSynchronize(stop.e));
-  if (elapsed_seconds) {
-    float ms = 0.f;
-    MM_HIP(hipEventElapsedTime(&ms, start.e, stop.e));
-    *elapsed_seconds = 1e-3 * (double)ms;
-  }
-  return MM_OK;
+  const mm::Problem p{a, b, c, n, k, m, cfg->layout_a == MM_A_TRANSPOSED};
+  return launch_timed(device, false, elapsed_seconds, [&](hipStream_t s) { return dispatch(s, *cfg, p); });
 }
 
 int mm_gemm_batched_enqueue(void *hip_stream, const mm_config_t *cfg, const void *a, const void *b, void *c, unsigned n,
                             unsigned k, unsigned m, unsigned batch, size_t stride_a, size_t stride_b, size_t stride_c) {
   const mm::Problem p = batched_problem(cfg, a, b, c, n, k, m, batch, stride_a, stride_b, stride_c);
   Family fam;
-  int rc = check_batched(cfg, p, &fam);
-  if (rc || fam == FAM_NONE) return rc;   // (FAM_NONE: an empty batch, nothing to do)
-  if ((rc = ensure_init())) return rc;
-  return dispatch_batched((hipStream_t)hip_stream, *cfg, p, fam);
+  if (int rc = check_batched(cfg, p, &fam)) return rc;
+  return enqueue_on(hip_stream, fam == FAM_NONE, [&](hipStream_t s) { return dispatch_batched(s, *cfg, p, fam); });
 }
 
 int mm_gemm_batched_launch(int device, const mm_config_t *cfg, const void *a, const void *b, void *c, unsigned n,
@@ -961,28 +974,8 @@ int mm_gemm_batched_launch(int device, const mm_config_t *cfg, const void *a, co
                            double *elapsed_seconds) {
   const mm::Problem p = batched_problem(cfg, a, b, c, n, k, m, batch, stride_a, stride_b, stride_c);
   Family fam;
-  int rc = check_batched(cfg, p, &fam);
-  if (rc) return rc;
-  if (fam == FAM_NONE) {   // an empty batch: nothing to launch or time
-    if (elapsed_seconds) *elapsed_seconds = 0.0;
-    return MM_OK;
-  }
-  if ((rc = check_device(device))) return rc;
-  MM_HIP(hipSetDevice(device));
-  Event start, stop;
-  MM_HIP(hipEventCreate(&start.e));
-  MM_HIP(hipEventCreate(&stop.e));
-  MM_HIP(hipEventRecord(start.e, nullptr));
-  rc = dispatch_batched(nullptr, *cfg, p, fam);
-  if (rc != MM_OK) return rc;
-  MM_HIP(hipEventRecord(stop.e, nullptr));
-  MM_HIP(hipEventSynchronize(stop.e));
-  if (elapsed_seconds) {
-    float ms = 0.f;
-    MM_HIP(hipEventElapsedTime(&ms, start.e, stop.e));
-    *elapsed_seconds = 1e-3 * (double)ms;
-  }
-  return MM_OK;
+  if (int rc = check_batched(cfg, p, &fam)) return rc;
+  return launch_timed(device, fam == FAM_NONE, elapsed_seconds, [&](hipStream_t s) { return dispatch_batched(s, *cfg, p, fam); });
 }
 
 int mm_gemm_batched_accumulate_enqueue(void *hip_stream, const mm_config_t *cfg, const void *a, const void *b, void *c,
@@ -991,10 +984,8 @@ int mm_gemm_batched_accumulate_enqueue(void *hip_stream, const mm_config_t *cfg,
   mm::Problem p = batched_problem(cfg, a, b, c, n, k, m, batch, stride_a, stride_b, stride_c);
   p.seed = true;
   Family fam;
-  int rc = check_accumulate(cfg, p, &fam);
-  if (rc || fam == FAM_NONE) return rc;   // (FAM_NONE: an empty batch or K = 0, nothing to do)
-  if ((rc = ensure_init())) return rc;
-  return dispatch_batched((hipStream_t)hip_stream, *cfg, p, fam);
+  if (int rc = check_accumulate(cfg, p, &fam)) return rc;
+  return enqueue_on(hip_stream, fam == FAM_NONE, [&](hipStream_t s) { return dispatch_batched(s, *cfg, p, fam); });
 }
 
 int mm_gemm_batched_accumulate_launch(int device, const mm_config_t *cfg, const void *a, const void *b, void *c, unsigned n,
@@ -1003,28 +994,8 @@ int mm_gemm_batched_accumulate_launch(int device, const mm_config_t *cfg, const 
   mm::Problem p = batched_problem(cfg, a, b, c, n, k, m, batch, stride_a, stride_b, stride_c);
   p.seed = true;
   Family fam;
-  int rc = check_accumulate(cfg, p, &fam);
-  if (rc) return rc;
-  if (fam == FAM_NONE) {   // an empty batch or K = 0: nothing to launch or time
-    if (elapsed_seconds) *elapsed_seconds = 0.0;
-    return MM_OK;
-  }
-  if ((rc = check_device(device))) return rc;
-  MM_HIP(hipSetDevice(device));
-  Event start, stop;
-  MM_HIP(hipEventCreate(&start.e));
-  MM_HIP(hipEventCreate(&stop.e));
-  MM_HIP(hipEventRecord(start.e, nullptr));
-  rc = dispatch_batched(nullptr, *cfg, p, fam);
-  if (rc != MM_OK) return rc;
-  MM_HIP(hipEventRecord(stop.e, nullptr));
-  MM_HIP(hipEventSynchronize(stop.e));
-  if (elapsed_seconds) {
-    float ms = 0.f;
-    MM_HIP(hipEventElapsedTime(&ms, start.e, stop.e));
-    *elapsed_seconds = 1e-3 * (double)ms;
-  }
-  return MM_OK;
+  if (int rc = check_accumulate(cfg, p, &fam)) return rc;
+  return launch_timed(device, fam == FAM_NONE, elapsed_seconds, [&](hipStream_t s) { return dispatch_batched(s, *cfg, p, fam); });
 }
 
 // The single accumulating launch is a batch of one: the batched kernel mm_kernel_name_batched(cfg, n, k, m, 1) names.
@@ -1044,10 +1015,9 @@ int mm_gemm_argreduce_enqueue(void *hip_stream, const mm_config_t *cfg, const vo
   mm::Problem p = batched_problem(cfg, a, b, c, n, k, m, batch, stride_a, stride_b, stride_c);
   p.seed = accumulate != 0;
   ArKernel ker;
-  int rc = check_argreduce(cfg, p, c_index, index_base, &ker);
-  if (rc || ker == AR_NONE) return rc;   // (AR_NONE: an empty batch or K = 0 accumulating, nothing to do)
-  if ((rc = ensure_init())) return rc;
-  return dispatch_argreduce((hipStream_t)hip_stream, *cfg, p, c_index, index_base, ker);
+  if (int rc = check_argreduce(cfg, p, c_index, index_base, &ker)) return rc;
+  return enqueue_on(hip_stream, ker == AR_NONE,
+                    [&](hipStream_t s) { return dispatch_argreduce(s, *cfg, p, c_index, index_base, ker); });
 }
 
 int mm_gemm_argreduce_launch(int device, const mm_config_t *cfg, const void *a, const void *b, void *c, int *c_index,
@@ -1056,28 +1026,9 @@ int mm_gemm_argreduce_launch(int device, const mm_config_t *cfg, const void *a, 
   mm::Problem p = batched_problem(cfg, a, b, c, n, k, m, batch, stride_a, stride_b, stride_c);
   p.seed = accumulate != 0;
   ArKernel ker;
-  int rc = check_argreduce(cfg, p, c_index, index_base, &ker);
-  if (rc) return rc;
-  if (ker == AR_NONE) {   // nothing to launch or time
-    if (elapsed_seconds) *elapsed_seconds = 0.0;
-    return MM_OK;
-  }
-  if ((rc = check_device(device))) return rc;
-  MM_HIP(hipSetDevice(device));
-  Event start, stop;
-  MM_HIP(hipEventCreate(&start.e));
-  MM_HIP(hipEventCreate(&stop.e));
-  MM_HIP(hipEventRecord(start.e, nullptr));
-  rc = dispatch_argreduce(nullptr, *cfg, p, c_index, index_base, ker);
-  if (rc != MM_OK) return rc;
-  MM_HIP(hipEventRecord(stop.e, nullptr));
-  MM_HIP(hipEventSynchronize(stop.e));
-  if (elapsed_seconds) {
-    float ms = 0.f;
-    MM_HIP(hipEventElapsedTime(&ms, start.e, stop.e));
-    *elapsed_seconds = 1e-3 * (double)ms;
-  }
-  return MM_OK;
+  if (int rc = check_argreduce(cfg, p, c_index, index_base, &ker)) return rc;
+  return launch_timed(device, ker == AR_NONE, elapsed_seconds,
+                      [&](hipStream_t s) { return dispatch_argreduce(s, *cfg, p, c_index, index_base, ker); });
 }
 
 int mm_gemm_logsumexp_enqueue(void *hip_stream, const mm_config_t *cfg, const void *a, const void *b, void *c, unsigned n,
@@ -1086,10 +1037,8 @@ int mm_gemm_logsumexp_enqueue(void *hip_stream, const mm_config_t *cfg, const vo
   mm::Problem p = batched_problem(cfg, a, b, c, n, k, m, batch, stride_a, stride_b, stride_c);
   p.seed = accumulate != 0;
   LseKernel ker;
-  int rc = check_lse(cfg, p, &ker);
-  if (rc || ker == LSE_NONE) return rc;   // (LSE_NONE: an empty batch or K = 0 accumulating, nothing to do)
-  if ((rc = ensure_init())) return rc;
-  return dispatch_lse((hipStream_t)hip_stream, *cfg, p, ker);
+  if (int rc = check_lse(cfg, p, &ker)) return rc;
+  return enqueue_on(hip_stream, ker == LSE_NONE, [&](hipStream_t s) { return dispatch_lse(s, *cfg, p, ker); });
 }
 
 int mm_gemm_logsumexp_launch(int device, const mm_config_t *cfg, const void *a, const void *b, void *c, unsigned n,
@@ -1098,64 +1047,24 @@ int mm_gemm_logsumexp_launch(int device, const mm_config_t *cfg, const void *a, 
   mm::Problem p = batched_problem(cfg, a, b, c, n, k, m, batch, stride_a, stride_b, stride_c);
   p.seed = accumulate != 0;
   LseKernel ker;
-  int rc = check_lse(cfg, p, &ker);
-  if (rc) return rc;
-  if (ker == LSE_NONE) {   // nothing to launch or time
-    if (elapsed_seconds) *elapsed_seconds = 0.0;
-    return MM_OK;
-  }
-  if ((rc = check_device(device))) return rc;
-  MM_HIP(hipSetDevice(device));
-  Event start, stop;
-  MM_HIP(hipEventCreate(&start.e));
-  MM_HIP(hipEventCreate(&stop.e));
-  MM_HIP(hipEventRecord(start.e, nullptr));
-  rc = dispatch_lse(nullptr, *cfg, p, ker);
-  if (rc != MM_OK) return rc;
-  MM_HIP(hipEventRecord(stop.e, nullptr));
-  MM_HIP(hipEventSynchronize(stop.e));
-  if (elapsed_seconds) {
-    float ms = 0.f;
-    MM_HIP(hipEventElapsedTime(&ms, start.e, stop.e));
-    *elapsed_seconds = 1e-3 * (double)ms;
-  }
-  return MM_OK;
+  if (int rc = check_lse(cfg, p, &ker)) return rc;
+  return launch_timed(device, ker == LSE_NONE, elapsed_seconds, [&](hipStream_t s) { return dispatch_lse(s, *cfg, p, ker); });
 }
 
 int mm_closure_enqueue(void *hip_stream, const mm_config_t *cfg, void *d, int *witness, unsigned n, unsigned batch,
                        size_t stride_d) {
-  unsigned block;
-  int rc = check_closure(cfg, d, witness, n, batch, stride_d, &block);
-  if (rc || block == 0) return rc;   // (block 0: n or batch 0, nothing to do)
-  if ((rc = ensure_init())) return rc;
-  return dispatch_closure((hipStream_t)hip_stream, *cfg, d, witness, n, batch, stride_d, block);
+  unsigned block;   // 0: n or batch 0, nothing to do
+  if (int rc = check_closure(cfg, d, witness, n, batch, stride_d, &block)) return rc;
+  return enqueue_on(hip_stream, block == 0,
+                    [&](hipStream_t s) { return dispatch_closure(s, *cfg, d, witness, n, batch, stride_d, block); });
 }
 
 int mm_closure_launch(int device, const mm_config_t *cfg, void *d, int *witness, unsigned n, unsigned batch, size_t stride_d,
                       double *elapsed_seconds) {
   unsigned block;
-  int rc = check_closure(cfg, d, witness, n, batch, stride_d, &block);
-  if (rc) return rc;
-  if (block == 0) {   // nothing to launch or time
-    if (elapsed_seconds) *elapsed_seconds = 0.0;
-    return MM_OK;
-  }
-  if ((rc = check_device(device))) return rc;
-  MM_HIP(hipSetDevice(device));
-  Event start, stop;
-  MM_HIP(hipEventCreate(&start.e));
-  MM_HIP(hipEventCreate(&stop.e));
-  MM_HIP(hipEventRecord(start.e, nullptr));
-  rc = dispatch_closure(nullptr, *cfg, d, witness, n, batch, stride_d, block);
-  if (rc != MM_OK) return rc;
-  MM_HIP(hipEventRecord(stop.e, nullptr));
-  MM_HIP(hipEventSynchronize(stop.e));
-  if (elapsed_seconds) {
-    float ms = 0.f;
-    MM_HIP(hipEventElapsedTime(&ms, start.e, stop.e));
-    *elapsed_seconds = 1e-3 * (double)ms;
-  }
-  return MM_OK;
+  if (int rc = check_closure(cfg, d, witness, n, batch, stride_d, &block)) return rc;
+  return launch_timed(device, block == 0, elapsed_seconds,
+                      [&](hipStream_t s) { return dispatch_closure(s, *cfg, d, witness, n, batch, stride_d, block); });
 }
 
 // Rows per device of the N split: ceil(N / G) rounded up to whole tile rows of the kernel that will run on a slab of that
@@ -1247,11 +1156,6 @@ int mm_gemm_multi_device_timed(int device_count, const mm_config_t *cfg, const v
   const bool kxn = cfg->layout_a == MM_A_TRANSPOSED;
   const unsigned slab = md_slab_rows(*cfg, n, k, m, device_count);
   std::vector<SplitDevice> devs(device_count);
-#define MM_HIP_MD(call)                                       \
-  do {                                                        \
-    hipError_t e_ = (call);                                   \
-    if (e_ != hipSuccess) return hip_fail(e_, #call);         \
-  } while (0)
   // independent row slabs: logical device g owns C[row0 : row0+rows, :] = A[row0 : row0+rows, :] . B
   // (kernel/Compute.cpp:53-60: no outer tile of C depends on another one)
   for (int g = 0; g < device_count; ++g) {
@@ -1259,28 +1163,28 @@ int mm_gemm_multi_device_timed(int device_count, const mm_config_t *cfg, const v
     d.phys = g % g_device_count;
     d.row0 = (unsigned)std::min<size_t>((size_t)g * slab, n);
     d.rows = std::min(slab, n - d.row0);
-    MM_HIP_MD(hipSetDevice(d.phys));
-    MM_HIP_MD(hipStreamCreateWithFlags(&d.s, hipStreamNonBlocking));
+    MM_HIP(hipSetDevice(d.phys));
+    MM_HIP(hipStreamCreateWithFlags(&d.s, hipStreamNonBlocking));
     if (!d.rows) continue;          // a trailing device without rows takes no part (and no copy of B)
-    MM_HIP_MD(hipEventCreate(&d.start));
-    MM_HIP_MD(hipEventCreate(&d.stop));
-    MM_HIP_MD(hipMalloc(&d.b, (size_t)k * m * es));
-    MM_HIP_MD(hipMalloc(&d.a, (size_t)d.rows * k * es));
-    MM_HIP_MD(hipMalloc(&d.c, (size_t)d.rows * m * es));
+    MM_HIP(hipEventCreate(&d.start));
+    MM_HIP(hipEventCreate(&d.stop));
+    MM_HIP(hipMalloc(&d.b, (size_t)k * m * es));
+    MM_HIP(hipMalloc(&d.a, (size_t)d.rows * k * es));
+    MM_HIP(hipMalloc(&d.c, (size_t)d.rows * m * es));
   }
   // B crosses PCIe ONCE (host -> device 0) and is then fanned out device 0 -> device g over xGMI
   // (every GPU has its own link to GPU 0, so the G-1 peer copies run concurrently), instead of G
   // pageable host copies through one root complex; the A slabs go up meanwhile.  A device that
   // cannot take the peer copy gets B from the host as before.
   Event b_on_dev0;
-  MM_HIP_MD(hipSetDevice(devs[0].phys));
-  MM_HIP_MD(hipEventCreateWithFlags(&b_on_dev0.e, hipEventDisableTiming));
-  MM_HIP_MD(hipMemcpyAsync(devs[0].b, b_host, (size_t)k * m * es, hipMemcpyHostToDevice, devs[0].s));
-  MM_HIP_MD(hipEventRecord(b_on_dev0.e, devs[0].s));
+  MM_HIP(hipSetDevice(devs[0].phys));
+  MM_HIP(hipEventCreateWithFlags(&b_on_dev0.e, hipEventDisableTiming));
+  MM_HIP(hipMemcpyAsync(devs[0].b, b_host, (size_t)k * m * es, hipMemcpyHostToDevice, devs[0].s));
+  MM_HIP(hipEventRecord(b_on_dev0.e, devs[0].s));
   for (int g = 0; g < device_count; ++g) {
     SplitDevice &d = devs[g];
     if (!d.rows) continue;
-    MM_HIP_MD(hipSetDevice(d.phys));
+    MM_HIP(hipSetDevice(d.phys));
     if (g > 0) {
       bool peer = d.phys == devs[0].phys;          // the same physical device (virtual devices): a peer copy onto itself
       if (!peer) {
@@ -1293,22 +1197,22 @@ int mm_gemm_multi_device_timed(int device_count, const mm_config_t *cfg, const v
         (void)hipGetLastError();  // "already enabled" / "no peer" are not errors of this call
       }
       if (peer) {
-        MM_HIP_MD(hipStreamWaitEvent(d.s, b_on_dev0.e, 0));
-        MM_HIP_MD(hipMemcpyPeerAsync(d.b, d.phys, devs[0].b, devs[0].phys, (size_t)k * m * es, d.s));
+        MM_HIP(hipStreamWaitEvent(d.s, b_on_dev0.e, 0));
+        MM_HIP(hipMemcpyPeerAsync(d.b, d.phys, devs[0].b, devs[0].phys, (size_t)k * m * es, d.s));
       } else {
-        MM_HIP_MD(hipMemcpyAsync(d.b, b_host, (size_t)k * m * es, hipMemcpyHostToDevice, d.s));
+        MM_HIP(hipMemcpyAsync(d.b, b_host, (size_t)k * m * es, hipMemcpyHostToDevice, d.s));
       }
     }
     if (!kxn) {   // rows [row0, row0 + rows) of a row-major A: one contiguous block
-      MM_HIP_MD(hipMemcpyAsync(d.a, (const char *)a_host + (size_t)d.row0 * k * es, (size_t)d.rows * k * es,
-                               hipMemcpyHostToDevice, d.s));
+      MM_HIP(hipMemcpyAsync(d.a, (const char *)a_host + (size_t)d.row0 * k * es, (size_t)d.rows * k * es,
+                            hipMemcpyHostToDevice, d.s));
     } else {      // the same rows of a K x N A (MM_TRANSPOSED_A, kernel/Memory.cpp:205-261): COLUMNS [row0, row0 + rows) of every
                   // one of its K rows -> a dense K x rows matrix on the device
-      MM_HIP_MD(hipMemcpy2DAsync(d.a, (size_t)d.rows * es, (const char *)a_host + (size_t)d.row0 * es, (size_t)n * es,
-                                 (size_t)d.rows * es, k, hipMemcpyHostToDevice, d.s));
+      MM_HIP(hipMemcpy2DAsync(d.a, (size_t)d.rows * es, (const char *)a_host + (size_t)d.row0 * es, (size_t)n * es,
+                              (size_t)d.rows * es, k, hipMemcpyHostToDevice, d.s));
     }
   }
-  for (SplitDevice &d : devs) { MM_HIP_MD(hipSetDevice(d.phys)); MM_HIP_MD(hipStreamSynchronize(d.s)); }
+  for (SplitDevice &d : devs) { MM_HIP(hipSetDevice(d.phys)); MM_HIP(hipStreamSynchronize(d.s)); }
   // untimed warm-up pass of the same launch: the first dispatch on a device loads the code object,
   // opts the kernel into its LDS size and ramps the clocks; paying that outside the timed region
   // makes this figure comparable with mm_gemm_launch's (whose callers warm up the same way).
@@ -1321,23 +1225,23 @@ int mm_gemm_multi_device_timed(int device_count, const mm_config_t *cfg, const v
     const auto t0 = std::chrono::steady_clock::now();
     for (SplitDevice &d : devs) {
       if (!d.rows) continue;
-      MM_HIP_MD(hipSetDevice(d.phys));
+      MM_HIP(hipSetDevice(d.phys));
       // a row slab of the n-row job (n_total 0: the slab IS the job -- the same launch as mm_gemm_launch's)
       const mm::Problem p{d.a, d.b, d.c, d.rows, k, m, kxn, d.rows == n ? 0u : n};
-      MM_HIP_MD(hipEventRecord(d.start, d.s));
+      MM_HIP(hipEventRecord(d.start, d.s));
       rc = dispatch(d.s, *cfg, p);
       if (rc) return rc;
-      MM_HIP_MD(hipEventRecord(d.stop, d.s));
+      MM_HIP(hipEventRecord(d.stop, d.s));
     }
-    for (SplitDevice &d : devs) { MM_HIP_MD(hipSetDevice(d.phys)); MM_HIP_MD(hipStreamSynchronize(d.s)); }
+    for (SplitDevice &d : devs) { MM_HIP(hipSetDevice(d.phys)); MM_HIP(hipStreamSynchronize(d.s)); }
     wall = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
   }
   for (int g = 0; g < device_count; ++g) {
     SplitDevice &d = devs[g];
     if (!d.rows) continue;
-    MM_HIP_MD(hipSetDevice(d.phys));
+    MM_HIP(hipSetDevice(d.phys));
     float ms = 0.f;
-    MM_HIP_MD(hipEventElapsedTime(&ms, d.start, d.stop));
+    MM_HIP(hipEventElapsedTime(&ms, d.start, d.stop));
     if (per_device_seconds) per_device_seconds[g] = 1e-3 * (double)ms;
     elapsed = std::max(elapsed, 1e-3 * (double)ms);
   }
@@ -1345,10 +1249,9 @@ int mm_gemm_multi_device_timed(int device_count, const mm_config_t *cfg, const v
   if (elapsed_seconds) *elapsed_seconds = elapsed;
   for (SplitDevice &d : devs) {
     if (!d.rows) continue;
-    MM_HIP_MD(hipSetDevice(d.phys));
-    MM_HIP_MD(hipMemcpy((char *)c_host + (size_t)d.row0 * m * es, d.c, (size_t)d.rows * m * es, hipMemcpyDeviceToHost));
+    MM_HIP(hipSetDevice(d.phys));
+    MM_HIP(hipMemcpy((char *)c_host + (size_t)d.row0 * m * es, d.c, (size_t)d.rows * m * es, hipMemcpyDeviceToHost));
   }
-#undef MM_HIP_MD
   return MM_OK;
 }
 
@@ -1455,7 +1358,7 @@ int mm_config_supported(const mm_config_t *cfg) {
 const char *mm_kernel_name(const mm_config_t *cfg, unsigned n, unsigned k, unsigned m) {
   if (!valid_cfg(cfg)) return "invalid";
   mm::Problem p{nullptr, nullptr, nullptr, n, k, m, cfg->layout_a == MM_A_TRANSPOSED};
-  switch (choose(*cfg, p)) {
+  switch (const Family fam = choose(*cfg, p)) {
     // every family answers through the same resolver its launcher uses, so the name IS the kernel that runs
     case FAM_MFMA_F32: {
       const int v = f32_variant_for(p);
@@ -1481,19 +1384,15 @@ const char *mm_kernel_name(const mm_config_t *cfg, unsigned n, unsigned k, unsig
     case FAM_MFMA_F64: return mm::mfma_f64_name(p);
     case FAM_MFMA_F16: return mm::mfma_f16_name(p);
     case FAM_MFMA_I8: return mm::mfma_i8_name(p);
-    case FAM_HALF_WIDE: return "ordered_wide_f16";
     case FAM_F32_SPLIT: return "mfma_f32_split_bf16x3";
-    case FAM_NONE: return "unsupported";
-    case FAM_VALU_TILE: return "valu_tile";
-    case FAM_ORDERED_TILE: return "ordered_tile";   // k ascending, one accumulator, unfused: Naive's bits on 128 x 128 register tiles
-    default: return "ordered";
+    default: return family_name(fam);
   }
 }
 
 const char *mm_kernel_name_batched(const mm_config_t *cfg, unsigned n, unsigned k, unsigned m, unsigned batch) {
   if (!valid_cfg(cfg)) return "invalid";
   const mm::Problem p = batched_problem(cfg, nullptr, nullptr, nullptr, n, k, m, batch ? batch : 1, 0, 0, 0);
-  switch (choose_batched(*cfg, p)) {   // the resolver dispatch_batched uses
+  switch (const Family fam = choose_batched(*cfg, p)) {   // the resolver dispatch_batched uses
     case FAM_MFMA_F32: {
       const int v = mm::mfma_f32_batched_resolve(p, f32_variant());
       return v < 0 ? "unsupported" : mm::mfma_f32_name(v);
@@ -1501,11 +1400,7 @@ const char *mm_kernel_name_batched(const mm_config_t *cfg, unsigned n, unsigned 
     case FAM_MFMA_F64: return mm::mfma_f64_batched_name(p);
     case FAM_MFMA_F16: return mm::mfma_f16_batched_name(p);
     case FAM_MFMA_I8: return mm::mfma_i8_batched_name(p);
-    case FAM_HALF_WIDE: return "ordered_wide_f16";
-    case FAM_VALU_TILE: return "valu_tile";
-    case FAM_ORDERED_TILE: return "ordered_tile";
-    case FAM_NONE: return "unsupported";
-    default: return "ordered";
+    default: return family_name(fam);
   }
 }
 
