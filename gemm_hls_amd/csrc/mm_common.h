@@ -94,7 +94,7 @@ struct Problem {
   unsigned batch = 1;
   size_t stride_a = 0, stride_b = 0, stride_c = 0;
   // accumulate (mm_gemm_*accumulate_*): C <- C (+) (A (x) B), each output's reduction starts at the value C holds instead
-  // of identity().  Only the *_batched launchers read it (they then run the kernels' *_batched_seeded forms).
+  // of identity().  Only the *_batched launchers read it (they then run the kernels' Form::Seeded instantiations).
   bool seed = false;
 };
 
@@ -308,7 +308,13 @@ __device__ __forceinline__ unsigned xcd_remap(unsigned bid, unsigned nwg) {
   return base + slot;
 }
 
-// Batched launches (the *_batched_kernel forms): `batch` elements of one shape, `batch` copies of the tile grid in one
+// The three forms every kernel of the older families exists in, a template parameter of the kernel: the single launch,
+// the strided-batched launch, and the batched launch whose reduction starts at the value C holds (Problem::seed; Seeded
+// implies batched).  Every form takes the batched argument list (..., batch, stride_a, stride_b, stride_c); Form::Single
+// never reads that tail, so its machine code is that of a kernel without it.
+enum class Form { Single, Batched, Seeded };
+
+// Batched launches (Form::Batched, Form::Seeded): `batch` elements of one shape, `batch` copies of the tile grid in one
 // launch.  The XCD-remapped linear id is decomposed as (element, tile), so one element's tiles stay contiguous in an XCD's
 // chunk of the grid (a broadcast B, or one element's A panels, stays in that XCD's L2); the element index is uniform across
 // the workgroup (SGPRs) and moves the A, B and C bases before anything else.  Returns the element's linear tile id.
@@ -320,6 +326,15 @@ __device__ __forceinline__ unsigned batched_tile(PA &A, PB &B, PC &C, unsigned t
   B += e * stride_b;
   C += e * stride_c;
   return g - e * tiles;
+}
+
+// The workgroup's linear tile id in a kernel of form F: the XCD-remapped workgroup id of a single launch, or the
+// element's tile of a batched one (A, B and C then move to that element).
+template <Form F, typename PA, typename PB, typename PC>
+__device__ __forceinline__ unsigned form_tile(PA &A, PB &B, PC &C, unsigned tiles, unsigned batch, size_t stride_a,
+                                              size_t stride_b, size_t stride_c) {
+  if constexpr (F == Form::Single) return xcd_remap(blockIdx.x, tiles);
+  else return batched_tile(A, B, C, tiles, batch, stride_a, stride_b, stride_c);
 }
 
 }  // namespace mm

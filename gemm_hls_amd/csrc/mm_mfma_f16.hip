@@ -95,15 +95,7 @@ __device__ __forceinline__ h8 join(s4 lo, s4 hi) {
   return u.h;
 }
 
-#define MM_BATCHED 0
 #include "mm_mfma_f16_kernels.inc"
-#undef MM_BATCHED
-#define MM_BATCHED 1
-#include "mm_mfma_f16_kernels.inc"
-#define MM_SEEDED 1
-#include "mm_mfma_f16_kernels.inc"
-#undef MM_SEEDED
-#undef MM_BATCHED
 
 #undef MM_DMA_PIECE
 
@@ -166,36 +158,41 @@ static Kind resolve(const Problem &p) {
 
 const char *mfma_f16_name(const Problem &p) { return kNames[resolve(p)]; }
 
-template <typename Kern>
-static int launch_tile(hipStream_t s, const Problem &p, Kern kern, unsigned bm, unsigned bn, unsigned threads, int lds,
-                       unsigned long long &configured) {
+// One launch of the kernel KERN, an instantiation for form F: the problem at (a, b, c), or (F != Form::Single) p.batch copies of
+// the tile grid over the elements of p
+template <Form F, auto KERN>
+static int launch_tile(hipStream_t s, const Problem &p, unsigned bm, unsigned bn, unsigned threads, int lds) {
   const unsigned tiles_n = (p.n + bm - 1) / bm, tiles_m = (p.m + bn - 1) / bn;
-  if (int e = ensure_dynamic_lds((const void *)kern, lds, configured)) return e;
-  hipLaunchKernelGGL(kern, dim3(tiles_n * tiles_m), dim3(threads), lds, s, (const _Float16 *)p.a, (const _Float16 *)p.b,
-                     (_Float16 *)p.c, p.n, p.k, p.m, tiles_n, tiles_m, band_rows(bm, bn, 1));
+  static unsigned long long configured = 0;   // one per instantiation of this function, so one per kernel
+  if (int e = ensure_dynamic_lds((const void *)KERN, lds, configured)) return e;
+  hipLaunchKernelGGL(KERN, dim3(tiles_n * tiles_m * (F == Form::Single ? 1u : p.batch)), dim3(threads), lds, s,
+                     (const _Float16 *)p.a, (const _Float16 *)p.b, (_Float16 *)p.c, p.n, p.k, p.m, tiles_n, tiles_m,
+                     band_rows(bm, bn, 1), F == Form::Single ? 1u : p.batch, p.stride_a, p.stride_b, p.stride_c);
   return (int)hipGetLastError();
 }
 
-// the batched kernels' launch: p.batch copies of the tile grid, the element strides after the single kernel's arguments
-template <typename Kern>
-static int launch_tile_batched(hipStream_t s, const Problem &p, Kern kern, unsigned bm, unsigned bn, unsigned threads, int lds,
-                       unsigned long long &configured) {
-  const unsigned tiles_n = (p.n + bm - 1) / bm, tiles_m = (p.m + bn - 1) / bn;
-  if (int e = ensure_dynamic_lds((const void *)kern, lds, configured)) return e;
-  hipLaunchKernelGGL(kern, dim3(tiles_n * tiles_m * p.batch), dim3(threads), lds, s, (const _Float16 *)p.a, (const _Float16 *)p.b,
-                     (_Float16 *)p.c, p.n, p.k, p.m, tiles_n, tiles_m, band_rows(bm, bn, 1), p.batch, p.stride_a, p.stride_b, p.stride_c);
-  return (int)hipGetLastError();
+// The kernel of each Kind, in form F
+template <Form F>
+static int launch_kind(hipStream_t s, const Problem &p, Kind k) {
+  switch (k) {
+    case K_PP16: return launch_tile<F, mfma_f16_pp2s_kernel<F>>(s, p, 256, 256, GeoPP2::THREADS, GeoPP2::LDS_BYTES);
+    case K_PP32: return launch_tile<F, mfma_f16_pp2_kernel<F>>(s, p, 256, 256, GeoPP2::THREADS, GeoPP2::LDS_BYTES);
+    case K_PPK32: return launch_tile<F, mfma_f16_pp_kernel<F, false>>(s, p, 256, 256, GeoPP::THREADS, GeoPP::LDS_BYTES);
+    case K_PPK32_AT: return launch_tile<F, mfma_f16_pp_kernel<F, true>>(s, p, 256, 256, GeoPP::THREADS, GeoPP::LDS_BYTES);
+    case K_SLAB64: return launch_tile<F, mfma_f16_kernel<F, GeoH, false>>(s, p, GeoH::BM, GeoH::BN, GeoH::THREADS, GeoH::LDS_BYTES);
+    case K_SLAB64_AT: return launch_tile<F, mfma_f16_kernel<F, GeoH, true>>(s, p, GeoH::BM, GeoH::BN, GeoH::THREADS, GeoH::LDS_BYTES);
+    case K_SLAB64_128: return launch_tile<F, mfma_f16_kernel<F, GeoHS, false>>(s, p, GeoHS::BM, GeoHS::BN, GeoHS::THREADS, GeoHS::LDS_BYTES);
+    case K_SLAB64_64: return launch_tile<F, mfma_f16_kernel<F, GeoHXS, false>>(s, p, GeoHXS::BM, GeoHXS::BN, GeoHXS::THREADS, GeoHXS::LDS_BYTES);
+    default: return kErrNotSupported;
+  }
 }
 
 // A K x N A served where it lies (no workspace): the ping-pong K x N kernel where its shape rules allow, else slab64's
-static int launch_kxn_in_place(hipStream_t s, const Problem &p, unsigned long long (&cfg)[K_NONE]) {
-  if (tuning(TUNE_F16_VARIANT) != 0 && ppk32_serves(p))
-    return launch_tile(s, p, mfma_f16_pp_kernel<true>, 256, 256, GeoPP::THREADS, GeoPP::LDS_BYTES, cfg[K_PPK32_AT]);
-  return launch_tile(s, p, mfma_f16_kernel<GeoH, true>, GeoH::BM, GeoH::BN, GeoH::THREADS, GeoH::LDS_BYTES, cfg[K_SLAB64_AT]);
+static int launch_kxn_in_place(hipStream_t s, const Problem &p) {
+  return launch_kind<Form::Single>(s, p, tuning(TUNE_F16_VARIANT) != 0 && ppk32_serves(p) ? K_PPK32_AT : K_SLAB64_AT);
 }
 
 int launch_mfma_f16(hipStream_t s, const Problem &p) {
-  static unsigned long long cfg[K_NONE] = {};
   if (transposes_first(p)) {
     int dev = 0;
     hipError_t e = hipGetDevice(&dev);
@@ -207,7 +204,7 @@ int launch_mfma_f16(hipStream_t s, const Problem &p) {
       // no room for the N x K copy (up to 4 GiB next to a nearly full device): not an error -- the K x N kernels serve the
       // call without extra memory, as they did before the pre-pass existed; same contract, ~2-3 % slower
       (void)hipGetLastError();
-      return launch_kxn_in_place(s, p, cfg);
+      return launch_kxn_in_place(s, p);
     }
     int rc = launch_transpose_kxn(s, p.a, an, p.k, p.n, 2);
     if (rc == 0) {
@@ -219,20 +216,8 @@ int launch_mfma_f16(hipStream_t s, const Problem &p) {
     const hipError_t f = hipFreeAsync(an, s);
     return rc ? rc : (int)f;
   }
-  const Kind k = resolve(p);
-  switch (k) {
-    case K_PP16: return launch_tile(s, p, mfma_f16_pp2s_kernel, 256, 256, GeoPP2::THREADS, GeoPP2::LDS_BYTES, cfg[k]);
-    case K_PP32: return launch_tile(s, p, mfma_f16_pp2_kernel, 256, 256, GeoPP2::THREADS, GeoPP2::LDS_BYTES, cfg[k]);
-    case K_PPK32: return launch_tile(s, p, mfma_f16_pp_kernel<false>, 256, 256, GeoPP::THREADS, GeoPP::LDS_BYTES, cfg[k]);
-    case K_PPK32_AT: return launch_tile(s, p, mfma_f16_pp_kernel<true>, 256, 256, GeoPP::THREADS, GeoPP::LDS_BYTES, cfg[k]);
-    case K_SLAB64: return launch_tile(s, p, mfma_f16_kernel<GeoH, false>, GeoH::BM, GeoH::BN, GeoH::THREADS, GeoH::LDS_BYTES, cfg[k]);
-    case K_SLAB64_AT: return launch_tile(s, p, mfma_f16_kernel<GeoH, true>, GeoH::BM, GeoH::BN, GeoH::THREADS, GeoH::LDS_BYTES, cfg[k]);
-    case K_SLAB64_128: return launch_tile(s, p, mfma_f16_kernel<GeoHS, false>, GeoHS::BM, GeoHS::BN, GeoHS::THREADS, GeoHS::LDS_BYTES, cfg[k]);
-    case K_SLAB64_64: return launch_tile(s, p, mfma_f16_kernel<GeoHXS, false>, GeoHXS::BM, GeoHXS::BN, GeoHXS::THREADS, GeoHXS::LDS_BYTES, cfg[k]);
-    default: return kErrNotSupported;
-  }
+  return launch_kind<Form::Single>(s, p, resolve(p));
 }
-
 
 // Batched (mm_gemm_batched_*): whole tiles of the in-place kernels, decided on the whole batch (Problem::batch copies of the
 // tile grid).  The instruction schedule -- and with it the bits -- depends on the element's shape only: where a ping-pong
@@ -248,25 +233,9 @@ static Kind resolve_batched(const Problem &p) {
 int mfma_f16_batched_resolve(const Problem &p) { const Kind k = resolve_batched(p); return k == K_NONE ? -1 : (int)k; }
 const char *mfma_f16_batched_name(const Problem &p) { return kNames[resolve_batched(p)]; }
 int launch_mfma_f16_batched(hipStream_t s, const Problem &p, int kind) {
-  static unsigned long long bcfg[K_NONE] = {}, scfg[K_NONE] = {};
   if (kind < 0 || kind >= (int)K_NONE) return kErrNotSupported;
-  const Kind k = (Kind)kind;
-  // SUF: _batched, or _batched_seeded for an accumulating launch (p.seed) -- the same kernel with C's value in its epilogue
-#define MM_F16_BATCHED(SUF, CFG)                                                                                                       \
-  switch (k) {                                                                                                                         \
-    case K_PP16: return launch_tile_batched(s, p, mfma_f16_pp2s_kernel##SUF, 256, 256, GeoPP2::THREADS, GeoPP2::LDS_BYTES, CFG[k]);   \
-    case K_PP32: return launch_tile_batched(s, p, mfma_f16_pp2_kernel##SUF, 256, 256, GeoPP2::THREADS, GeoPP2::LDS_BYTES, CFG[k]);    \
-    case K_PPK32: return launch_tile_batched(s, p, mfma_f16_pp_kernel##SUF<false>, 256, 256, GeoPP::THREADS, GeoPP::LDS_BYTES, CFG[k]); \
-    case K_PPK32_AT: return launch_tile_batched(s, p, mfma_f16_pp_kernel##SUF<true>, 256, 256, GeoPP::THREADS, GeoPP::LDS_BYTES, CFG[k]); \
-    case K_SLAB64: return launch_tile_batched(s, p, mfma_f16_kernel##SUF<GeoH, false>, GeoH::BM, GeoH::BN, GeoH::THREADS, GeoH::LDS_BYTES, CFG[k]); \
-    case K_SLAB64_AT: return launch_tile_batched(s, p, mfma_f16_kernel##SUF<GeoH, true>, GeoH::BM, GeoH::BN, GeoH::THREADS, GeoH::LDS_BYTES, CFG[k]); \
-    case K_SLAB64_128: return launch_tile_batched(s, p, mfma_f16_kernel##SUF<GeoHS, false>, GeoHS::BM, GeoHS::BN, GeoHS::THREADS, GeoHS::LDS_BYTES, CFG[k]); \
-    case K_SLAB64_64: return launch_tile_batched(s, p, mfma_f16_kernel##SUF<GeoHXS, false>, GeoHXS::BM, GeoHXS::BN, GeoHXS::THREADS, GeoHXS::LDS_BYTES, CFG[k]); \
-    default: return kErrNotSupported;                                                                                                  \
-  }
-  if (p.seed) MM_F16_BATCHED(_batched_seeded, scfg)
-  MM_F16_BATCHED(_batched, bcfg)
-#undef MM_F16_BATCHED
+  // an accumulating launch (p.seed): the same kernel with C's value in its epilogue
+  return p.seed ? launch_kind<Form::Seeded>(s, p, (Kind)kind) : launch_kind<Form::Batched>(s, p, (Kind)kind);
 }
 
 }  // namespace mm

@@ -1,12 +1,11 @@
-// The kernels of mm_mfma_f16.hip, compiled three times by it: MM_BATCHED 0 the single-problem kernels, 1 their *_batched twins,
-// MM_BATCHED 1 with MM_SEEDED 1 the *_batched_seeded forms that accumulate into C
-// (mm_batched_kernel.h).  Definitions that are not kernels appear in the first pass only.
-#include "mm_batched_kernel.h"
-template <typename G, bool AT>
-__global__ __launch_bounds__(G::THREADS) void MM_KNAME(mfma_f16_kernel)(const _Float16 *__restrict__ A,
+// The kernels of mm_mfma_f16.hip.  F (mm_common.h) is the form of each: the single-problem kernel, its strided-batched form,
+// or the batched form that accumulates into C.
+template <Form F, typename G, bool AT>
+__global__ __launch_bounds__(G::THREADS) void mfma_f16_kernel(const _Float16 *__restrict__ A,
                                                                  const _Float16 *__restrict__ B,
                                                                  _Float16 *__restrict__ C, unsigned N, unsigned K,
-                                                                 unsigned M, unsigned tiles_n, unsigned tiles_m, unsigned kBand MM_BATCH_PARAMS) {
+                                                                 unsigned M, unsigned tiles_n, unsigned tiles_m, unsigned kBand,
+                                                                 unsigned batch, size_t stride_a, size_t stride_b, size_t stride_c) {
   constexpr int TM = G::TM, TN = G::TN, BK = G::BK, NS = G::NS, CPR = G::CPR;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const unsigned lane = threadIdx.x & 63u;
@@ -15,7 +14,7 @@ __global__ __launch_bounds__(G::THREADS) void MM_KNAME(mfma_f16_kernel)(const _F
   const unsigned lo = lane & 31u, hi = lane >> 5;
 
   const unsigned nwg = tiles_n * tiles_m;
-  const unsigned lin = MM_TILE_LIN(blockIdx.x, nwg);
+  const unsigned lin = form_tile<F>(A, B, C, nwg, batch, stride_a, stride_b, stride_c);
   const unsigned band = lin / (kBand * tiles_m), within = lin % (kBand * tiles_m);
   const unsigned rows_in_band = min(kBand, tiles_n - band * kBand);
   const unsigned row0 = (band * kBand + within % rows_in_band) * G::BM, col0 = (within / rows_in_band) * G::BN;
@@ -170,9 +169,9 @@ __global__ __launch_bounds__(G::THREADS) void MM_KNAME(mfma_f16_kernel)(const _F
   {
     constexpr int ROWS = TM * 32;                       // rows of this wave's tile, 128 columns = 256 B each
     char *slice = smem + wave * (ROWS * 256);
-#if MM_SEEDED
-    {  // accumulate: C's tile enters the slice in the coalesced store layout (a lane reads the 16 bytes it later writes back),
-       // then every accumulator adds its own element in f32 -- the seed before the one rounding
+    if constexpr (F == Form::Seeded) {
+      // accumulate: C's tile enters the slice in the coalesced store layout (a lane reads the 16 bytes it later writes back),
+      // then every accumulator adds its own element in f32 -- the seed before the one rounding
       using u32x4 = __attribute__((ext_vector_type(4))) unsigned;
 #pragma unroll
       for (int it = 0; it < ROWS * 16 / 64; ++it) {
@@ -190,7 +189,6 @@ __global__ __launch_bounds__(G::THREADS) void MM_KNAME(mfma_f16_kernel)(const _F
           for (int rr = 0; rr < 16; ++rr)
           acc[mi][ni][rr] += (float)*(const _Float16 *)(slice + (mi * 32 + (rr & 3) + 8 * (rr >> 2) + 4 * hi) * 256 + (ni * 32 + lo) * 2);
     }
-#endif
 #pragma unroll
     for (int mi = 0; mi < TM; ++mi)
 #pragma unroll
@@ -210,7 +208,6 @@ __global__ __launch_bounds__(G::THREADS) void MM_KNAME(mfma_f16_kernel)(const _F
     }
   }
 }
-#if !MM_BATCHED
 
 
 // =================================================================================================
@@ -248,13 +245,13 @@ struct GeoPP {
 // one LDS-DMA piece: 64 lanes x 16 B from (uniform base + per-lane 32-bit offset) to LDS at m0
 #define MM_DMA_PIECE(vo, sb, la) "s_mov_b32 m0, " la "\n\ts_nop 0\n\tglobal_load_lds_dwordx4 " vo ", " sb "\n\t"
 
-#endif  // !MM_BATCHED
-template <bool AT>  // AT: A stored K x N (MM_TRANSPOSED_A): the A slab is staged and gathered exactly like B's
-__global__ __launch_bounds__(GeoPP::THREADS) void MM_KNAME(mfma_f16_pp_kernel)(const _Float16 *__restrict__ A,
+template <Form F, bool AT>  // AT: A stored K x N (MM_TRANSPOSED_A): the A slab is staged and gathered exactly like B's
+__global__ __launch_bounds__(GeoPP::THREADS) void mfma_f16_pp_kernel(const _Float16 *__restrict__ A,
                                                                        const _Float16 *__restrict__ B,
                                                                        _Float16 *__restrict__ C, unsigned N, unsigned K,
                                                                        unsigned M, unsigned tiles_n, unsigned tiles_m,
-                                                                       unsigned kBand MM_BATCH_PARAMS) {
+                                                                       unsigned kBand, unsigned batch, size_t stride_a,
+                                                                       size_t stride_b, size_t stride_c) {
   using G = GeoPP;
   constexpr int RB = 8, NB = 4;  // 16-row / 16-column blocks of a wavefront's 128 x 64 part (16x16x32 instruction, round 3)
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -266,7 +263,7 @@ __global__ __launch_bounds__(GeoPP::THREADS) void MM_KNAME(mfma_f16_pp_kernel)(c
   const unsigned l15 = lane & 15u, g = lane >> 4;
 
   const unsigned nwg = tiles_n * tiles_m;
-  const unsigned lin = MM_TILE_LIN(blockIdx.x, nwg);
+  const unsigned lin = form_tile<F>(A, B, C, nwg, batch, stride_a, stride_b, stride_c);
   const unsigned band = lin / (kBand * tiles_m), within = lin % (kBand * tiles_m);
   const unsigned rows_in_band = min(kBand, tiles_n - band * kBand);
   const unsigned row0 = (band * kBand + within % rows_in_band) * G::BM, col0 = (within / rows_in_band) * G::BN;
@@ -385,9 +382,9 @@ __global__ __launch_bounds__(GeoPP::THREADS) void MM_KNAME(mfma_f16_pp_kernel)(c
   //      (C/D of the 16x16 form: column l15, rows 4*g + i)
   {
     char *slice = smem + wave * (128 * 128);
-#if MM_SEEDED
-    {  // accumulate: C's tile enters the slice in the coalesced store layout (a lane reads the 16 bytes it later writes back),
-       // then every accumulator adds its own element in f32 -- the seed before the one rounding
+    if constexpr (F == Form::Seeded) {
+      // accumulate: C's tile enters the slice in the coalesced store layout (a lane reads the 16 bytes it later writes back),
+      // then every accumulator adds its own element in f32 -- the seed before the one rounding
       using u32x4 = __attribute__((ext_vector_type(4))) unsigned;
 #pragma unroll
       for (int it = 0; it < 128 * 8 / 64; ++it) {
@@ -405,7 +402,6 @@ __global__ __launch_bounds__(GeoPP::THREADS) void MM_KNAME(mfma_f16_pp_kernel)(c
           for (int i = 0; i < 4; ++i)
           acc[rb][nb][i] += (float)*(const _Float16 *)(slice + (rb * 16 + 4 * g + i) * 128 + (nb * 16 + l15) * 2);
     }
-#endif
 #pragma unroll
     for (int rb = 0; rb < RB; ++rb)
 #pragma unroll
@@ -423,7 +419,6 @@ __global__ __launch_bounds__(GeoPP::THREADS) void MM_KNAME(mfma_f16_pp_kernel)(c
     }
   }
 }
-#if !MM_BATCHED
 
 // -------------------------------------------------------------------------------------------------
 // Ping-pong with full-line A requests.  A 32-deep slab gives A rows of 64 bytes, i.e. TWO L2 requests per 128-byte
@@ -445,12 +440,13 @@ struct GeoPP2 {
   static constexpr int BROW = BN * 2;
 };
 
-#endif  // !MM_BATCHED
-__global__ __launch_bounds__(GeoPP2::THREADS) void MM_KNAME(mfma_f16_pp2_kernel)(const _Float16 *__restrict__ A,
+template <Form F>
+__global__ __launch_bounds__(GeoPP2::THREADS) void mfma_f16_pp2_kernel(const _Float16 *__restrict__ A,
                                                                          const _Float16 *__restrict__ B,
                                                                          _Float16 *__restrict__ C, unsigned N, unsigned K,
                                                                          unsigned M, unsigned tiles_n, unsigned tiles_m,
-                                                                         unsigned kBand MM_BATCH_PARAMS) {
+                                                                         unsigned kBand, unsigned batch, size_t stride_a,
+                                                                         size_t stride_b, size_t stride_c) {
   using G = GeoPP2;
   constexpr int TM = G::TM, TN = G::TN;
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -460,7 +456,7 @@ __global__ __launch_bounds__(GeoPP2::THREADS) void MM_KNAME(mfma_f16_pp2_kernel)
   const unsigned wm = wq >> 1, wn = (wq & 1u) * 2 + group;
   const unsigned lo = lane & 31u, hi = lane >> 5;
 
-  const unsigned lin = MM_TILE_LIN(blockIdx.x, tiles_n * tiles_m);
+  const unsigned lin = form_tile<F>(A, B, C, tiles_n * tiles_m, batch, stride_a, stride_b, stride_c);
   const unsigned band = lin / (kBand * tiles_m), within = lin % (kBand * tiles_m);
   const unsigned rows_in_band = min(kBand, tiles_n - band * kBand);
   const unsigned row0 = (band * kBand + within % rows_in_band) * G::BM, col0 = (within / rows_in_band) * G::BN;
@@ -596,9 +592,9 @@ __global__ __launch_bounds__(GeoPP2::THREADS) void MM_KNAME(mfma_f16_pp2_kernel)
 
   {
     char *slice = smem + wave * (128 * 128);
-#if MM_SEEDED
-    {  // accumulate: C's tile enters the slice in the coalesced store layout (a lane reads the 16 bytes it later writes back),
-       // then every accumulator adds its own element in f32 -- the seed before the one rounding
+    if constexpr (F == Form::Seeded) {
+      // accumulate: C's tile enters the slice in the coalesced store layout (a lane reads the 16 bytes it later writes back),
+      // then every accumulator adds its own element in f32 -- the seed before the one rounding
       using u32x4 = __attribute__((ext_vector_type(4))) unsigned;
 #pragma unroll
       for (int it = 0; it < 128 * 8 / 64; ++it) {
@@ -616,7 +612,6 @@ __global__ __launch_bounds__(GeoPP2::THREADS) void MM_KNAME(mfma_f16_pp2_kernel)
           for (int rr = 0; rr < 16; ++rr)
           acc[mi][ni][rr] += (float)*(const _Float16 *)(slice + (mi * 32 + (rr & 3) + 8 * (rr >> 2) + 4 * hi) * 128 + (ni * 32 + lo) * 2);
     }
-#endif
 #pragma unroll
     for (int mi = 0; mi < TM; ++mi)
 #pragma unroll
@@ -636,7 +631,6 @@ __global__ __launch_bounds__(GeoPP2::THREADS) void MM_KNAME(mfma_f16_pp2_kernel)
     }
   }
 }
-#if !MM_BATCHED
 
 // -------------------------------------------------------------------------------------------------
 // pingpong_16x16x32 (round 3, the default).  Same tile, LDS rings, DMA and segment
@@ -656,12 +650,13 @@ __global__ __launch_bounds__(GeoPP2::THREADS) void MM_KNAME(mfma_f16_pp2_kernel)
 //     half-wave touches fall into 8 different 32-byte octants of the 256-byte bank row.
 // Accumulation order per output element: k ascending in steps of 32, inside an MFMA the hardware's order;
 // results are within the same 1-ulp-of-binary16 bound as the 32x32x16 kernels (not bit-identical to them).
-#endif  // !MM_BATCHED
-__global__ __launch_bounds__(GeoPP2::THREADS) void MM_KNAME(mfma_f16_pp2s_kernel)(const _Float16 *__restrict__ A,
+template <Form F>
+__global__ __launch_bounds__(GeoPP2::THREADS) void mfma_f16_pp2s_kernel(const _Float16 *__restrict__ A,
                                                                           const _Float16 *__restrict__ B,
                                                                           _Float16 *__restrict__ C, unsigned N, unsigned K,
                                                                           unsigned M, unsigned tiles_n, unsigned tiles_m,
-                                                                          unsigned kBand MM_BATCH_PARAMS) {
+                                                                          unsigned kBand, unsigned batch, size_t stride_a,
+                                                                          size_t stride_b, size_t stride_c) {
   using G = GeoPP2;
   constexpr int RB = 8, NB = 4;  // 16-row / 16-column blocks of a wavefront's 128 x 64 part
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -671,7 +666,7 @@ __global__ __launch_bounds__(GeoPP2::THREADS) void MM_KNAME(mfma_f16_pp2s_kernel
   const unsigned wm = wq >> 1, wn = (wq & 1u) * 2 + group;
   const unsigned l15 = lane & 15u, g = lane >> 4;
 
-  const unsigned lin = MM_TILE_LIN(blockIdx.x, tiles_n * tiles_m);
+  const unsigned lin = form_tile<F>(A, B, C, tiles_n * tiles_m, batch, stride_a, stride_b, stride_c);
   const unsigned band = lin / (kBand * tiles_m), within = lin % (kBand * tiles_m);
   const unsigned rows_in_band = min(kBand, tiles_n - band * kBand);
   const unsigned row0 = (band * kBand + within % rows_in_band) * G::BM, col0 = (within / rows_in_band) * G::BN;
@@ -795,9 +790,9 @@ __global__ __launch_bounds__(GeoPP2::THREADS) void MM_KNAME(mfma_f16_pp2s_kernel
 
   {  // epilogue: C/D of the 16x16 form: column l15, rows 4*g + i
     char *slice = smem + wave * (128 * 128);
-#if MM_SEEDED
-    {  // accumulate: C's tile enters the slice in the coalesced store layout (a lane reads the 16 bytes it later writes back),
-       // then every accumulator adds its own element in f32 -- the seed before the one rounding
+    if constexpr (F == Form::Seeded) {
+      // accumulate: C's tile enters the slice in the coalesced store layout (a lane reads the 16 bytes it later writes back),
+      // then every accumulator adds its own element in f32 -- the seed before the one rounding
       using u32x4 = __attribute__((ext_vector_type(4))) unsigned;
 #pragma unroll
       for (int it = 0; it < 128 * 8 / 64; ++it) {
@@ -815,7 +810,6 @@ __global__ __launch_bounds__(GeoPP2::THREADS) void MM_KNAME(mfma_f16_pp2s_kernel
           for (int i = 0; i < 4; ++i)
           acc[rb][nb][i] += (float)*(const _Float16 *)(slice + (rb * 16 + 4 * g + i) * 128 + (nb * 16 + l15) * 2);
     }
-#endif
 #pragma unroll
     for (int rb = 0; rb < RB; ++rb)
 #pragma unroll
@@ -833,6 +827,3 @@ __global__ __launch_bounds__(GeoPP2::THREADS) void MM_KNAME(mfma_f16_pp2s_kernel
     }
   }
 }
-#undef MM_KNAME
-#undef MM_BATCH_PARAMS
-#undef MM_TILE_LIN

@@ -117,62 +117,36 @@ int launch_geo(hipStream_t s, const Problem &p, unsigned splits = 1) {
 }
 
 // Batched launches (mm_gemm_batched_*): `batch` copies of the whole-tile grid in one launch, as the split-K launch holds
-// `splits` copies -- the copies are the elements.  The XCD-remapped linear id is decomposed as (element, tile), so one
-// element's tiles stay contiguous in an XCD's chunk of the grid; the element index is uniform (SGPRs) and moves the A, B
-// and C bases before anything else.  Per element exactly mfma_f32_kernel's whole-tile arithmetic: the same bits.
-template <typename G, bool AT>
+// `splits` copies -- the copies are the elements (batched_tile, mm_common.h).  Per element exactly mfma_f32_kernel's
+// whole-tile arithmetic: the same bits.  SEED: the accumulating form (mm_gemm_*accumulate_*), C (+)= A B, C's value
+// entering in the tile's first write-back to C.
+template <typename G, bool AT, bool SEED>
 __global__ __launch_bounds__(G::THREADS, G::MIN_WAVES) void mfma_f32_batched_kernel(
     const float *__restrict__ A, const float *__restrict__ B, float *__restrict__ C, unsigned N, unsigned K, unsigned M,
     unsigned tiles_n, unsigned tiles_m, unsigned kBand, unsigned batch, size_t stride_a, size_t stride_b, size_t stride_c) {
-  const unsigned nwg = tiles_n * tiles_m;
-  const unsigned g = xcd_remap(blockIdx.x, nwg * batch), e = g / nwg;
-  A += e * stride_a;
-  B += e * stride_b;
-  C += e * stride_c;
-  const unsigned lin = g - e * nwg;
+  const unsigned lin = batched_tile(A, B, C, tiles_n * tiles_m, batch, stride_a, stride_b, stride_c);
   const unsigned band = lin / (kBand * tiles_m), within = lin % (kBand * tiles_m);
   const unsigned rows_in_band = min(kBand, tiles_n - band * kBand);
   const unsigned tile_row = band * kBand + within % rows_in_band;
   const unsigned tile_col = within / rows_in_band;
-  tile_body<G, AT>(A, B, C, N, K, M, K, M, N, M, tile_row * G::BM, tile_col * G::BN);
+  tile_body<G, AT, false, SEED>(A, B, C, N, K, M, K, M, N, M, tile_row * G::BM, tile_col * G::BN);
 }
 
-// The accumulating form (mm_gemm_*accumulate_*): C (+)= A B, C's value entering in the tile's first write-back to C.  A
-// copy of the kernel above rather than a shared body, so that the unseeded kernel keeps its machine code to the bit.
-template <typename G, bool AT>
-__global__ __launch_bounds__(G::THREADS, G::MIN_WAVES) void mfma_f32_batched_seeded_kernel(
-    const float *__restrict__ A, const float *__restrict__ B, float *__restrict__ C, unsigned N, unsigned K, unsigned M,
-    unsigned tiles_n, unsigned tiles_m, unsigned kBand, unsigned batch, size_t stride_a, size_t stride_b, size_t stride_c) {
-  const unsigned nwg = tiles_n * tiles_m;
-  const unsigned g = xcd_remap(blockIdx.x, nwg * batch), e = g / nwg;
-  A += e * stride_a;
-  B += e * stride_b;
-  C += e * stride_c;
-  const unsigned lin = g - e * nwg;
-  const unsigned band = lin / (kBand * tiles_m), within = lin % (kBand * tiles_m);
-  const unsigned rows_in_band = min(kBand, tiles_n - band * kBand);
-  const unsigned tile_row = band * kBand + within % rows_in_band;
-  const unsigned tile_col = within / rows_in_band;
-  tile_body<G, AT, false, true>(A, B, C, N, K, M, K, M, N, M, tile_row * G::BM, tile_col * G::BN);
+template <typename G, bool AT, bool SEED>
+int launch_geo_batched_seed(hipStream_t s, const Problem &p) {
+  const unsigned tiles_n = (p.n + G::BM - 1) / G::BM, tiles_m = (p.m + G::BN - 1) / G::BN;
+  static unsigned long long configured = 0;   // one per instantiation of this function, so one per kernel
+  (void)hipGetLastError();
+  if (int e = ensure_dynamic_lds((const void *)mfma_f32_batched_kernel<G, AT, SEED>, G::LDS_BYTES, configured)) return e;
+  hipLaunchKernelGGL((mfma_f32_batched_kernel<G, AT, SEED>), dim3(tiles_n * tiles_m * p.batch), dim3(G::THREADS), G::LDS_BYTES,
+                     s, (const float *)p.a, (const float *)p.b, (float *)p.c, p.n, p.k, p.m, tiles_n, tiles_m,
+                     band_rows(G::BM, G::BN, G::MIN_WAVES), p.batch, p.stride_a, p.stride_b, p.stride_c);
+  return (int)hipGetLastError();
 }
 
 template <typename G, bool AT = false>
 int launch_geo_batched(hipStream_t s, const Problem &p) {
-  const unsigned tiles_n = (p.n + G::BM - 1) / G::BM, tiles_m = (p.m + G::BN - 1) / G::BN;
-  static unsigned long long configured = 0, configured_seeded = 0;
-  (void)hipGetLastError();
-  if (p.seed) {
-    if (int e = ensure_dynamic_lds((const void *)mfma_f32_batched_seeded_kernel<G, AT>, G::LDS_BYTES, configured_seeded)) return e;
-    hipLaunchKernelGGL((mfma_f32_batched_seeded_kernel<G, AT>), dim3(tiles_n * tiles_m * p.batch), dim3(G::THREADS), G::LDS_BYTES,
-                       s, (const float *)p.a, (const float *)p.b, (float *)p.c, p.n, p.k, p.m, tiles_n, tiles_m,
-                       band_rows(G::BM, G::BN, G::MIN_WAVES), p.batch, p.stride_a, p.stride_b, p.stride_c);
-    return (int)hipGetLastError();
-  }
-  if (int e = ensure_dynamic_lds((const void *)mfma_f32_batched_kernel<G, AT>, G::LDS_BYTES, configured)) return e;
-  hipLaunchKernelGGL((mfma_f32_batched_kernel<G, AT>), dim3(tiles_n * tiles_m * p.batch), dim3(G::THREADS), G::LDS_BYTES, s,
-                     (const float *)p.a, (const float *)p.b, (float *)p.c, p.n, p.k, p.m, tiles_n, tiles_m,
-                     band_rows(G::BM, G::BN, G::MIN_WAVES), p.batch, p.stride_a, p.stride_b, p.stride_c);
-  return (int)hipGetLastError();
+  return p.seed ? launch_geo_batched_seed<G, AT, true>(s, p) : launch_geo_batched_seed<G, AT, false>(s, p);
 }
 
 // The geometries of the product.  Every shipped geometry exists as a (ScalarBase, VectorAddress) pair with identical

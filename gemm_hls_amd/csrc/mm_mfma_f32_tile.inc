@@ -58,7 +58,7 @@ struct Geo {
 // One k-range of one output tile: A / B point at the first k of the range (row stride of A: lda), K = its length, the
 // result goes to Cst[row * ldc + col] for rows < Nst, cols < Mst.  For a whole tile of C that is (C, M, N, M); a partial
 // tile of a stream-K launch targets a 128 x 128 scratch slot instead (ldc = 128, no limits).
-// SEED (accumulate, the *_batched_seeded kernels): C's value enters the first write-back to C, the chain flush into C's own
+// SEED (accumulate, mfma_f32_batched_kernel<G, AT, true>): C's value enters the first write-back to C, the chain flush into C's own
 // read-modify-write (FlushIntoC geometries only): the tile behaves as if an earlier chunk had already been flushed there.
 template <typename G, bool AT, bool AGENT_STORES = false, bool SEED = false>
 __device__ __forceinline__ void tile_body(const float *__restrict__ A, const float *__restrict__ B, float *__restrict__ Cst,

@@ -48,15 +48,7 @@ struct GeoD {
   static_assert(LDS_BYTES <= 160 * 1024, "LDS");
 };
 
-#define MM_BATCHED 0
 #include "mm_mfma_f64_kernels.inc"
-#undef MM_BATCHED
-#define MM_BATCHED 1
-#include "mm_mfma_f64_kernels.inc"
-#define MM_SEEDED 1
-#include "mm_mfma_f64_kernels.inc"
-#undef MM_SEEDED
-#undef MM_BATCHED
 
 using D0 = GeoD<4, 2, 2>;  // 256 x 128 tile, 8 wavefronts (2 per SIMD), 96 KiB LDS
 using D1 = GeoD<2, 2, 2>;  // 128 x 128 tile, 4 wavefronts, 64 KiB LDS: two workgroups per CU (small / mid-size shapes)
@@ -73,41 +65,23 @@ bool mfma_f64_serves(const Problem &p) {
   return !p.a_transposed || (p.n >= 2 && p.n % 2 == 0);
 }
 
-// BATCHED: the p.batch elements of p (strides p.stride_*) in one launch of mfma_f64_kernel_batched (p.seed: _batched_seeded)
-template <typename G, bool BATCHED = false>
-static int launch_d(hipStream_t s, const Problem &p) {
+// One launch of mfma_f64_kernel<F, G, AT>: the problem at (a, b, c), or (F != Form::Single) the p.batch elements of p
+template <Form F, typename G, bool AT>
+static int launch_at(hipStream_t s, const Problem &p) {
   const unsigned tiles_n = (p.n + G::BM - 1) / G::BM, tiles_m = (p.m + G::BN - 1) / G::BN;
-  const unsigned grid = tiles_n * tiles_m * (BATCHED ? p.batch : 1u);
+  const unsigned grid = tiles_n * tiles_m * (F == Form::Single ? 1u : p.batch);
   const unsigned band = band_rows(G::BM, G::BN, G::BM * G::BN <= 64 * 64 ? 4 : G::BM * G::BN <= 128 * 128 ? 2 : 1);
-  static unsigned long long configured = 0, configured_at = 0, configured_seeded = 0, configured_seeded_at = 0;
-#define MM_F64_LAUNCH(AT)                                                                                                        \
-  do {                                                                                                                           \
-    if constexpr (BATCHED) {                                                                                                     \
-      if (p.seed) {                                                                                                              \
-        if (int e = ensure_dynamic_lds((const void *)mfma_f64_kernel_batched_seeded<G, AT>, G::LDS_BYTES,                       \
-                                       AT ? configured_seeded_at : configured_seeded))                                           \
-          return e;                                                                                                              \
-        hipLaunchKernelGGL((mfma_f64_kernel_batched_seeded<G, AT>), dim3(grid), dim3(G::THREADS), G::LDS_BYTES, s,              \
-                           (const double *)p.a, (const double *)p.b, (double *)p.c, p.n, p.k, p.m, tiles_n, tiles_m, band,      \
-                           p.batch, p.stride_a, p.stride_b, p.stride_c);                                                        \
-        break;                                                                                                                   \
-      }                                                                                                                          \
-      if (int e = ensure_dynamic_lds((const void *)mfma_f64_kernel_batched<G, AT>, G::LDS_BYTES, AT ? configured_at : configured)) \
-        return e;                                                                                                                \
-      hipLaunchKernelGGL((mfma_f64_kernel_batched<G, AT>), dim3(grid), dim3(G::THREADS), G::LDS_BYTES, s, (const double *)p.a, \
-                         (const double *)p.b, (double *)p.c, p.n, p.k, p.m, tiles_n, tiles_m, band, p.batch, p.stride_a,        \
-                         p.stride_b, p.stride_c);                                                                               \
-    } else {                                                                                                                     \
-      if (int e = ensure_dynamic_lds((const void *)mfma_f64_kernel<G, AT>, G::LDS_BYTES, AT ? configured_at : configured))    \
-        return e;                                                                                                                \
-      hipLaunchKernelGGL((mfma_f64_kernel<G, AT>), dim3(grid), dim3(G::THREADS), G::LDS_BYTES, s, (const double *)p.a,         \
-                         (const double *)p.b, (double *)p.c, p.n, p.k, p.m, tiles_n, tiles_m, band);                            \
-    }                                                                                                                            \
-  } while (0)
-  if (p.a_transposed) MM_F64_LAUNCH(true);
-  else MM_F64_LAUNCH(false);
-#undef MM_F64_LAUNCH
+  static unsigned long long configured = 0;   // one per instantiation of this function, so one per kernel
+  if (int e = ensure_dynamic_lds((const void *)mfma_f64_kernel<F, G, AT>, G::LDS_BYTES, configured)) return e;
+  hipLaunchKernelGGL((mfma_f64_kernel<F, G, AT>), dim3(grid), dim3(G::THREADS), G::LDS_BYTES, s, (const double *)p.a,
+                     (const double *)p.b, (double *)p.c, p.n, p.k, p.m, tiles_n, tiles_m, band,
+                     F == Form::Single ? 1u : p.batch, p.stride_a, p.stride_b, p.stride_c);
   return (int)hipGetLastError();
+}
+
+template <Form F, typename G>
+static int launch_d(hipStream_t s, const Problem &p) {
+  return p.a_transposed ? launch_at<F, G, true>(s, p) : launch_at<F, G, false>(s, p);
 }
 
 int mfma_f64_tile(const Problem &p) {  // 0: 256x128, 1: 128x128, 4: 64x64
@@ -140,30 +114,26 @@ const char *mfma_f64_name(const Problem &p) {
   return r < 0 ? "unsupported" : names[r];
 }
 
-// Batched (mm_gemm_batched_*): the same resolver on the whole batch (Problem::batch copies of the tile grid; every f64
-// geometry gives the same bits), the kernels' *_batched forms; no workspace is involved in any f64 launch.
-int mfma_f64_batched_resolve(const Problem &p) { return resolve(p); }
-const char *mfma_f64_batched_name(const Problem &p) { return mfma_f64_name(p); }
-int launch_mfma_f64_batched(hipStream_t s, const Problem &p, int r) {
+template <Form F>
+static int launch_resolved(hipStream_t s, const Problem &p, int r) {   // r: resolve()'s answer
   switch (r) {
-    case 0: return launch_d<D0, true>(s, p);
-    case 1: return launch_d<D1, true>(s, p);
-    case 2: return launch_d<D0R1, true>(s, p);
-    case 3: return launch_d<D1R1, true>(s, p);
-    case 4: return launch_d<DS, true>(s, p);
+    case 0: return launch_d<F, D0>(s, p);
+    case 1: return launch_d<F, D1>(s, p);
+    case 2: return launch_d<F, D0R1>(s, p);
+    case 3: return launch_d<F, D1R1>(s, p);
+    case 4: return launch_d<F, DS>(s, p);
   }
   return kErrNotSupported;
 }
 
-int launch_mfma_f64(hipStream_t s, const Problem &p) {
-  switch (resolve(p)) {
-    case 0: return launch_d<D0>(s, p);
-    case 1: return launch_d<D1>(s, p);
-    case 2: return launch_d<D0R1>(s, p);
-    case 3: return launch_d<D1R1>(s, p);
-    case 4: return launch_d<DS>(s, p);
-  }
-  return kErrNotSupported;
+// Batched (mm_gemm_batched_*): the same resolver on the whole batch (Problem::batch copies of the tile grid; every f64
+// geometry gives the same bits), the kernels' batched forms (Form::Seeded for p.seed); no workspace is involved in any f64 launch.
+int mfma_f64_batched_resolve(const Problem &p) { return resolve(p); }
+const char *mfma_f64_batched_name(const Problem &p) { return mfma_f64_name(p); }
+int launch_mfma_f64_batched(hipStream_t s, const Problem &p, int r) {
+  return p.seed ? launch_resolved<Form::Seeded>(s, p, r) : launch_resolved<Form::Batched>(s, p, r);
 }
+
+int launch_mfma_f64(hipStream_t s, const Problem &p) { return launch_resolved<Form::Single>(s, p, resolve(p)); }
 
 }  // namespace mm

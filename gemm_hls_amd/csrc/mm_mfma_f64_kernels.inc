@@ -1,13 +1,13 @@
-// The kernels of mm_mfma_f64.hip, compiled three times by it: MM_BATCHED 0 the single-problem kernels, 1 their *_batched twins,
-// and MM_BATCHED 1 with MM_SEEDED 1 the *_batched_seeded forms that accumulate into C (mm_batched_kernel.h).  Definitions that are not kernels appear in the first pass only.
-#include "mm_batched_kernel.h"
-template <typename G, bool AT>
-__global__ __launch_bounds__(G::THREADS, G::MIN_WAVES) void MM_KNAME(mfma_f64_kernel)(  // 2 wavefronts per SIMD: <= 256 VGPRs, so that the
+// The kernel of mm_mfma_f64.hip.  F (mm_common.h): the single-problem kernel, its strided-batched form, or the batched form
+// that accumulates into C.
+template <Form F, typename G, bool AT>
+__global__ __launch_bounds__(G::THREADS, G::MIN_WAVES) void mfma_f64_kernel(  // 2 wavefronts per SIMD: <= 256 VGPRs, so that the
                                                                    // 4-wavefront geometry really fits twice on a CU
     const double *__restrict__ A,
                                                               const double *__restrict__ B,
                                                               double *__restrict__ C, unsigned N, unsigned K,
-                                                              unsigned M, unsigned tiles_n, unsigned tiles_m, unsigned kBand MM_BATCH_PARAMS) {
+                                                              unsigned M, unsigned tiles_n, unsigned tiles_m, unsigned kBand, unsigned batch,
+                                                              size_t stride_a, size_t stride_b, size_t stride_c) {
   constexpr int TM = G::TM, TP = G::TP, BK = G::BK, NS = G::NS, CPR = G::CPR;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const unsigned lane = threadIdx.x & 63u;
@@ -16,7 +16,7 @@ __global__ __launch_bounds__(G::THREADS, G::MIN_WAVES) void MM_KNAME(mfma_f64_ke
   const unsigned lo = lane & 15u, g4 = lane >> 4;
 
   const unsigned nwg = tiles_n * tiles_m;
-  const unsigned lin = MM_TILE_LIN(blockIdx.x, nwg);
+  const unsigned lin = form_tile<F>(A, B, C, nwg, batch, stride_a, stride_b, stride_c);
   const unsigned band = lin / (kBand * tiles_m), within = lin % (kBand * tiles_m);
   const unsigned rows_in_band = min(kBand, tiles_n - band * kBand);
   const unsigned row0 = (band * kBand + within % rows_in_band) * G::BM, col0 = (within / rows_in_band) * G::BN;
@@ -270,14 +270,10 @@ __global__ __launch_bounds__(G::THREADS, G::MIN_WAVES) void MM_KNAME(mfma_f64_ke
           f64x2 v;
           v[0] = acc[mi][pr][0][r];
           v[1] = acc[mi][pr][1][r];
-#if MM_SEEDED
-          v += *(const f64x2 *)(C + (size_t)row * M + ccol);   // accumulate: C's value enters here, read by the lane that writes it
-#endif
+          if constexpr (F == Form::Seeded)
+            v += *(const f64x2 *)(C + (size_t)row * M + ccol);   // accumulate: C's value enters here, read by the lane that writes it
           *(f64x2 *)(C + (size_t)row * M + ccol) = v;
         }
       }
   }
 }
-#undef MM_KNAME
-#undef MM_BATCH_PARAMS
-#undef MM_TILE_LIN

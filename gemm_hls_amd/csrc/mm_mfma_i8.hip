@@ -72,22 +72,14 @@ __device__ __forceinline__ i32x4 join(v2i lo, v2i hi) {
   return r;
 }
 
-// Accumulate (the *_batched_seeded kernels): the seed plus the i32 sum, low 8 bits -- which only the low 8 bits of either
+// Accumulate (Form::Seeded): the seed plus the i32 sum, low 8 bits -- which only the low 8 bits of either
 // decide, so the two C images are added bytewise, mod 2^8 per byte (sign or zero extension of the seed does not matter).
 __device__ __forceinline__ __attribute__((ext_vector_type(4))) unsigned add_bytes(__attribute__((ext_vector_type(4))) unsigned x,
                                                                                  __attribute__((ext_vector_type(4))) unsigned y) {
   return ((x & 0x7f7f7f7fu) + (y & 0x7f7f7f7fu)) ^ ((x ^ y) & 0x80808080u);
 }
 
-#define MM_BATCHED 0
 #include "mm_mfma_i8_kernels.inc"
-#undef MM_BATCHED
-#define MM_BATCHED 1
-#include "mm_mfma_i8_kernels.inc"
-#define MM_SEEDED 1
-#include "mm_mfma_i8_kernels.inc"
-#undef MM_SEEDED
-#undef MM_BATCHED
 #undef MM_DMA_PIECE
 
 enum Kind { K_PP16, K_PP32, K_PPK64, K_PPK64_AT, K_SLAB128, K_SLAB128_AT, K_SLAB128_64, K_NONE };
@@ -146,36 +138,40 @@ static Kind resolve(const Problem &p) {
 
 const char *mfma_i8_name(const Problem &p) { return kNames[resolve(p)]; }
 
-template <typename Kern>
-static int launch_tile(hipStream_t s, const Problem &p, Kern kern, unsigned threads, int lds, unsigned long long &configured,
-                       unsigned bm = 256) {
+// One launch of the kernel KERN, an instantiation for form F: the problem at (a, b, c), or (F != Form::Single) p.batch copies of
+// the tile grid over the elements of p
+template <Form F, auto KERN>
+static int launch_tile(hipStream_t s, const Problem &p, unsigned threads, int lds, unsigned bm = 256) {
   const unsigned tiles_n = (p.n + bm - 1) / bm, tiles_m = (p.m + 255) / 256;
-  if (int e = ensure_dynamic_lds((const void *)kern, lds, configured)) return e;
-  hipLaunchKernelGGL(kern, dim3(tiles_n * tiles_m), dim3(threads), lds, s, (const signed char *)p.a, (const signed char *)p.b,
-                     (signed char *)p.c, p.n, p.k, p.m, tiles_n, tiles_m, band_rows(bm, 256, 1));
+  static unsigned long long configured = 0;   // one per instantiation of this function, so one per kernel
+  if (int e = ensure_dynamic_lds((const void *)KERN, lds, configured)) return e;
+  hipLaunchKernelGGL(KERN, dim3(tiles_n * tiles_m * (F == Form::Single ? 1u : p.batch)), dim3(threads), lds, s,
+                     (const signed char *)p.a, (const signed char *)p.b, (signed char *)p.c, p.n, p.k, p.m, tiles_n, tiles_m,
+                     band_rows(bm, 256, 1), F == Form::Single ? 1u : p.batch, p.stride_a, p.stride_b, p.stride_c);
   return (int)hipGetLastError();
 }
 
-// the batched kernels' launch: p.batch copies of the tile grid, the element strides after the single kernel's arguments
-template <typename Kern>
-static int launch_tile_batched(hipStream_t s, const Problem &p, Kern kern, unsigned threads, int lds, unsigned long long &configured,
-                       unsigned bm = 256) {
-  const unsigned tiles_n = (p.n + bm - 1) / bm, tiles_m = (p.m + 255) / 256;
-  if (int e = ensure_dynamic_lds((const void *)kern, lds, configured)) return e;
-  hipLaunchKernelGGL(kern, dim3(tiles_n * tiles_m * p.batch), dim3(threads), lds, s, (const signed char *)p.a, (const signed char *)p.b,
-                     (signed char *)p.c, p.n, p.k, p.m, tiles_n, tiles_m, band_rows(bm, 256, 1), p.batch, p.stride_a, p.stride_b, p.stride_c);
-  return (int)hipGetLastError();
+// The kernel of each Kind, in form F
+template <Form F>
+static int launch_kind(hipStream_t s, const Problem &p, Kind k) {
+  switch (k) {
+    case K_PP16: return launch_tile<F, mfma_i8_pp2s_kernel<F>>(s, p, GeoI8PP2::THREADS, GeoI8PP2::LDS_BYTES);
+    case K_PP32: return launch_tile<F, mfma_i8_pp2_kernel<F>>(s, p, GeoI8PP2::THREADS, GeoI8PP2::LDS_BYTES);
+    case K_PPK64: return launch_tile<F, mfma_i8_pp_kernel<F, false>>(s, p, GeoI8PP::THREADS, GeoI8PP::LDS_BYTES);
+    case K_PPK64_AT: return launch_tile<F, mfma_i8_pp_kernel<F, true>>(s, p, GeoI8PP::THREADS, GeoI8PP::LDS_BYTES);
+    case K_SLAB128: return launch_tile<F, mfma_i8_kernel<F, GeoI8, false>>(s, p, GeoI8::THREADS, GeoI8::LDS_BYTES);
+    case K_SLAB128_AT: return launch_tile<F, mfma_i8_kernel<F, GeoI8, true>>(s, p, GeoI8::THREADS, GeoI8::LDS_BYTES);
+    case K_SLAB128_64: return launch_tile<F, mfma_i8_kernel<F, GeoI8S, false>>(s, p, GeoI8S::THREADS, GeoI8S::LDS_BYTES, GeoI8S::BM);
+    default: return kErrNotSupported;
+  }
 }
 
 // A K x N A served where it lies (no workspace): the ping-pong K x N kernel where its shape rules allow, else slab128's
-static int launch_kxn_in_place(hipStream_t s, const Problem &p, unsigned long long (&cfg)[K_NONE]) {
-  if (tuning(TUNE_I8_VARIANT) != 0 && ppk64_serves(p))
-    return launch_tile(s, p, mfma_i8_pp_kernel<true>, GeoI8PP::THREADS, GeoI8PP::LDS_BYTES, cfg[K_PPK64_AT]);
-  return launch_tile(s, p, mfma_i8_kernel<GeoI8, true>, GeoI8::THREADS, GeoI8::LDS_BYTES, cfg[K_SLAB128_AT]);
+static int launch_kxn_in_place(hipStream_t s, const Problem &p) {
+  return launch_kind<Form::Single>(s, p, tuning(TUNE_I8_VARIANT) != 0 && ppk64_serves(p) ? K_PPK64_AT : K_SLAB128_AT);
 }
 
 int launch_mfma_i8(hipStream_t s, const Problem &p) {
-  static unsigned long long cfg[K_NONE] = {};
   if (transposes_first(p)) {
     int dev = 0;
     hipError_t e = hipGetDevice(&dev);
@@ -187,7 +183,7 @@ int launch_mfma_i8(hipStream_t s, const Problem &p) {
       // no room for the N x K copy (up to 4 GiB next to a nearly full device): not an error -- the K x N kernels serve the
       // call without extra memory, as they did before the pre-pass existed; same contract, ~2-3 % slower
       (void)hipGetLastError();
-      return launch_kxn_in_place(s, p, cfg);
+      return launch_kxn_in_place(s, p);
     }
     int rc = launch_transpose_kxn(s, p.a, an, p.k, p.n, 1);
     if (rc == 0) {
@@ -199,19 +195,8 @@ int launch_mfma_i8(hipStream_t s, const Problem &p) {
     const hipError_t f = hipFreeAsync(an, s);
     return rc ? rc : (int)f;
   }
-  const Kind k = resolve(p);
-  switch (k) {
-    case K_PP16: return launch_tile(s, p, mfma_i8_pp2s_kernel, GeoI8PP2::THREADS, GeoI8PP2::LDS_BYTES, cfg[k]);
-    case K_PP32: return launch_tile(s, p, mfma_i8_pp2_kernel, GeoI8PP2::THREADS, GeoI8PP2::LDS_BYTES, cfg[k]);
-    case K_PPK64: return launch_tile(s, p, mfma_i8_pp_kernel<false>, GeoI8PP::THREADS, GeoI8PP::LDS_BYTES, cfg[k]);
-    case K_PPK64_AT: return launch_tile(s, p, mfma_i8_pp_kernel<true>, GeoI8PP::THREADS, GeoI8PP::LDS_BYTES, cfg[k]);
-    case K_SLAB128: return launch_tile(s, p, mfma_i8_kernel<GeoI8, false>, GeoI8::THREADS, GeoI8::LDS_BYTES, cfg[k]);
-    case K_SLAB128_AT: return launch_tile(s, p, mfma_i8_kernel<GeoI8, true>, GeoI8::THREADS, GeoI8::LDS_BYTES, cfg[k]);
-    case K_SLAB128_64: return launch_tile(s, p, mfma_i8_kernel<GeoI8S, false>, GeoI8S::THREADS, GeoI8S::LDS_BYTES, cfg[k], GeoI8S::BM);
-    default: return kErrNotSupported;
-  }
+  return launch_kind<Form::Single>(s, p, resolve(p));
 }
-
 
 // Batched (mm_gemm_batched_*): whole tiles of the in-place kernels, decided on the whole batch (Problem::batch copies of the
 // tile grid).  The instruction schedule -- and with it the bits -- depends on the element's shape only: where a ping-pong
@@ -227,25 +212,9 @@ static Kind resolve_batched(const Problem &p) {
 int mfma_i8_batched_resolve(const Problem &p) { const Kind k = resolve_batched(p); return k == K_NONE ? -1 : (int)k; }
 const char *mfma_i8_batched_name(const Problem &p) { return kNames[resolve_batched(p)]; }
 int launch_mfma_i8_batched(hipStream_t s, const Problem &p, int kind) {
-  static unsigned long long bcfg[K_NONE] = {}, scfg[K_NONE] = {};
   if (kind < 0 || kind >= (int)K_NONE) return kErrNotSupported;
-  const Kind k = (Kind)kind;
-  // SUF: _batched, or _batched_seeded for an accumulating launch (p.seed) -- the same kernel with C's value in its epilogue
-#define MM_I8_BATCHED(SUF, CFG)                                                                                                        \
-  switch (k) {                                                                                                                         \
-    case K_PP16: return launch_tile_batched(s, p, mfma_i8_pp2s_kernel##SUF, GeoI8PP2::THREADS, GeoI8PP2::LDS_BYTES, CFG[k]);          \
-    case K_PP32: return launch_tile_batched(s, p, mfma_i8_pp2_kernel##SUF, GeoI8PP2::THREADS, GeoI8PP2::LDS_BYTES, CFG[k]);           \
-    case K_PPK64: return launch_tile_batched(s, p, mfma_i8_pp_kernel##SUF<false>, GeoI8PP::THREADS, GeoI8PP::LDS_BYTES, CFG[k]);      \
-    case K_PPK64_AT: return launch_tile_batched(s, p, mfma_i8_pp_kernel##SUF<true>, GeoI8PP::THREADS, GeoI8PP::LDS_BYTES, CFG[k]);    \
-    case K_SLAB128: return launch_tile_batched(s, p, mfma_i8_kernel##SUF<GeoI8, false>, GeoI8::THREADS, GeoI8::LDS_BYTES, CFG[k]);    \
-    case K_SLAB128_AT: return launch_tile_batched(s, p, mfma_i8_kernel##SUF<GeoI8, true>, GeoI8::THREADS, GeoI8::LDS_BYTES, CFG[k]);  \
-    case K_SLAB128_64:                                                                                                                 \
-      return launch_tile_batched(s, p, mfma_i8_kernel##SUF<GeoI8S, false>, GeoI8S::THREADS, GeoI8S::LDS_BYTES, CFG[k], GeoI8S::BM);  \
-    default: return kErrNotSupported;                                                                                                  \
-  }
-  if (p.seed) MM_I8_BATCHED(_batched_seeded, scfg)
-  MM_I8_BATCHED(_batched, bcfg)
-#undef MM_I8_BATCHED
+  // an accumulating launch (p.seed): the same kernel with C's value in its epilogue
+  return p.seed ? launch_kind<Form::Seeded>(s, p, (Kind)kind) : launch_kind<Form::Batched>(s, p, (Kind)kind);
 }
 
 }  // namespace mm

@@ -1,13 +1,12 @@
-// The kernels of mm_mfma_i8.hip, compiled three times by it: MM_BATCHED 0 the single-problem kernels, 1 their *_batched twins,
-// MM_BATCHED 1 with MM_SEEDED 1 the *_batched_seeded forms that accumulate into C
-// (mm_batched_kernel.h).  Definitions that are not kernels appear in the first pass only.
-#include "mm_batched_kernel.h"
-template <typename G, bool AT>
-__global__ __launch_bounds__(G::THREADS) void MM_KNAME(mfma_i8_kernel)(const signed char *__restrict__ A,
+// The kernels of mm_mfma_i8.hip.  F (mm_common.h) is the form of each: the single-problem kernel, its strided-batched form,
+// or the batched form that accumulates into C.
+template <Form F, typename G, bool AT>
+__global__ __launch_bounds__(G::THREADS) void mfma_i8_kernel(const signed char *__restrict__ A,
                                                                  const signed char *__restrict__ B,
                                                                  signed char *__restrict__ C, unsigned N, unsigned K,
                                                                  unsigned M, unsigned tiles_n, unsigned tiles_m,
-                                                                 unsigned kBand MM_BATCH_PARAMS) {
+                                                                 unsigned kBand, unsigned batch, size_t stride_a,
+                                                                 size_t stride_b, size_t stride_c) {
   constexpr int TM = G::TM, TN = G::TN, BK = G::BK, NS = G::NS, CPR = G::CPR;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const unsigned lane = threadIdx.x & 63u;
@@ -15,7 +14,7 @@ __global__ __launch_bounds__(G::THREADS) void MM_KNAME(mfma_i8_kernel)(const sig
   const unsigned wm = wave / G::WN, wn = wave % G::WN;
   const unsigned lo = lane & 31u, hi = lane >> 5;
 
-  const unsigned lin = MM_TILE_LIN(blockIdx.x, tiles_n * tiles_m);
+  const unsigned lin = form_tile<F>(A, B, C, tiles_n * tiles_m, batch, stride_a, stride_b, stride_c);
   const unsigned band = lin / (kBand * tiles_m), within = lin % (kBand * tiles_m);
   const unsigned rows_in_band = min(kBand, tiles_n - band * kBand);
   const unsigned row0 = (band * kBand + within % rows_in_band) * G::BM, col0 = (within / rows_in_band) * G::BN;
@@ -175,18 +174,17 @@ __global__ __launch_bounds__(G::THREADS) void MM_KNAME(mfma_i8_kernel)(const sig
       const unsigned c = it * 64 + lane, row = c / 8, ch = c % 8;
       const u32x4 v = *(const u32x4 *)(slice + row * 128 + ch * 16);
       const unsigned grow = row0 + wm * ROWS + row, gcol = col0 + wn * 128 + ch * 16;
-#if MM_SEEDED
-      if (grow < N && gcol < M) {   // accumulate: low 8 bits of seed + sum, bytewise; the lane reads what it then writes
-        u32x4 *dst = (u32x4 *)(C + (size_t)grow * M + gcol);
-        *dst = add_bytes(v, *dst);
+      if constexpr (F == Form::Seeded) {
+        if (grow < N && gcol < M) {   // accumulate: low 8 bits of seed + sum, bytewise; the lane reads what it then writes
+          u32x4 *dst = (u32x4 *)(C + (size_t)grow * M + gcol);
+          *dst = add_bytes(v, *dst);
+        }
+      } else {
+        if (grow < N && gcol < M) *(u32x4 *)(C + (size_t)grow * M + gcol) = v;
       }
-#else
-      if (grow < N && gcol < M) *(u32x4 *)(C + (size_t)grow * M + gcol) = v;
-#endif
     }
   }
 }
-#if !MM_BATCHED
 
 
 // =================================================================================================
@@ -205,13 +203,13 @@ struct GeoI8PP {
 };
 #define MM_DMA_PIECE(vo, sb, la) "s_mov_b32 m0, " la "\n\ts_nop 0\n\tglobal_load_lds_dwordx4 " vo ", " sb "\n\t"
 
-#endif  // !MM_BATCHED
-template <bool AT>  // AT: A stored K x N, staged and gathered like B
-__global__ __launch_bounds__(GeoI8PP::THREADS) void MM_KNAME(mfma_i8_pp_kernel)(const signed char *__restrict__ A,
+template <Form F, bool AT>  // AT: A stored K x N, staged and gathered like B
+__global__ __launch_bounds__(GeoI8PP::THREADS) void mfma_i8_pp_kernel(const signed char *__restrict__ A,
                                                                         const signed char *__restrict__ B,
                                                                         signed char *__restrict__ C, unsigned N, unsigned K,
                                                                         unsigned M, unsigned tiles_n, unsigned tiles_m,
-                                                                        unsigned kBand MM_BATCH_PARAMS) {
+                                                                        unsigned kBand, unsigned batch, size_t stride_a,
+                                                                        size_t stride_b, size_t stride_c) {
   // pingpong_k64 on v_mfma_i32_16x16x64_i8 since round 3 (one 64-deep slab = one MFMA k; the 32x32x32 edition is in the lab)
   using G = GeoI8PP;
   constexpr int RB = 8, NB = 4;
@@ -222,7 +220,7 @@ __global__ __launch_bounds__(GeoI8PP::THREADS) void MM_KNAME(mfma_i8_pp_kernel)(
   const unsigned wm = wq >> 1, wn = (wq & 1u) * 2 + group;
   const unsigned l15 = lane & 15u, g = lane >> 4;
 
-  const unsigned lin = MM_TILE_LIN(blockIdx.x, tiles_n * tiles_m);
+  const unsigned lin = form_tile<F>(A, B, C, tiles_n * tiles_m, batch, stride_a, stride_b, stride_c);
   const unsigned band = lin / (kBand * tiles_m), within = lin % (kBand * tiles_m);
   const unsigned rows_in_band = min(kBand, tiles_n - band * kBand);
   const unsigned row0 = (band * kBand + within % rows_in_band) * G::BM, col0 = (within / rows_in_band) * G::BN;
@@ -342,18 +340,17 @@ __global__ __launch_bounds__(GeoI8PP::THREADS) void MM_KNAME(mfma_i8_pp_kernel)(
       const unsigned c = it * 64 + lane, row = c / 4, ch = c % 4;
       const u32x4 v = *(const u32x4 *)(slice + row * 64 + ch * 16);
       const unsigned grow = row0 + wm * 128 + row, gcol = col0 + wn * 64 + ch * 16;
-#if MM_SEEDED
-      if (grow < N && gcol < M) {   // accumulate: low 8 bits of seed + sum, bytewise; the lane reads what it then writes
-        u32x4 *dst = (u32x4 *)(C + (size_t)grow * M + gcol);
-        *dst = add_bytes(v, *dst);
+      if constexpr (F == Form::Seeded) {
+        if (grow < N && gcol < M) {   // accumulate: low 8 bits of seed + sum, bytewise; the lane reads what it then writes
+          u32x4 *dst = (u32x4 *)(C + (size_t)grow * M + gcol);
+          *dst = add_bytes(v, *dst);
+        }
+      } else {
+        if (grow < N && gcol < M) *(u32x4 *)(C + (size_t)grow * M + gcol) = v;
       }
-#else
-      if (grow < N && gcol < M) *(u32x4 *)(C + (size_t)grow * M + gcol) = v;
-#endif
     }
   }
 }
-#if !MM_BATCHED
 
 // Ping-pong with full-line A requests (see mfma_f16_pp2_kernel in mm_mfma_f16.hip): A staged in
 // double slabs [256 rows][128 B] (ring of 3 x 32 KiB, chunk ^ (row>>1)&7), B in 64-deep slabs (ring of
@@ -366,12 +363,13 @@ struct GeoI8PP2 {
   static constexpr int BROW = BN;
 };
 
-#endif  // !MM_BATCHED
-__global__ __launch_bounds__(GeoI8PP2::THREADS) void MM_KNAME(mfma_i8_pp2_kernel)(const signed char *__restrict__ A,
+template <Form F>
+__global__ __launch_bounds__(GeoI8PP2::THREADS) void mfma_i8_pp2_kernel(const signed char *__restrict__ A,
                                                                          const signed char *__restrict__ B,
                                                                          signed char *__restrict__ C, unsigned N, unsigned K,
                                                                          unsigned M, unsigned tiles_n, unsigned tiles_m,
-                                                                         unsigned kBand MM_BATCH_PARAMS) {
+                                                                         unsigned kBand, unsigned batch, size_t stride_a,
+                                                                         size_t stride_b, size_t stride_c) {
   using G = GeoI8PP2;
   constexpr int TM = G::TM, TN = G::TN;
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -381,7 +379,7 @@ __global__ __launch_bounds__(GeoI8PP2::THREADS) void MM_KNAME(mfma_i8_pp2_kernel
   const unsigned wm = wq >> 1, wn = (wq & 1u) * 2 + group;
   const unsigned lo = lane & 31u, hi = lane >> 5;
 
-  const unsigned lin = MM_TILE_LIN(blockIdx.x, tiles_n * tiles_m);
+  const unsigned lin = form_tile<F>(A, B, C, tiles_n * tiles_m, batch, stride_a, stride_b, stride_c);
   const unsigned band = lin / (kBand * tiles_m), within = lin % (kBand * tiles_m);
   const unsigned rows_in_band = min(kBand, tiles_n - band * kBand);
   const unsigned row0 = (band * kBand + within % rows_in_band) * G::BM, col0 = (within / rows_in_band) * G::BN;
@@ -520,18 +518,17 @@ __global__ __launch_bounds__(GeoI8PP2::THREADS) void MM_KNAME(mfma_i8_pp2_kernel
       const unsigned c = it * 64 + lane, row = c / 4, ch = c % 4;
       const u32x4 v = *(const u32x4 *)(slice + row * 64 + ch * 16);
       const unsigned grow = row0 + wm * 128 + row, gcol = col0 + wn * 64 + ch * 16;
-#if MM_SEEDED
-      if (grow < N && gcol < M) {   // accumulate: low 8 bits of seed + sum, bytewise; the lane reads what it then writes
-        u32x4 *dst = (u32x4 *)(C + (size_t)grow * M + gcol);
-        *dst = add_bytes(v, *dst);
+      if constexpr (F == Form::Seeded) {
+        if (grow < N && gcol < M) {   // accumulate: low 8 bits of seed + sum, bytewise; the lane reads what it then writes
+          u32x4 *dst = (u32x4 *)(C + (size_t)grow * M + gcol);
+          *dst = add_bytes(v, *dst);
+        }
+      } else {
+        if (grow < N && gcol < M) *(u32x4 *)(C + (size_t)grow * M + gcol) = v;
       }
-#else
-      if (grow < N && gcol < M) *(u32x4 *)(C + (size_t)grow * M + gcol) = v;
-#endif
     }
   }
 }
-#if !MM_BATCHED
 
 // pingpong_16x16x64 (round 3, the default): same tile, rings, DMA and segment protocol as
 // pingpong_32x32x32, the matrix instruction in its 16 x 16 x 64 form (4 accumulator registers, 16 cycles) -- on full-range random
@@ -543,12 +540,13 @@ __global__ __launch_bounds__(GeoI8PP2::THREADS) void MM_KNAME(mfma_i8_pp2_kernel
 // instead of in column by 16, so the chunk index is XORed with ((k&7)<<1) | ((k>>4)&1): the 16 k-rows a half-wave
 // touches fall into the 16 different chunks of the 256-byte bank row.  Integer sums: bit-identical to every
 // other schedule and to Naive.
-#endif  // !MM_BATCHED
-__global__ __launch_bounds__(GeoI8PP2::THREADS) void MM_KNAME(mfma_i8_pp2s_kernel)(const signed char *__restrict__ A,
+template <Form F>
+__global__ __launch_bounds__(GeoI8PP2::THREADS) void mfma_i8_pp2s_kernel(const signed char *__restrict__ A,
                                                                           const signed char *__restrict__ B,
                                                                           signed char *__restrict__ C, unsigned N, unsigned K,
                                                                           unsigned M, unsigned tiles_n, unsigned tiles_m,
-                                                                          unsigned kBand MM_BATCH_PARAMS) {
+                                                                          unsigned kBand, unsigned batch, size_t stride_a,
+                                                                          size_t stride_b, size_t stride_c) {
   using G = GeoI8PP2;
   constexpr int RB = 8, NB = 4;
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -558,7 +556,7 @@ __global__ __launch_bounds__(GeoI8PP2::THREADS) void MM_KNAME(mfma_i8_pp2s_kerne
   const unsigned wm = wq >> 1, wn = (wq & 1u) * 2 + group;
   const unsigned l15 = lane & 15u, g = lane >> 4;
 
-  const unsigned lin = MM_TILE_LIN(blockIdx.x, tiles_n * tiles_m);
+  const unsigned lin = form_tile<F>(A, B, C, tiles_n * tiles_m, batch, stride_a, stride_b, stride_c);
   const unsigned band = lin / (kBand * tiles_m), within = lin % (kBand * tiles_m);
   const unsigned rows_in_band = min(kBand, tiles_n - band * kBand);
   const unsigned row0 = (band * kBand + within % rows_in_band) * G::BM, col0 = (within / rows_in_band) * G::BN;
@@ -688,17 +686,14 @@ __global__ __launch_bounds__(GeoI8PP2::THREADS) void MM_KNAME(mfma_i8_pp2s_kerne
       const unsigned c = it * 64 + lane, row = c / 4, ch = c % 4;
       const u32x4 v = *(const u32x4 *)(slice + row * 64 + ch * 16);
       const unsigned grow = row0 + wm * 128 + row, gcol = col0 + wn * 64 + ch * 16;
-#if MM_SEEDED
-      if (grow < N && gcol < M) {   // accumulate: low 8 bits of seed + sum, bytewise; the lane reads what it then writes
-        u32x4 *dst = (u32x4 *)(C + (size_t)grow * M + gcol);
-        *dst = add_bytes(v, *dst);
+      if constexpr (F == Form::Seeded) {
+        if (grow < N && gcol < M) {   // accumulate: low 8 bits of seed + sum, bytewise; the lane reads what it then writes
+          u32x4 *dst = (u32x4 *)(C + (size_t)grow * M + gcol);
+          *dst = add_bytes(v, *dst);
+        }
+      } else {
+        if (grow < N && gcol < M) *(u32x4 *)(C + (size_t)grow * M + gcol) = v;
       }
-#else
-      if (grow < N && gcol < M) *(u32x4 *)(C + (size_t)grow * M + gcol) = v;
-#endif
     }
   }
 }
-#undef MM_KNAME
-#undef MM_BATCH_PARAMS
-#undef MM_TILE_LIN

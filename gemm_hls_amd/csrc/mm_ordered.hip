@@ -19,108 +19,151 @@ constexpr int kPerThread = 4;
 // half (Multiply, Add) under MM_PATH_AUTO on shapes the matrix-core kernel does not take
 // ("ordered_wide_f16": exact products, f32 accumulation, ONE rounding to binary16 on store -- the
 // same contract as mfma_f16, so the AUTO path's half semantics do not change with the shape).
-template <typename T, int MAP, int RED, bool AT, typename ACC = T>
+// F (mm_common.h): Form::Single is one problem on a 2-D grid of tiles; the batched forms run `p.batch` elements of one shape
+// on a 1-D grid of batch x tiles workgroups, element-major, Form::Seeded with chains that start at the value C holds
+// instead of identity().  Form::Single never reads the strides.
+template <Form F, typename T, int MAP, int RED, bool AT, typename ACC = T>
 __global__ __launch_bounds__(256) void ordered_kernel(const T *__restrict__ A, const T *__restrict__ B,
-                                                      T *__restrict__ C, unsigned N, unsigned K,
-                                                      unsigned M) {
-#define MM_ORDERED_BATCHED 0
-#include "mm_ordered_body.inc"
-#undef MM_ORDERED_BATCHED
-}
-
-// `p.batch` elements of one shape in one launch: a 1-D grid of batch x tiles workgroups, element-major
-template <typename T, int MAP, int RED, bool AT, typename ACC = T>
-__global__ __launch_bounds__(256) void ordered_batched_kernel(const T *__restrict__ A, const T *__restrict__ B,
-                                                              T *__restrict__ C, unsigned N, unsigned K, unsigned M,
-                                                              size_t stride_a, size_t stride_b, size_t stride_c) {
-#define MM_ORDERED_BATCHED 1
-#include "mm_ordered_body.inc"
-#undef MM_ORDERED_BATCHED
-}
-
-// accumulate (p.seed): ordered_batched_kernel whose chains start at the value C holds instead of identity()
-template <typename T, int MAP, int RED, bool AT, typename ACC = T>
-__global__ __launch_bounds__(256) void ordered_batched_seeded_kernel(const T *__restrict__ A, const T *__restrict__ B,
-                                                                     T *__restrict__ C, unsigned N, unsigned K, unsigned M,
-                                                                     size_t stride_a, size_t stride_b, size_t stride_c) {
-#define MM_ORDERED_BATCHED 1
-#define MM_ORDERED_SEEDED 1
-#include "mm_ordered_body.inc"
-#undef MM_ORDERED_SEEDED
-#undef MM_ORDERED_BATCHED
-}
-
-// BATCHED: the p.batch elements of p (strides p.stride_*) in one launch of ordered_batched_kernel (p.seed: its seeded form)
-template <typename T, int MAP, int RED, bool BATCHED, typename ACC = T>
-int launch_t(hipStream_t s, const Problem &p) {
-  if (p.n == 0 || p.m == 0) return 0;
-  if constexpr (BATCHED) {
-    const unsigned tiles = ((p.m + kTile - 1) / kTile) * ((p.n + kTile - 1) / kTile);
-    if (p.seed) {
-      if (p.a_transposed)
-        hipLaunchKernelGGL((ordered_batched_seeded_kernel<T, MAP, RED, true, ACC>), dim3(tiles * p.batch), dim3(256), 0, s,
-                           (const T *)p.a, (const T *)p.b, (T *)p.c, p.n, p.k, p.m, p.stride_a, p.stride_b, p.stride_c);
-      else
-        hipLaunchKernelGGL((ordered_batched_seeded_kernel<T, MAP, RED, false, ACC>), dim3(tiles * p.batch), dim3(256), 0, s,
-                           (const T *)p.a, (const T *)p.b, (T *)p.c, p.n, p.k, p.m, p.stride_a, p.stride_b, p.stride_c);
-      return (int)hipGetLastError();
-    }
-    if (p.a_transposed)
-      hipLaunchKernelGGL((ordered_batched_kernel<T, MAP, RED, true, ACC>), dim3(tiles * p.batch), dim3(256), 0, s,
-                         (const T *)p.a, (const T *)p.b, (T *)p.c, p.n, p.k, p.m, p.stride_a, p.stride_b, p.stride_c);
-    else
-      hipLaunchKernelGGL((ordered_batched_kernel<T, MAP, RED, false, ACC>), dim3(tiles * p.batch), dim3(256), 0, s,
-                         (const T *)p.a, (const T *)p.b, (T *)p.c, p.n, p.k, p.m, p.stride_a, p.stride_b, p.stride_c);
-    return (int)hipGetLastError();
+                                                      T *__restrict__ C, unsigned N, unsigned K, unsigned M,
+                                                      size_t stride_a, size_t stride_b, size_t stride_c) {
+  __shared__ T As[kBK][kTile + 1];  // [k][row], +1: column reads of a row-major source
+  __shared__ T Bs[kBK][kTile];      // [k][col]
+  const unsigned tid = threadIdx.x;
+  const unsigned tx = tid % 16, ty = tid / 16;
+  unsigned row0, col0;
+  if constexpr (F == Form::Single) {   // a 2-D grid of tiles
+    row0 = blockIdx.y * kTile, col0 = blockIdx.x * kTile;
+  } else {
+    // element e of the batch: XCD-remapped ids e * tiles .. (e + 1) * tiles - 1 (one element's tiles stay on one XCD),
+    // row-major over its tile grid; uniform, SGPRs
+    const unsigned tiles_m = (M + kTile - 1) / kTile, tiles = tiles_m * ((N + kTile - 1) / kTile);
+    const unsigned lin = xcd_remap(blockIdx.x, gridDim.x), e = lin / tiles, t = lin - e * tiles;
+    A += e * stride_a;
+    B += e * stride_b;
+    C += e * stride_c;
+    row0 = (t / tiles_m) * kTile, col0 = (t % tiles_m) * kTile;
   }
-  dim3 grid((p.m + kTile - 1) / kTile, (p.n + kTile - 1) / kTile);
-  if (p.a_transposed)
-    hipLaunchKernelGGL((ordered_kernel<T, MAP, RED, true>), grid, dim3(256), 0, s, (const T *)p.a,
-                       (const T *)p.b, (T *)p.c, p.n, p.k, p.m);
-  else
-    hipLaunchKernelGGL((ordered_kernel<T, MAP, RED, false>), grid, dim3(256), 0, s, (const T *)p.a,
-                       (const T *)p.b, (T *)p.c, p.n, p.k, p.m);
+
+  ACC acc[kPerThread][kPerThread];
+#pragma unroll
+  for (int i = 0; i < kPerThread; ++i)
+#pragma unroll
+    for (int j = 0; j < kPerThread; ++j) acc[i][j] = Op<RED, ACC>::identity();
+  if constexpr (F == Form::Seeded) {
+    // accumulate: the value C holds replaces identity() as the start of the chain (Naive with acc = C[i][j]); the loads are
+    // only consumed at the first k-step, so they are in flight while the first slab is staged
+#pragma unroll
+    for (int i = 0; i < kPerThread; ++i) {
+      const unsigned gr = row0 + ty * kPerThread + i;
+#pragma unroll
+      for (int j = 0; j < kPerThread; ++j) {
+        const unsigned gc = col0 + tx + 16 * j;
+        if (gr < N && gc < M) acc[i][j] = (ACC)C[(size_t)gr * M + gc];
+      }
+    }
+  }
+
+  for (unsigned k0 = 0; k0 < K; k0 += kBK) {
+    // stage A: 64 rows x 16 k
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      unsigned r, kk;
+      if (AT) { r = tid % 64; kk = tid / 64 + 4 * i; }   // A is K x N: consecutive lanes along N
+      else    { kk = tid % 16; r = tid / 16 + 16 * i; }  // A is N x K: consecutive lanes along K
+      const unsigned gr = row0 + r, gk = k0 + kk;
+      T v = (T)0;
+      if (gr < N && gk < K) v = AT ? A[(size_t)gk * N + gr] : A[(size_t)gr * K + gk];
+      As[kk][r] = v;
+    }
+    // stage B: 16 k x 64 cols
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const unsigned c = tid % 64, kk = tid / 64 + 4 * i;
+      const unsigned gc = col0 + c, gk = k0 + kk;
+      Bs[kk][c] = (gc < M && gk < K) ? B[(size_t)gk * M + gc] : (T)0;
+    }
+    __syncthreads();
+    const unsigned kmax = (K - k0) < (unsigned)kBK ? (K - k0) : (unsigned)kBK;
+    for (unsigned kk = 0; kk < kmax; ++kk) {  // strictly ascending k
+      T av[kPerThread], bv[kPerThread];
+#pragma unroll
+      for (int i = 0; i < kPerThread; ++i) av[i] = As[kk][ty * kPerThread + i];
+#pragma unroll
+      for (int j = 0; j < kPerThread; ++j) bv[j] = Bs[kk][tx + 16 * j];
+#pragma unroll
+      for (int i = 0; i < kPerThread; ++i)
+#pragma unroll
+        for (int j = 0; j < kPerThread; ++j)
+          acc[i][j] = Op<RED, ACC>::apply(acc[i][j], Op<MAP, ACC>::apply((ACC)av[i], (ACC)bv[j]));
+    }
+    __syncthreads();
+  }
+#pragma unroll
+  for (int i = 0; i < kPerThread; ++i) {
+    const unsigned gr = row0 + ty * kPerThread + i;
+    if (gr >= N) continue;
+#pragma unroll
+    for (int j = 0; j < kPerThread; ++j) {
+      const unsigned gc = col0 + tx + 16 * j;
+      if (gc < M) C[(size_t)gr * M + gc] = (T)acc[i][j];
+    }
+  }
+}
+
+// One launch of ordered_kernel<F, ...>: the problem at (a, b, c), or (F != Form::Single) the p.batch elements of p
+template <Form F, typename T, int MAP, int RED, bool AT, typename ACC>
+int launch_at(hipStream_t s, const Problem &p) {
+  const unsigned tiles_m = (p.m + kTile - 1) / kTile, tiles_n = (p.n + kTile - 1) / kTile;
+  const dim3 grid = F == Form::Single ? dim3(tiles_m, tiles_n) : dim3(tiles_m * tiles_n * p.batch);
+  hipLaunchKernelGGL((ordered_kernel<F, T, MAP, RED, AT, ACC>), grid, dim3(256), 0, s, (const T *)p.a, (const T *)p.b,
+                     (T *)p.c, p.n, p.k, p.m, p.stride_a, p.stride_b, p.stride_c);
   return (int)hipGetLastError();
 }
 
-template <typename T, int MAP, bool BATCHED>
+template <Form F, typename T, int MAP, int RED, typename ACC = T>
+int launch_t(hipStream_t s, const Problem &p) {
+  if (p.n == 0 || p.m == 0) return 0;
+  return p.a_transposed ? launch_at<F, T, MAP, RED, true, ACC>(s, p) : launch_at<F, T, MAP, RED, false, ACC>(s, p);
+}
+
+template <Form F, typename T, int MAP>
 int launch_red(hipStream_t s, int red, const Problem &p) {
   switch (red) {
-    case MM_OP_ADD: return launch_t<T, MAP, MM_OP_ADD, BATCHED>(s, p);
-    case MM_OP_MULTIPLY: return launch_t<T, MAP, MM_OP_MULTIPLY, BATCHED>(s, p);
-    case MM_OP_AND: return launch_t<T, MAP, MM_OP_AND, BATCHED>(s, p);
-    case MM_OP_MIN: return launch_t<T, MAP, MM_OP_MIN, BATCHED>(s, p);
-    case MM_OP_MAX: return launch_t<T, MAP, MM_OP_MAX, BATCHED>(s, p);
+    case MM_OP_ADD: return launch_t<F, T, MAP, MM_OP_ADD>(s, p);
+    case MM_OP_MULTIPLY: return launch_t<F, T, MAP, MM_OP_MULTIPLY>(s, p);
+    case MM_OP_AND: return launch_t<F, T, MAP, MM_OP_AND>(s, p);
+    case MM_OP_MIN: return launch_t<F, T, MAP, MM_OP_MIN>(s, p);
+    case MM_OP_MAX: return launch_t<F, T, MAP, MM_OP_MAX>(s, p);
   }
   return kErrNotSupported;
 }
 
-template <typename T, bool BATCHED>
+template <Form F, typename T>
 int launch_map(hipStream_t s, const mm_config_t &cfg, const Problem &p) {
   switch (cfg.map_op) {
-    case MM_OP_ADD: return launch_red<T, MM_OP_ADD, BATCHED>(s, cfg.reduce_op, p);
-    case MM_OP_MULTIPLY: return launch_red<T, MM_OP_MULTIPLY, BATCHED>(s, cfg.reduce_op, p);
-    case MM_OP_AND: return launch_red<T, MM_OP_AND, BATCHED>(s, cfg.reduce_op, p);
-    case MM_OP_MIN: return launch_red<T, MM_OP_MIN, BATCHED>(s, cfg.reduce_op, p);
-    case MM_OP_MAX: return launch_red<T, MM_OP_MAX, BATCHED>(s, cfg.reduce_op, p);
+    case MM_OP_ADD: return launch_red<F, T, MM_OP_ADD>(s, cfg.reduce_op, p);
+    case MM_OP_MULTIPLY: return launch_red<F, T, MM_OP_MULTIPLY>(s, cfg.reduce_op, p);
+    case MM_OP_AND: return launch_red<F, T, MM_OP_AND>(s, cfg.reduce_op, p);
+    case MM_OP_MIN: return launch_red<F, T, MM_OP_MIN>(s, cfg.reduce_op, p);
+    case MM_OP_MAX: return launch_red<F, T, MM_OP_MAX>(s, cfg.reduce_op, p);
   }
   return kErrNotSupported;
 }
 
-template <bool BATCHED>
+template <Form F>
 int launch_type(hipStream_t s, const mm_config_t &cfg, const Problem &p) {
   switch (cfg.dtype) {
-    case MM_DTYPE_F32: return launch_map<float, BATCHED>(s, cfg, p);
-    case MM_DTYPE_F64: return launch_map<double, BATCHED>(s, cfg, p);
-    case MM_DTYPE_F16: return launch_map<half_t, BATCHED>(s, cfg, p);
-    case MM_DTYPE_I8: return launch_map<int8_t, BATCHED>(s, cfg, p);
-    case MM_DTYPE_U8: return launch_map<uint8_t, BATCHED>(s, cfg, p);
-    case MM_DTYPE_I16: return launch_map<int16_t, BATCHED>(s, cfg, p);
-    case MM_DTYPE_U16: return launch_map<uint16_t, BATCHED>(s, cfg, p);
-    case MM_DTYPE_I32: return launch_map<int32_t, BATCHED>(s, cfg, p);
-    case MM_DTYPE_U32: return launch_map<uint32_t, BATCHED>(s, cfg, p);
-    case MM_DTYPE_I64: return launch_map<int64_t, BATCHED>(s, cfg, p);
-    case MM_DTYPE_U64: return launch_map<uint64_t, BATCHED>(s, cfg, p);
+    case MM_DTYPE_F32: return launch_map<F, float>(s, cfg, p);
+    case MM_DTYPE_F64: return launch_map<F, double>(s, cfg, p);
+    case MM_DTYPE_F16: return launch_map<F, half_t>(s, cfg, p);
+    case MM_DTYPE_I8: return launch_map<F, int8_t>(s, cfg, p);
+    case MM_DTYPE_U8: return launch_map<F, uint8_t>(s, cfg, p);
+    case MM_DTYPE_I16: return launch_map<F, int16_t>(s, cfg, p);
+    case MM_DTYPE_U16: return launch_map<F, uint16_t>(s, cfg, p);
+    case MM_DTYPE_I32: return launch_map<F, int32_t>(s, cfg, p);
+    case MM_DTYPE_U32: return launch_map<F, uint32_t>(s, cfg, p);
+    case MM_DTYPE_I64: return launch_map<F, int64_t>(s, cfg, p);
+    case MM_DTYPE_U64: return launch_map<F, uint64_t>(s, cfg, p);
   }
   return kErrNotSupported;
 }
@@ -128,21 +171,17 @@ int launch_type(hipStream_t s, const mm_config_t &cfg, const Problem &p) {
 }  // namespace
 
 int launch_half_wide(hipStream_t s, const Problem &p) {
-  if (p.n == 0 || p.m == 0) return 0;
-  dim3 grid((p.m + kTile - 1) / kTile, (p.n + kTile - 1) / kTile);
-  if (p.a_transposed)
-    hipLaunchKernelGGL((ordered_kernel<half_t, MM_OP_MULTIPLY, MM_OP_ADD, true, float>), grid, dim3(256), 0, s,
-                       (const half_t *)p.a, (const half_t *)p.b, (half_t *)p.c, p.n, p.k, p.m);
-  else
-    hipLaunchKernelGGL((ordered_kernel<half_t, MM_OP_MULTIPLY, MM_OP_ADD, false, float>), grid, dim3(256), 0, s,
-                       (const half_t *)p.a, (const half_t *)p.b, (half_t *)p.c, p.n, p.k, p.m);
-  return (int)hipGetLastError();
+  return launch_t<Form::Single, half_t, MM_OP_MULTIPLY, MM_OP_ADD, float>(s, p);
 }
 
-int launch_ordered(hipStream_t s, const mm_config_t &cfg, const Problem &p) { return launch_type<false>(s, cfg, p); }
-int launch_ordered_batched(hipStream_t s, const mm_config_t &cfg, const Problem &p) { return launch_type<true>(s, cfg, p); }
+int launch_ordered(hipStream_t s, const mm_config_t &cfg, const Problem &p) { return launch_type<Form::Single>(s, cfg, p); }
+// batched: the p.batch elements of p (strides p.stride_*) in one launch; p.seed: the chains start from C
+int launch_ordered_batched(hipStream_t s, const mm_config_t &cfg, const Problem &p) {
+  return p.seed ? launch_type<Form::Seeded>(s, cfg, p) : launch_type<Form::Batched>(s, cfg, p);
+}
 int launch_half_wide_batched(hipStream_t s, const Problem &p) {
-  return launch_t<half_t, MM_OP_MULTIPLY, MM_OP_ADD, true, float>(s, p);
+  return p.seed ? launch_t<Form::Seeded, half_t, MM_OP_MULTIPLY, MM_OP_ADD, float>(s, p)
+                : launch_t<Form::Batched, half_t, MM_OP_MULTIPLY, MM_OP_ADD, float>(s, p);
 }
 
 }  // namespace mm

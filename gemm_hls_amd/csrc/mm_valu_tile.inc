@@ -56,36 +56,108 @@ template <> struct FastOp<MM_OP_MAX, half_t> : Op<MM_OP_MAX, half_t> {
 #endif
 
 
-template <typename T, int MAP, int RED, bool AT>
+// F (mm_common.h): the single-problem kernel, its strided-batched form, or (Form::Seeded) the batched form with the acc tile
+// loaded from C instead of set to identity()
+template <Form F, typename T, int MAP, int RED, bool AT>
 __global__ __launch_bounds__(256) void valu_tile_kernel(const T *__restrict__ A, const T *__restrict__ B,
                                                         T *__restrict__ C, unsigned N, unsigned K, unsigned M,
-                                                        unsigned tiles_n, unsigned tiles_m, unsigned kBand) {
-#define MM_VT_BATCHED 0
-#include "mm_valu_tile_body.inc"
-#undef MM_VT_BATCHED
-}
-
-template <typename T, int MAP, int RED, bool AT>
-__global__ __launch_bounds__(256) void valu_tile_batched_kernel(const T *__restrict__ A, const T *__restrict__ B,
-                                                        T *__restrict__ C, unsigned N, unsigned K, unsigned M,
                                                         unsigned tiles_n, unsigned tiles_m, unsigned kBand,
-    unsigned batch, size_t stride_a, size_t stride_b, size_t stride_c) {
-#define MM_VT_BATCHED 1
-#include "mm_valu_tile_body.inc"
-#undef MM_VT_BATCHED
-}
+                                                        unsigned batch, size_t stride_a, size_t stride_b, size_t stride_c) {
+  __shared__ __attribute__((aligned(16))) T As[VT_BK][VT_BM + VT_PAD];
+  __shared__ __attribute__((aligned(16))) T Bs[VT_BK][VT_BN + VT_PAD];
+  const unsigned tid = threadIdx.x, tx = tid % 16, ty = tid / 16;
+  const unsigned lin = form_tile<F>(A, B, C, tiles_n * tiles_m, batch, stride_a, stride_b, stride_c);
+  const unsigned band = lin / (kBand * tiles_m), within = lin % (kBand * tiles_m);
+  const unsigned rows_in_band = min(kBand, tiles_n - band * kBand);
+  const unsigned row0 = (band * kBand + within % rows_in_band) * VT_BM, col0 = (within / rows_in_band) * VT_BN;
 
-// accumulate (Problem::seed): valu_tile_batched_kernel with the acc tile loaded from C instead of set to identity()
-template <typename T, int MAP, int RED, bool AT>
-__global__ __launch_bounds__(256) void valu_tile_batched_seeded_kernel(const T *__restrict__ A, const T *__restrict__ B,
-                                                        T *__restrict__ C, unsigned N, unsigned K, unsigned M,
-                                                        unsigned tiles_n, unsigned tiles_m, unsigned kBand,
-    unsigned batch, size_t stride_a, size_t stride_b, size_t stride_c) {
-#define MM_VT_BATCHED 1
-#define MM_VT_SEEDED 1
-#include "mm_valu_tile_body.inc"
-#undef MM_VT_SEEDED
-#undef MM_VT_BATCHED
+  T acc[8][8];
+#pragma unroll
+  for (int i = 0; i < 8; ++i)
+#pragma unroll
+    for (int j = 0; j < 8; ++j) acc[i][j] = Op<RED, T>::identity();
+
+  using V = Vec4<T>;
+  if constexpr (F == Form::Seeded) {
+    // accumulate: the acc tile starts from C, read with the Vec4 accesses the store below uses (a lane reads exactly what it
+    // later writes); the loads are consumed at the first k-step, so they are in flight while the first slab is staged
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      const unsigned r = row0 + (i < 4 ? ty * 4 + i : 64 + ty * 4 + (i - 4));
+      if (r >= N) continue;
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        const unsigned c = col0 + h * 64 + tx * 4;
+        if (c < M) {
+          const V v = *(const V *)(C + (size_t)r * M + c);
+#pragma unroll
+          for (int e = 0; e < 4; ++e) acc[i][h * 4 + e] = v.v[e];
+        }
+      }
+    }
+  }
+  for (unsigned k0 = 0; k0 < K; k0 += VT_BK) {
+    // ---- stage (K % 4 == 0, so a 4-wide k chunk is entirely inside or entirely outside) ----
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+      const unsigned idx = tid + 256 * u;
+      if (AT) {  // A is K x N: rows of the tile are contiguous
+        const unsigned kr = idx / 32, r4 = (idx % 32) * 4;
+        V v = {};
+        if (k0 + kr < K && row0 + r4 < N) v = *(const V *)(A + (size_t)(k0 + kr) * N + row0 + r4);
+        *(V *)&As[kr][r4] = v;
+      } else {   // A is N x K: 4 lanes cover one row's 16 k; scatter into the k-major image
+        const unsigned r = idx / 4, kc = (idx % 4) * 4;
+        V v = {};
+        if (row0 + r < N && k0 + kc < K) v = *(const V *)(A + (size_t)(row0 + r) * K + k0 + kc);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) As[kc + e][r] = v.v[e];
+      }
+      {
+        const unsigned kr = idx / 32, c4 = (idx % 32) * 4;
+        V v = {};
+        if (k0 + kr < K && col0 + c4 < M) v = *(const V *)(B + (size_t)(k0 + kr) * M + col0 + c4);
+        *(V *)&Bs[kr][c4] = v;
+      }
+    }
+    __syncthreads();
+    const unsigned kmax = min((unsigned)VT_BK, K - k0);  // multiple of 4
+    for (unsigned kk = 0; kk < kmax; kk += 2) {
+      T a0[8], b0[8], a1[8], b1[8];
+      *(V *)&a0[0] = *(const V *)&As[kk][ty * 4];
+      *(V *)&a0[4] = *(const V *)&As[kk][64 + ty * 4];
+      *(V *)&b0[0] = *(const V *)&Bs[kk][tx * 4];
+      *(V *)&b0[4] = *(const V *)&Bs[kk][64 + tx * 4];
+      *(V *)&a1[0] = *(const V *)&As[kk + 1][ty * 4];
+      *(V *)&a1[4] = *(const V *)&As[kk + 1][64 + ty * 4];
+      *(V *)&b1[0] = *(const V *)&Bs[kk + 1][tx * 4];
+      *(V *)&b1[4] = *(const V *)&Bs[kk + 1][64 + tx * 4];
+#pragma unroll
+      for (int i = 0; i < 8; ++i)
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          const T s0 = FastOp<MAP, T>::apply(a0[i], b0[j]);
+          const T s1 = FastOp<MAP, T>::apply(a1[i], b1[j]);
+          acc[i][j] = FastOp<RED, T>::apply(FastOp<RED, T>::apply(acc[i][j], s0), s1);  // k, then k+1
+        }
+    }
+    __syncthreads();
+  }
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    const unsigned r = row0 + (i < 4 ? ty * 4 + i : 64 + ty * 4 + (i - 4));
+    if (r >= N) continue;
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      const unsigned c = col0 + h * 64 + tx * 4;
+      if (c < M) {
+        V v;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) v.v[e] = acc[i][h * 4 + e];
+        *(V *)(C + (size_t)r * M + c) = v;
+      }
+    }
+  }
 }
 
 // -------------------------------------------------------------------------------------------------
@@ -111,35 +183,140 @@ constexpr int VTD_A_BYTES = VT_BM * 64, VTD_SLAB = 2 * VTD_A_BYTES;  // 8 KiB + 
 // instead of 128, so two workgroups = 4 wavefronts per SIMD fit a CU where the 8 x 8 form fits 2 (fp64 VALU instructions
 // issue every 4.26 cycles at 4 waves per SIMD against 4.51 at 2: profiles/r03s_probe_valu_issue_rates_incl_f64.txt).
 // The per-output operation sequence does not depend on TI: same bits.
-template <typename T, int MAP, int RED, int TI>
+template <Form F, typename T, int MAP, int RED, int TI>
 __global__ __launch_bounds__(TI == 8 ? 256 : 512, TI == 8 ? 1 : 4) void valu_tile_dma_kernel(const T *__restrict__ A, const T *__restrict__ B,
                                                             T *__restrict__ C, unsigned N, unsigned K, unsigned M,
-                                                            unsigned tiles_n, unsigned tiles_m, unsigned kBand) {
-#define MM_VT_BATCHED 0
-#include "mm_valu_tile_dma_body.inc"
-#undef MM_VT_BATCHED
-}
-
-template <typename T, int MAP, int RED, int TI>
-__global__ __launch_bounds__(TI == 8 ? 256 : 512, TI == 8 ? 1 : 4) void valu_tile_dma_batched_kernel(const T *__restrict__ A, const T *__restrict__ B,
-                                                            T *__restrict__ C, unsigned N, unsigned K, unsigned M,
                                                             unsigned tiles_n, unsigned tiles_m, unsigned kBand,
-    unsigned batch, size_t stride_a, size_t stride_b, size_t stride_c) {
-#define MM_VT_BATCHED 1
-#include "mm_valu_tile_dma_body.inc"
-#undef MM_VT_BATCHED
-}
+                                                            unsigned batch, size_t stride_a, size_t stride_b, size_t stride_c) {
+  static_assert(TI == 8 || TI == 4, "rows per thread");
+  constexpr unsigned ES = sizeof(T), EPC = 16 / ES, BK = 64 / ES;   // bytes, elements per 16-B chunk, slab depth
+  constexpr unsigned LPR = 8 * ES, KRP = 64 / LPR;                  // lanes per B k-row (128 cols), k-rows per 1-KiB piece
+  constexpr unsigned NW = TI == 8 ? 4 : 8, PW = 8 / NW;             // wavefronts; DMA pieces of A (and of B) per wavefront and slab
+  static_assert(VT_BN * ES * BK == VTD_A_BYTES && VT_BM == 128 && VT_BN == 128, "byte geometry");
+  __shared__ __attribute__((aligned(16))) char smem[2 * VTD_SLAB];
+  const unsigned tid = threadIdx.x, tx = tid % 16, ty = tid / 16;
+  const unsigned lane = tid & 63u, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const unsigned lin = form_tile<F>(A, B, C, tiles_n * tiles_m, batch, stride_a, stride_b, stride_c);
+  const unsigned band = lin / (kBand * tiles_m), within = lin % (kBand * tiles_m);
+  const unsigned rows_in_band = min(kBand, tiles_n - band * kBand);
+  const unsigned row0 = (band * kBand + within % rows_in_band) * VT_BM, col0 = (within / rows_in_band) * VT_BN;
 
-template <typename T, int MAP, int RED, int TI>
-__global__ __launch_bounds__(TI == 8 ? 256 : 512, TI == 8 ? 1 : 4) void valu_tile_dma_batched_seeded_kernel(const T *__restrict__ A, const T *__restrict__ B,
-                                                            T *__restrict__ C, unsigned N, unsigned K, unsigned M,
-                                                            unsigned tiles_n, unsigned tiles_m, unsigned kBand,
-    unsigned batch, size_t stride_a, size_t stride_b, size_t stride_c) {
-#define MM_VT_BATCHED 1
-#define MM_VT_SEEDED 1
-#include "mm_valu_tile_dma_body.inc"
-#undef MM_VT_SEEDED
-#undef MM_VT_BATCHED
+  // DMA: 8 A pieces (16 rows x 64 B) and 8 B pieces (KRP k-rows x 128 cols) per slab, PW + PW per wave
+  unsigned voff_a[PW], voff_b[PW];
+#pragma unroll
+  for (unsigned i = 0; i < PW; ++i) {
+    const unsigned piece = wave + NW * i;
+    const unsigned row = piece * 16 + lane / 4, pc = lane % 4;
+    voff_a[i] = (min(row0 + row, N - 1) - row0) * K * ES + (pc ^ ((row >> 2) & 3u)) * 16;
+    const unsigned kr = piece * KRP + lane / LPR, c = (lane % LPR) * EPC;
+    voff_b[i] = kr * M * ES + (min(col0 + c, M - EPC) - col0) * ES;
+  }
+  const char *a_base = (const char *)A + (size_t)row0 * K * ES;
+  const char *b_base = (const char *)B + (size_t)col0 * ES;
+  const unsigned lds0 = (unsigned)(size_t)(__attribute__((address_space(3))) char *)smem;
+  const unsigned slabs = (K + BK - 1) / BK;
+  auto issue = [&](unsigned t) {  // slab t -> buffer t & 1; the last slab starts at K - BK
+    const unsigned k0 = min(t * BK, K - BK);
+    const char *ap = a_base + (size_t)k0 * ES;
+    const char *bp = b_base + (size_t)k0 * M * ES;
+    const unsigned la0 = lds0 + (t & 1u) * VTD_SLAB + wave * 1024, la1 = la0 + 4 * 1024;
+    const unsigned lb0 = la0 + VTD_A_BYTES, lb1 = lb0 + 4 * 1024;
+    unsigned keep;
+    if constexpr (PW == 2) {
+      asm volatile("s_mov_b32 %0, m0\n\t" MM_DMA_PIECE("%1", "%5", "%7") MM_DMA_PIECE("%2", "%5", "%8")
+                       MM_DMA_PIECE("%3", "%6", "%9") MM_DMA_PIECE("%4", "%6", "%10") "s_mov_b32 m0, %0"
+                   : "=&s"(keep)
+                   : "v"(voff_a[0]), "v"(voff_a[1]), "v"(voff_b[0]), "v"(voff_b[1]), "s"(ap), "s"(bp), "s"(la0), "s"(la1),
+                     "s"(lb0), "s"(lb1)
+                   : "memory");
+    } else {
+      asm volatile("s_mov_b32 %0, m0\n\t" MM_DMA_PIECE("%1", "%3", "%5") MM_DMA_PIECE("%2", "%4", "%6") "s_mov_b32 m0, %0"
+                   : "=&s"(keep)
+                   : "v"(voff_a[0]), "v"(voff_b[0]), "s"(ap), "s"(bp), "s"(la0), "s"(lb0)
+                   : "memory");
+    }
+  };
+
+  T acc[TI][8];
+#pragma unroll
+  for (int i = 0; i < TI; ++i)
+#pragma unroll
+    for (int j = 0; j < 8; ++j) acc[i][j] = Op<RED, T>::identity();
+
+  using V = Vec4<T>;
+  constexpr unsigned KSTEP = ES >= 4 ? 2 : 8 / ES;   // k per A read: 16 B (8-byte types) or 8 B
+  struct alignas(KSTEP * sizeof(T)) PK { T v[KSTEP]; };
+  // row i of this thread: TI == 8: ty*4 + i, then 64 + ty*4 + (i-4) (ty < 16); TI == 4: ty*4 + i (ty < 32).
+  // Either way all of a thread's rows have (row >> 2) & 3 == ty & 3
+  auto thread_row = [&](int i) -> unsigned { return TI == 8 ? (i < 4 ? ty * 4 + i : 64 + ty * 4 + (i - 4)) : ty * 4 + i; };
+  const unsigned a_swz = ty & 3u;
+  issue(0);
+  if constexpr (F == Form::Seeded) {
+    // accumulate: the acc tile starts from C, read with the Vec4 accesses the store below uses (a lane reads exactly what it
+    // later writes), issued behind the first slab's DMA pieces; the loop's first vmcnt(0) waits for both
+#pragma unroll
+    for (int i = 0; i < TI; ++i) {
+      const unsigned r = row0 + thread_row(i);
+      if (r >= N) continue;
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        const unsigned c = col0 + h * 64 + tx * 4;
+        if (c < M) {
+          const V v = *(const V *)(C + (size_t)r * M + c);
+#pragma unroll
+          for (int e = 0; e < 4; ++e) acc[i][h * 4 + e] = v.v[e];
+        }
+      }
+    }
+  }
+  for (unsigned t = 0; t < slabs; ++t) {
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // own pieces of slab t have landed
+    __syncthreads();                                  // everybody's have; buffer (t+1)&1 is no longer being read
+    if (t + 1 < slabs) issue(t + 1);
+    const char *as = smem + (t & 1u) * VTD_SLAB;
+    const char *bs = as + VTD_A_BYTES;
+    // a full slab uses k 0..BK-1 of the buffer; the (shifted) last slab only its new k
+    const unsigned kbeg = t * BK - min(t * BK, K - BK);  // 0 except for a partial last slab
+    // one LDS read per row fetches KSTEP consecutive k (8 or 16 bytes: a pair for 4- and 8-byte types, 4 / 8 k for
+    // 2- / 1-byte types); the map-reduce steps then go pair by pair, k ascending
+    for (unsigned kk = kbeg; kk < BK; kk += KSTEP) {
+      PK av[TI];
+      const unsigned kb = kk * ES, aoff = (((kb >> 4) ^ a_swz) * 16) + (kb & 15u);
+#pragma unroll
+      for (int i = 0; i < TI; ++i) av[i] = *(const PK *)(as + thread_row(i) * 64 + aoff);
+#pragma unroll
+      for (unsigned q = 0; q < KSTEP; q += 2) {
+        T b0[8], b1[8];
+        *(V *)&b0[0] = *(const V *)(bs + ((kk + q) * VT_BN + tx * 4) * ES);
+        *(V *)&b0[4] = *(const V *)(bs + ((kk + q) * VT_BN + 64 + tx * 4) * ES);
+        *(V *)&b1[0] = *(const V *)(bs + ((kk + q + 1) * VT_BN + tx * 4) * ES);
+        *(V *)&b1[4] = *(const V *)(bs + ((kk + q + 1) * VT_BN + 64 + tx * 4) * ES);
+#pragma unroll
+        for (int i = 0; i < TI; ++i)
+#pragma unroll
+          for (int j = 0; j < 8; ++j) {
+            const T s0 = FastOp<MAP, T>::apply(av[i].v[q], b0[j]);
+            const T s1 = FastOp<MAP, T>::apply(av[i].v[q + 1], b1[j]);
+            acc[i][j] = FastOp<RED, T>::apply(FastOp<RED, T>::apply(acc[i][j], s0), s1);  // k, then k+1
+          }
+      }
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < TI; ++i) {
+    const unsigned r = row0 + thread_row(i);
+    if (r >= N) continue;
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      const unsigned c = col0 + h * 64 + tx * 4;
+      if (c < M) {
+        V v;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) v.v[e] = acc[i][h * 4 + e];
+        *(V *)(C + (size_t)r * M + c) = v;
+      }
+    }
+  }
 }
 #undef MM_DMA_PIECE
 
@@ -152,26 +329,17 @@ bool vt_dma_serves(const Problem &p) {
          BK * (unsigned long long)p.m * ES < (1ull << 32);
 }
 
-// BATCHED: p.batch elements of p's shape in one launch (the *_batched_kernel forms), same tile and kernel choice per element
-template <typename T, int MAP, int RED, bool BATCHED>
-int vt_launch(hipStream_t s, const Problem &p) {
+// One launch in form F: the problem at (a, b, c), or (F != Form::Single) p.batch elements of p's shape, same tile and kernel
+// choice per element
+template <Form F, typename T, int MAP, int RED>
+int vt_launch_form(hipStream_t s, const Problem &p) {
   const unsigned tiles_n = (p.n + VT_BM - 1) / VT_BM, tiles_m = (p.m + VT_BN - 1) / VT_BN;
-  const unsigned grid = tiles_n * tiles_m * (BATCHED ? p.batch : 1u);
-  // the kernels' argument lists: the single problem's, plus the batch and the element strides for the batched forms (whose
-  // seeded twins, for p.seed, take the same arguments)
-#define MM_VT_LAUNCH(KERNEL, BATCHED_KERNEL, SEEDED_KERNEL, THREADS, BAND)                                                    \
-  do {                                                                                                                      \
-    if constexpr (BATCHED) {                                                                                                \
-      if (p.seed)                                                                                                           \
-        hipLaunchKernelGGL(SEEDED_KERNEL, dim3(grid), dim3(THREADS), 0, s, (const T *)p.a, (const T *)p.b, (T *)p.c, p.n,  \
-                           p.k, p.m, tiles_n, tiles_m, BAND, p.batch, p.stride_a, p.stride_b, p.stride_c);                \
-      else                                                                                                                  \
-        hipLaunchKernelGGL(BATCHED_KERNEL, dim3(grid), dim3(THREADS), 0, s, (const T *)p.a, (const T *)p.b, (T *)p.c, p.n, \
-                           p.k, p.m, tiles_n, tiles_m, BAND, p.batch, p.stride_a, p.stride_b, p.stride_c);                \
-    } else                                                                                                                  \
-      hipLaunchKernelGGL(KERNEL, dim3(grid), dim3(THREADS), 0, s, (const T *)p.a, (const T *)p.b, (T *)p.c, p.n, p.k, p.m, \
-                         tiles_n, tiles_m, BAND);                                                                           \
-  } while (0)
+  const unsigned grid = tiles_n * tiles_m * (F == Form::Single ? 1u : p.batch);
+  auto launch = [&](auto kernel, unsigned threads, unsigned band) {
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(threads), 0, s, (const T *)p.a, (const T *)p.b, (T *)p.c, p.n, p.k, p.m,
+                       tiles_n, tiles_m, band, F == Form::Single ? 1u : p.batch, p.stride_a, p.stride_b, p.stride_c);
+    return (int)hipGetLastError();
+  };
   // valu_variant knob: 0 = the synchronous kernel; 2 = the DMA-staged kernel with 8 rows per thread for the 8-byte types too
   // (their default since round 4 is 4 rows per thread on 512 threads: 4 wavefronts per SIMD; for the narrower types the same
   // form measured flat, 0.97-1.015 x the 8-row form over float / half / int / uint8, k-ordered and fast alike:
@@ -179,26 +347,19 @@ int vt_launch(hipStream_t s, const Problem &p) {
   const int vv = tuning(TUNE_VALU_VARIANT);
   if (vt_dma_serves<T>(p) && vv != 0) {
     if constexpr (sizeof(T) == 8) {
-      if (vv != 2) {
-        MM_VT_LAUNCH((valu_tile_dma_kernel<T, MAP, RED, 4>), (valu_tile_dma_batched_kernel<T, MAP, RED, 4>),
-                     (valu_tile_dma_batched_seeded_kernel<T, MAP, RED, 4>), 512,
-                     band_rows(VT_BM, VT_BN, 2));
-        return (int)hipGetLastError();
-      }
+      if (vv != 2) return launch(valu_tile_dma_kernel<F, T, MAP, RED, 4>, 512, band_rows(VT_BM, VT_BN, 2));
     }
-    MM_VT_LAUNCH((valu_tile_dma_kernel<T, MAP, RED, 8>), (valu_tile_dma_batched_kernel<T, MAP, RED, 8>),
-                 (valu_tile_dma_batched_seeded_kernel<T, MAP, RED, 8>), 256,
-                 band_rows(VT_BM, VT_BN, 2));
-    return (int)hipGetLastError();
+    return launch(valu_tile_dma_kernel<F, T, MAP, RED, 8>, 256, band_rows(VT_BM, VT_BN, 2));
   }
-  if (p.a_transposed)
-    MM_VT_LAUNCH((valu_tile_kernel<T, MAP, RED, true>), (valu_tile_batched_kernel<T, MAP, RED, true>),
-                 (valu_tile_batched_seeded_kernel<T, MAP, RED, true>), 256, band_rows());
-  else
-    MM_VT_LAUNCH((valu_tile_kernel<T, MAP, RED, false>), (valu_tile_batched_kernel<T, MAP, RED, false>),
-                 (valu_tile_batched_seeded_kernel<T, MAP, RED, false>), 256, band_rows());
-#undef MM_VT_LAUNCH
-  return (int)hipGetLastError();
+  return p.a_transposed ? launch(valu_tile_kernel<F, T, MAP, RED, true>, 256, band_rows())
+                        : launch(valu_tile_kernel<F, T, MAP, RED, false>, 256, band_rows());
+}
+
+// BATCHED: the p.batch elements of p in one launch, accumulating into C for p.seed
+template <typename T, int MAP, int RED, bool BATCHED>
+int vt_launch(hipStream_t s, const Problem &p) {
+  if constexpr (!BATCHED) return vt_launch_form<Form::Single, T, MAP, RED>(s, p);
+  else return p.seed ? vt_launch_form<Form::Seeded, T, MAP, RED>(s, p) : vt_launch_form<Form::Batched, T, MAP, RED>(s, p);
 }
 
 template <typename T, int MAP, bool BATCHED>
