@@ -28,7 +28,8 @@ EXPORTS = ["mm_init", "mm_alloc", "mm_free", "mm_copy_to_device", "mm_copy_to_ho
            "mm_kernel_name_batched", "mm_gemm_accumulate_enqueue", "mm_gemm_accumulate_launch",
            "mm_gemm_batched_accumulate_enqueue", "mm_gemm_batched_accumulate_launch", "mm_gemm_argreduce_enqueue",
            "mm_gemm_argreduce_launch", "mm_kernel_name_argreduce", "mm_closure_enqueue", "mm_closure_launch",
-           "mm_kernel_name_closure", "mm_gemm_logsumexp_enqueue", "mm_gemm_logsumexp_launch", "mm_kernel_name_logsumexp"]
+           "mm_kernel_name_closure", "mm_gemm_logsumexp_enqueue", "mm_gemm_logsumexp_launch", "mm_kernel_name_logsumexp",
+           "mm_gemm_widen_enqueue", "mm_gemm_widen_launch", "mm_kernel_name_widen", "mm_widen_dtype"]
 
 
 class MMError(RuntimeError):
@@ -119,6 +120,11 @@ def lib():
         L.mm_gemm_logsumexp_launch.argtypes = [i, cfgp, vp, vp, vp, u, u, u, u, sz, sz, sz, i, ctypes.POINTER(ctypes.c_double)]
         L.mm_kernel_name_logsumexp.argtypes = [cfgp, u, u, u, u]
         L.mm_kernel_name_logsumexp.restype = ctypes.c_char_p
+        L.mm_gemm_widen_enqueue.argtypes = [vp, cfgp, vp, vp, vp, u, u, u, u, sz, sz, sz, i]
+        L.mm_gemm_widen_launch.argtypes = [i, cfgp, vp, vp, vp, u, u, u, u, sz, sz, sz, i, ctypes.POINTER(ctypes.c_double)]
+        L.mm_kernel_name_widen.argtypes = [cfgp, u, u, u, u]
+        L.mm_kernel_name_widen.restype = ctypes.c_char_p
+        L.mm_widen_dtype.argtypes = [i]
         _lib = L
     return _lib
 
@@ -170,6 +176,17 @@ def kernel_name_closure(cfg, n, batch=1, with_witness=False):
 
 def kernel_name_logsumexp(cfg, n, k, m, batch=1):
     return lib().mm_kernel_name_logsumexp(ctypes.byref(cfg), n, k, m, batch).decode()
+
+
+def kernel_name_widen(cfg, n, k, m, batch=1):
+    return lib().mm_kernel_name_widen(ctypes.byref(cfg), n, k, m, batch).decode()
+
+
+def widen_dtype(dtype):
+    """Name of C's type in the widening calls for operands of `dtype`: "float" for "half", "int" for "int8_t"; None for every
+    other type (mm_widen_dtype)."""
+    code = lib().mm_widen_dtype(DTYPES[dtype])
+    return next((name for name, value in DTYPES.items() if value == code), None)
 
 
 def set_tuning(name, value):
@@ -432,6 +449,52 @@ def addmm_logsumexp_(c, a, b, dtype="float", reduce_op="Max", path=PATH_AUTO, tr
     batch, sc = _inplace_batch(c, n, m, batch)
     cfg = make_config(dtype, "Add", reduce_op, path, transposed_a)
     _enqueue(a.device, lib().mm_gemm_logsumexp_enqueue, ctypes.byref(cfg), a.data_ptr(), b.data_ptr(), c.data_ptr(),
+             n, k, m, batch, sa, sb, sc, 1)
+    return c
+
+
+def _widen_types(what, dtype):
+    wide = widen_dtype(dtype)
+    if wide is None:
+        raise MMError(f"{what} takes half or int8_t operands (got {dtype})")
+    return torch_dtype(dtype), torch_dtype(wide)
+
+
+def matmul_wide(a, b, dtype="half", path=PATH_AUTO, transposed_a=False, out=None):
+    """Widening product on torch's current stream (mm_gemm_widen_enqueue): half operands to a torch.float32 C -- the f32 sums
+    the matrix cores accumulate, not rounded to binary16 -- or int8_t operands to a torch.int32 C, the exact sums mod 2^32.
+    a and b as for bmm (2-D, 3-D, or expanded with batch stride 0); the output is (N, M) when both operands are 2-D, else
+    (B, N, M); out: a contiguous tensor of that shape and of the wide type.  Asynchronous."""
+    import torch
+    tdt, wdt = _widen_types("matmul_wide", dtype)
+    _device_operands("matmul_wide", tdt, a, b)
+    n, k, m, batch, sa, sb = _bmm_shapes("matmul_wide", a, b, transposed_a)
+    shape = (n, m) if a.dim() == 2 and b.dim() == 2 else (batch, n, m)
+    if out is None:
+        out = torch.empty(shape, dtype=wdt, device=a.device)
+    else:
+        _check_out(out, "out", shape, wdt, a.device)
+    cfg = make_config(dtype, "Multiply", "Add", path, transposed_a)
+    _enqueue(a.device, lib().mm_gemm_widen_enqueue, ctypes.byref(cfg), a.data_ptr(), b.data_ptr(), out.data_ptr(),
+             n, k, m, batch, sa, sb, n * m, 0)
+    return out
+
+
+def addmm_wide_(c, a, b, dtype="half", path=PATH_AUTO, transposed_a=False):
+    """In place C <- C + A B in the wide type on torch's current stream (mm_gemm_widen_enqueue, accumulate): c is
+    torch.float32 for half operands, torch.int32 for int8_t; a K-split accumulated through it never rounds to the operand
+    type.  2-D operands as for addmm_, 3-D (and broadcast) as for baddbmm_.  Returns c.  Asynchronous."""
+    tdt, wdt = _widen_types("addmm_wide_", dtype)
+    _device_operands("addmm_wide_", tdt, a, b)
+    _device_operands("addmm_wide_", wdt, c)
+    if c.device != a.device:
+        raise MMError(f"operands live on different devices: {c.device}, {a.device}")
+    if c.dim() not in (2, 3):
+        raise MMError("addmm_wide_ takes 2-D or 3-D operands")
+    n, k, m, batch, sa, sb = _bmm_shapes("addmm_wide_", a, b, transposed_a)
+    batch, sc = _inplace_batch(c, n, m, batch)
+    cfg = make_config(dtype, "Multiply", "Add", path, transposed_a)
+    _enqueue(a.device, lib().mm_gemm_widen_enqueue, ctypes.byref(cfg), a.data_ptr(), b.data_ptr(), c.data_ptr(),
              n, k, m, batch, sa, sb, sc, 1)
     return c
 

@@ -35,6 +35,8 @@ EXTRA = {
     "mm_ordered.hip": ["-ffp-contract=off"],
     # the register-tiled kernels under the same k-ordered, unfused contract ("ordered_tile")
     "mm_valu_tile_fp_exact.hip": ["-ffp-contract=off"],
+    # the widening fallback: f32 sums of exact products in k order, reproducible on the host
+    "mm_widen_ordered.hip": ["-ffp-contract=off"],
 }
 
 HOST_CONFIGS = [  # (Data_t, MM_MAP_OP, MM_REDUCE_OP): BASELINE.json configs + an integer semiring

@@ -270,11 +270,12 @@ bool spans_overlap(const void *x, size_t xbytes, const void *y, size_t ybytes) {
 
 // Whether C overlaps A or B, or (given) the int32 index I, laid out as C, overlaps A, B or C -- over the bytes the whole
 // batch can touch.  A conservative test: the kernels read A and B while other workgroups already write C and I.
-bool outputs_overlap(const mm::Problem &p, size_t es, const int *index = nullptr) {
+// c_es: C's element size where it is not the operands' (mm_gemm_widen_*).
+bool outputs_overlap(const mm::Problem &p, size_t es, const int *index = nullptr, size_t c_es = 0) {
   const size_t nm = (size_t)p.n * p.m;
   const size_t a_bytes = batch_span((size_t)p.n * p.k, p.stride_a, p.batch, es);
   const size_t b_bytes = batch_span((size_t)p.k * p.m, p.stride_b, p.batch, es);
-  const size_t c_bytes = batch_span(nm, p.stride_c, p.batch, es), i_bytes = batch_span(nm, p.stride_c, p.batch, sizeof(int));
+  const size_t c_bytes = batch_span(nm, p.stride_c, p.batch, c_es ? c_es : es), i_bytes = batch_span(nm, p.stride_c, p.batch, sizeof(int));
   return spans_overlap(p.c, c_bytes, p.a, a_bytes) || spans_overlap(p.c, c_bytes, p.b, b_bytes) ||
          (index && (spans_overlap(index, i_bytes, p.a, a_bytes) || spans_overlap(index, i_bytes, p.b, b_bytes) ||
                     spans_overlap(index, i_bytes, p.c, c_bytes)));
@@ -707,6 +708,63 @@ int dispatch_lse(hipStream_t s, const mm_config_t &cfg, const mm::Problem &p, Ls
   return ker == LSE_HYBRID ? dispatch_lse_hybrid(s, cfg, q) : lse_exact_chunks(s, cfg, q, nullptr);
 }
 
+// ---- widening (mm_gemm_widen_*): int8_t operands to int sums, half operands to float sums -------------------------------------
+enum WidenKernel { WD_NONE, WD_ORDERED, WD_ORDERED_BLOCKED, WD_MFMA };   // BLOCKED: a misaligned matrix-core launch, demoted
+
+bool widen_serves(const mm_config_t &cfg) {
+  return (cfg.dtype == MM_DTYPE_F16 || cfg.dtype == MM_DTYPE_I8) && cfg.map_op == MM_OP_MULTIPLY && cfg.reduce_op == MM_OP_ADD &&
+         cfg.path != MM_PATH_SPLIT;
+}
+
+// The wide instantiation of the kernel the narrow batched resolver names, by shape and path alone (mm_kernel_name_widen);
+// null: widen_ordered.  The half_contract knob does not apply: it chooses between two narrow contracts.
+const char *widen_mfma_name(const mm_config_t &cfg, const mm::Problem &p) {
+  if (cfg.path != MM_PATH_AUTO) return nullptr;
+  return cfg.dtype == MM_DTYPE_I8 ? mm::mfma_i8_wide_name(p) : mm::mfma_f16_wide_name(p);
+}
+
+// All argument checks of a widening call, before any device is touched.  *ker = WD_NONE: nothing to launch (an empty batch,
+// or K = 0 when accumulating).
+int check_widen(const mm_config_t *cfg, const mm::Problem &p, WidenKernel *ker) {
+  *ker = WD_NONE;
+  if (!valid_cfg(cfg)) return fail(MM_ERR_BAD_ARGUMENT, "invalid mm_config_t");
+  if (!widen_serves(*cfg))
+    return fail(MM_ERR_UNSUPPORTED, "widening serves half and int8_t with (Multiply, Add), under MM_PATH_AUTO or MM_PATH_ORDERED "
+                "(got dtype %d, map %d, reduce %d, path %d)", (int)cfg->dtype, (int)cfg->map_op, (int)cfg->reduce_op,
+                (int)cfg->path);
+  if (p.k == 0 && !p.seed) return fail(MM_ERR_BAD_ARGUMENT, "size_k must be positive");
+  if (empty_batch(p)) return MM_OK;
+  if (!p.c || (p.k && (!p.a || !p.b))) return fail(MM_ERR_BAD_ARGUMENT, "null matrix pointer");   // (K = 0: A, B unread)
+  if (int rc = check_stride_c(p)) return rc;
+  const size_t es = mm_dtype_size(cfg->dtype), ws = mm_dtype_size((mm_dtype_t)mm_widen_dtype(cfg->dtype));
+  if (outputs_overlap(p, es, nullptr, ws))
+    return fail(MM_ERR_BAD_ARGUMENT, "c overlaps a or b (bases %p, %p, %p)", p.a, p.b, p.c);
+  if (p.k == 0) return MM_OK;   // accumulating over no k: C keeps its value
+  *ker = widen_mfma_name(*cfg, p) ? WD_MFMA : WD_ORDERED;
+  // the matrix-core kernels move 16 bytes per lane of A and B, and C is written in 64-byte runs: every element's a, b and c
+  // 16-byte aligned, else widen_ordered summing in blocks: MM_PATH_AUTO's contract, bound included
+  const size_t strides = p.batch > 1 ? ((p.stride_a | p.stride_b) * es) | (p.stride_c * ws) : 0;
+  if (*ker == WD_MFMA && (!aligned16(p) || (strides & 15u) != 0)) *ker = WD_ORDERED_BLOCKED;
+  return MM_OK;
+}
+
+// Launches the batch as consecutive launches of at most batch_chunk() elements on `s`; the matrix-core kernel is resolved
+// once, on the whole batch, so an element's kernel does not depend on how the batch was chunked.
+int dispatch_widen(hipStream_t s, const mm_config_t &cfg, const mm::Problem &p, WidenKernel ker) {
+  (void)hipGetLastError();   // a stale error of the application's own calls must not be reported as this launch's
+  mm::Problem q = p;
+  if (q.batch == 1) q.stride_a = q.stride_b = q.stride_c = 0;
+  const bool i8 = cfg.dtype == MM_DTYPE_I8;
+  const int kernel = ker != WD_MFMA ? -1 : i8 ? mm::mfma_i8_wide_resolve(q) : mm::mfma_f16_wide_resolve(q);
+  const size_t ws = mm_dtype_size((mm_dtype_t)mm_widen_dtype(cfg.dtype));
+  return for_each_chunk(q, mm_dtype_size(cfg.dtype), batch_chunk(q), [&](mm::Problem r, unsigned e0) {
+    r.c = (char *)q.c + (size_t)e0 * q.stride_c * ws;   // C advances in its own type
+    const int e = ker != WD_MFMA ? mm::launch_widen_ordered(s, cfg.dtype, r, ker == WD_ORDERED_BLOCKED)
+                  : i8 ? mm::launch_mfma_i8_wide(s, r, kernel) : mm::launch_mfma_f16_wide(s, r, kernel);
+    return launch_status(e, cfg, "widen ", "widen kernel launch");
+  });
+}
+
 // The kernel of a family that is one kernel whatever the shape (the matrix-core families name theirs by shape)
 const char *family_name(Family f) {
   switch (f) {
@@ -1049,6 +1107,28 @@ int mm_gemm_logsumexp_launch(int device, const mm_config_t *cfg, const void *a, 
   LseKernel ker;
   if (int rc = check_lse(cfg, p, &ker)) return rc;
   return launch_timed(device, ker == LSE_NONE, elapsed_seconds, [&](hipStream_t s) { return dispatch_lse(s, *cfg, p, ker); });
+}
+
+int mm_widen_dtype(mm_dtype_t dtype) { return dtype == MM_DTYPE_F16 ? (int)MM_DTYPE_F32 : dtype == MM_DTYPE_I8 ? (int)MM_DTYPE_I32 : -1; }
+
+int mm_gemm_widen_enqueue(void *hip_stream, const mm_config_t *cfg, const void *a, const void *b, void *c, unsigned n,
+                          unsigned k, unsigned m, unsigned batch, size_t stride_a, size_t stride_b, size_t stride_c,
+                          int accumulate) {
+  mm::Problem p = batched_problem(cfg, a, b, c, n, k, m, batch, stride_a, stride_b, stride_c);
+  p.seed = accumulate != 0;
+  WidenKernel ker;
+  if (int rc = check_widen(cfg, p, &ker)) return rc;
+  return enqueue_on(hip_stream, ker == WD_NONE, [&](hipStream_t s) { return dispatch_widen(s, *cfg, p, ker); });
+}
+
+int mm_gemm_widen_launch(int device, const mm_config_t *cfg, const void *a, const void *b, void *c, unsigned n, unsigned k,
+                         unsigned m, unsigned batch, size_t stride_a, size_t stride_b, size_t stride_c, int accumulate,
+                         double *elapsed_seconds) {
+  mm::Problem p = batched_problem(cfg, a, b, c, n, k, m, batch, stride_a, stride_b, stride_c);
+  p.seed = accumulate != 0;
+  WidenKernel ker;
+  if (int rc = check_widen(cfg, p, &ker)) return rc;
+  return launch_timed(device, ker == WD_NONE, elapsed_seconds, [&](hipStream_t s) { return dispatch_widen(s, *cfg, p, ker); });
 }
 
 int mm_closure_enqueue(void *hip_stream, const mm_config_t *cfg, void *d, int *witness, unsigned n, unsigned batch,
@@ -1422,6 +1502,14 @@ const char *mm_kernel_name_logsumexp(const mm_config_t *cfg, unsigned n, unsigne
   if (ker == LSE_NONE) return "unsupported";
   if (bad_knob) return "invalid";
   return ker == LSE_HYBRID ? "lse_hybrid" : "lse_exact";
+}
+
+const char *mm_kernel_name_widen(const mm_config_t *cfg, unsigned n, unsigned k, unsigned m, unsigned batch) {
+  if (!valid_cfg(cfg)) return "invalid";
+  if (!widen_serves(*cfg)) return "unsupported";
+  const mm::Problem p = batched_problem(cfg, nullptr, nullptr, nullptr, n, k, m, batch ? batch : 1, 0, 0, 0);
+  const char *wide = widen_mfma_name(*cfg, p);   // the choice check_widen makes, before alignment
+  return wide ? wide : "widen_ordered";
 }
 
 const char *mm_kernel_name_closure(const mm_config_t *cfg, unsigned n, unsigned batch, int with_witness) {

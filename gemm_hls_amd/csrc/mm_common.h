@@ -118,6 +118,18 @@ const char *mfma_i8_batched_name(const Problem &p);
 int launch_mfma_f64_batched(hipStream_t s, const Problem &p, int resolved);
 int launch_mfma_f16_batched(hipStream_t s, const Problem &p, int resolved);
 int launch_mfma_i8_batched(hipStream_t s, const Problem &p, int resolved);
+// Widening (mm_gemm_widen_*): the kernel mfma_*_batched_name(p) names, instantiated with a wide C (int for int8_t, float for
+// half; p.c and p.stride_c are of that type) -- mm_mfma_i8_wide.hip, mm_mfma_f16_wide.hip.  resolve: -1 where the narrow
+// batched resolver names no kernel of this library; name: that kernel's name + "_wide", null for -1.
+int mfma_i8_wide_resolve(const Problem &p);
+int mfma_f16_wide_resolve(const Problem &p);
+const char *mfma_i8_wide_name(const Problem &p);
+const char *mfma_f16_wide_name(const Problem &p);
+int launch_mfma_i8_wide(hipStream_t s, const Problem &p, int resolved);
+int launch_mfma_f16_wide(hipStream_t s, const Problem &p, int resolved);
+// "widen_ordered" (mm_widen_ordered.hip): k ascending, one accumulator in the wide type, fully predicated; dtype is the operands'.
+// blocked (half only): the terms summed in blocks of k instead -- MM_PATH_AUTO's bound where a misaligned launch was demoted
+int launch_widen_ordered(hipStream_t s, mm_dtype_t dtype, const Problem &p, bool blocked);
 
 // Launchers (one translation unit each).  Return hipError_t as int; hipErrorNotSupported (801)
 // means "this family does not serve this (config, shape)".
@@ -335,6 +347,55 @@ __device__ __forceinline__ unsigned form_tile(PA &A, PB &B, PC &C, unsigned tile
                                               size_t stride_b, size_t stride_c) {
   if constexpr (F == Form::Single) return xcd_remap(blockIdx.x, tiles);
   else return batched_tile(A, B, C, tiles, batch, stride_a, stride_b, stride_c);
+}
+
+// ---- wide epilogue of the int8 / half matrix-core kernels (mm_gemm_widen_*) ------------------------------------------------
+// The accumulators leave in their own type (int, float), straight from the C/D register layout: a lane holds ONE column, so
+// each store instruction writes whole 64- or 128-byte runs of rows (DESIGN.md 3.10 for why not through LDS).  Form::Seeded
+// adds C's input value first, in the wide type; a lane reads exactly the elements it then writes.  Rows >= N and columns
+// >= M are masked.
+__device__ __forceinline__ int wide_add(int a, int b) { return (int)((unsigned)a + (unsigned)b); }   // mod 2^32
+__device__ __forceinline__ float wide_add(float a, float b) { return a + b; }
+
+// Registers of one column: register i of `acc` is row grow + row_of(i).  wide_seed_column adds C's input value to them,
+// wide_store_column stores them; a kernel seeds a whole block of accumulators before it stores them, so the loads are in flight together.
+template <int R, typename CT, typename V, typename RowOf>
+__device__ __forceinline__ void wide_seed_column(const CT *C, unsigned N, unsigned M, unsigned grow, unsigned gcol, V &acc, RowOf row_of) {
+  if (gcol >= M) return;
+#pragma unroll
+  for (int i = 0; i < R; ++i) {
+    const unsigned row = grow + row_of(i);
+    if (row < N) acc[i] = wide_add(acc[i], C[(size_t)row * M + gcol]);
+  }
+}
+template <int R, typename CT, typename V, typename RowOf>
+__device__ __forceinline__ void wide_store_column(CT *C, unsigned N, unsigned M, unsigned grow, unsigned gcol, const V &acc, RowOf row_of) {
+  if (gcol >= M) return;
+#pragma unroll
+  for (int i = 0; i < R; ++i) {
+    const unsigned row = grow + row_of(i);
+    if (row < N) C[(size_t)row * M + gcol] = acc[i];
+  }
+}
+// a 32 x 32 accumulator (32x32 instructions): lane = column lo + 32 * hi, register rr = row (rr & 3) + 8 * (rr >> 2) + 4 * hi;
+// a 16 x 16 accumulator (16x16 instructions): lane = column l15 + 16 * g, register i = row 4 * g + i.  grow includes 4 * hi / 4 * g.
+struct WideRows32 { __device__ unsigned operator()(int rr) const { return (unsigned)((rr & 3) + 8 * (rr >> 2)); } };
+struct WideRows16 { __device__ unsigned operator()(int i) const { return (unsigned)i; } };
+template <typename CT, typename V>
+__device__ __forceinline__ void wide_seed_32x32(const CT *C, unsigned N, unsigned M, unsigned grow, unsigned gcol, V &acc) {
+  wide_seed_column<16>(C, N, M, grow, gcol, acc, WideRows32{});
+}
+template <typename CT, typename V>
+__device__ __forceinline__ void wide_store_32x32(CT *C, unsigned N, unsigned M, unsigned grow, unsigned gcol, const V &acc) {
+  wide_store_column<16>(C, N, M, grow, gcol, acc, WideRows32{});
+}
+template <typename CT, typename V>
+__device__ __forceinline__ void wide_seed_16x16(const CT *C, unsigned N, unsigned M, unsigned grow, unsigned gcol, V &acc) {
+  wide_seed_column<4>(C, N, M, grow, gcol, acc, WideRows16{});
+}
+template <typename CT, typename V>
+__device__ __forceinline__ void wide_store_16x16(CT *C, unsigned N, unsigned M, unsigned grow, unsigned gcol, const V &acc) {
+  wide_store_column<4>(C, N, M, grow, gcol, acc, WideRows16{});
 }
 
 }  // namespace mm

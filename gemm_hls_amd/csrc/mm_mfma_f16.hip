@@ -34,71 +34,12 @@
 namespace mm {
 namespace {
 
-using h8 = __attribute__((ext_vector_type(8))) _Float16;
-using h4 = __attribute__((ext_vector_type(4))) _Float16;
-using f32x16 = __attribute__((ext_vector_type(16))) float;
-typedef short s4 __attribute__((vector_size(8)));
-typedef const __attribute__((address_space(1))) void *gptr_t;
-typedef __attribute__((address_space(3))) void *lptr_t;
-
-template <int WM_, int WN_, int TM_, int BK_ = 64, int NS_ = 2>
-struct GeoHT {
-  static constexpr int WM = WM_, WN = WN_, NS = NS_;
-  static constexpr int TM = TM_, TN = 4;
-  static constexpr int NW = WM * WN, THREADS = NW * 64;
-  static constexpr int BM = WM * TM * 32, BN = WN * TN * 32, BK = BK_;  // 256 x 256 x BK
-  static constexpr int CPR = BK * 2 / 16;                              // 16-B chunks per A row
-  static constexpr int SWZ_SHIFT = (CPR == 4) ? 2 : 1;
-  static_assert(BK == 32 || BK == 64, "BK");
-  static constexpr int BROW = BN * 2, BCH = BROW / 16;                 // B k-row bytes / chunks
-  static constexpr int A_BYTES = BM * BK * 2, B_BYTES = BK * BROW;
-  static constexpr int STAGE_BYTES = A_BYTES + B_BYTES;
-  static constexpr int EPI_BYTES = NW * TM * 32 * 256;  // epilogue staging: a [TM*32][128] half slice per wave
-  static constexpr int LDS_BYTES = NS * STAGE_BYTES > EPI_BYTES ? NS * STAGE_BYTES : EPI_BYTES;
-  static constexpr int NA = A_BYTES / 1024, NB = B_BYTES / 1024;
-  static constexpr int LA = NA / NW, LB = NB / NW;
-  static constexpr int KS = BK / 16;                                   // MFMA k-steps per slab
-  static_assert(NA % NW == 0 && NB % NW == 0, "DMA split");
-  static_assert(LDS_BYTES <= 160 * 1024, "LDS");
-  static_assert(BN == 256, "B swizzle / chunk math assumes 256-column slabs");
-};
-// slab64: workgroup 256 x 256 (or 128 x 256), wavefronts of 64 x 128 = 2 x 4 accumulators of 32 x 32 (32x32x16 instruction);
-// K slab = 64 halves (an A row is 128 B = 8 chunks of 16 B, swizzled with (row>>1)&7); A fragment: ds_read_b128 =
-// A[row = l&31][8 consecutive k at 8*(l>>5)] -- exactly the operand; one barrier per slab, fragments double-buffered.
-using GeoH = GeoHT<4, 2, 2>;   // 256 x 256, 8 wavefronts of 64 x 128 (2 per SIMD)
-using GeoHS = GeoHT<2, 2, 2>;            // 128 x 256, 4 wavefronts of 64 x 128: small / mid-size shapes
-using GeoHXS = GeoHT<2, 2, 1>;           // 64 x 256, 4 wavefronts of 32 x 128: below a round of the 128 x 256 tile (round 3)
-
-// LDS-DMA issued from inline asm.  hipcc waits vmcnt(0) before every ds_read_b64_tr_b16 that
-// follows a __builtin_amdgcn_global_load_lds (the transpose-read builtin carries no alias
-// information, so the pending-DMA hazard check is conservative), which would serialise the ring.
-// An asm DMA is invisible to that bookkeeping; its completion is tracked by the kernel's own
-// counted s_waitcnt vmcnt(N) + barrier.  M0 (LDS base of the DMA) is saved and restored inside the
-// same statement because the compiler owns it.
-__device__ __forceinline__ void dma16(const void *gsrc, unsigned lds_byte_addr) {
-  unsigned keep;
-  asm volatile(
-      "s_mov_b32 %0, m0\n\t"
-      "s_mov_b32 m0, %2\n\t"
-      "s_nop 0\n\t"
-      "global_load_lds_dwordx4 %1, off\n\t"
-      "s_mov_b32 m0, %0"
-      : "=&s"(keep)
-      : "v"(gsrc), "s"(lds_byte_addr)
-      : "memory");
-}
-
-__device__ __forceinline__ h8 join(s4 lo, s4 hi) {
-  union { s4 s[2]; h8 h; } u;
-  u.s[0] = lo;
-  u.s[1] = hi;
-  return u.h;
-}
-
 #include "mm_mfma_f16_kernels.inc"
 
 #undef MM_DMA_PIECE
 
+// (mm_mfma_f16_wide.hip finds its instantiations by these names: a kernel added or renamed here needs its twin there --
+// tests/test_widen_capi.py compares the tables)
 enum Kind { K_PP16, K_PP32, K_PPK32, K_PPK32_AT, K_SLAB64, K_SLAB64_AT, K_SLAB64_128, K_SLAB64_64, K_NONE };
 const char *const kNames[] = {"mfma_f16_256x256_pingpong_16x16x32", "mfma_f16_256x256_pingpong_32x32x16",
                               "mfma_f16_256x256_pingpong_k32", "mfma_f16_256x256_pingpong_k32_KxN",
@@ -157,19 +98,6 @@ static Kind resolve(const Problem &p) {
 }
 
 const char *mfma_f16_name(const Problem &p) { return kNames[resolve(p)]; }
-
-// One launch of the kernel KERN, an instantiation for form F: the problem at (a, b, c), or (F != Form::Single) p.batch copies of
-// the tile grid over the elements of p
-template <Form F, auto KERN>
-static int launch_tile(hipStream_t s, const Problem &p, unsigned bm, unsigned bn, unsigned threads, int lds) {
-  const unsigned tiles_n = (p.n + bm - 1) / bm, tiles_m = (p.m + bn - 1) / bn;
-  static unsigned long long configured = 0;   // one per instantiation of this function, so one per kernel
-  if (int e = ensure_dynamic_lds((const void *)KERN, lds, configured)) return e;
-  hipLaunchKernelGGL(KERN, dim3(tiles_n * tiles_m * (F == Form::Single ? 1u : p.batch)), dim3(threads), lds, s,
-                     (const _Float16 *)p.a, (const _Float16 *)p.b, (_Float16 *)p.c, p.n, p.k, p.m, tiles_n, tiles_m,
-                     band_rows(bm, bn, 1), F == Form::Single ? 1u : p.batch, p.stride_a, p.stride_b, p.stride_c);
-  return (int)hipGetLastError();
-}
 
 // The kernel of each Kind, in form F
 template <Form F>

@@ -1,9 +1,71 @@
-// The kernels of mm_mfma_f16.hip.  F (mm_common.h) is the form of each: the single-problem kernel, its strided-batched form,
-// or the batched form that accumulates into C.
-template <Form F, typename G, bool AT>
+// The kernels of mm_mfma_f16.hip and mm_mfma_f16_wide.hip, their geometries and their launch.  F (mm_common.h) is the form of
+// each: the single-problem kernel, its strided-batched form, or the batched form that accumulates into C.  CT is C's element
+// type: _Float16 -- the f32 sums rounded once on store -- or float, the sums themselves (mm_gemm_widen_*).
+using h8 = __attribute__((ext_vector_type(8))) _Float16;
+using h4 = __attribute__((ext_vector_type(4))) _Float16;
+using f32x16 = __attribute__((ext_vector_type(16))) float;
+typedef short s4 __attribute__((vector_size(8)));
+typedef const __attribute__((address_space(1))) void *gptr_t;
+typedef __attribute__((address_space(3))) void *lptr_t;
+
+template <int WM_, int WN_, int TM_, int BK_ = 64, int NS_ = 2>
+struct GeoHT {
+  static constexpr int WM = WM_, WN = WN_, NS = NS_;
+  static constexpr int TM = TM_, TN = 4;
+  static constexpr int NW = WM * WN, THREADS = NW * 64;
+  static constexpr int BM = WM * TM * 32, BN = WN * TN * 32, BK = BK_;  // 256 x 256 x BK
+  static constexpr int CPR = BK * 2 / 16;                              // 16-B chunks per A row
+  static constexpr int SWZ_SHIFT = (CPR == 4) ? 2 : 1;
+  static_assert(BK == 32 || BK == 64, "BK");
+  static constexpr int BROW = BN * 2, BCH = BROW / 16;                 // B k-row bytes / chunks
+  static constexpr int A_BYTES = BM * BK * 2, B_BYTES = BK * BROW;
+  static constexpr int STAGE_BYTES = A_BYTES + B_BYTES;
+  static constexpr int EPI_BYTES = NW * TM * 32 * 256;  // epilogue staging: a [TM*32][128] half slice per wave
+  static constexpr int LDS_BYTES = NS * STAGE_BYTES > EPI_BYTES ? NS * STAGE_BYTES : EPI_BYTES;
+  static constexpr int NA = A_BYTES / 1024, NB = B_BYTES / 1024;
+  static constexpr int LA = NA / NW, LB = NB / NW;
+  static constexpr int KS = BK / 16;                                   // MFMA k-steps per slab
+  static_assert(NA % NW == 0 && NB % NW == 0, "DMA split");
+  static_assert(LDS_BYTES <= 160 * 1024, "LDS");
+  static_assert(BN == 256, "B swizzle / chunk math assumes 256-column slabs");
+};
+// slab64: workgroup 256 x 256 (or 128 x 256), wavefronts of 64 x 128 = 2 x 4 accumulators of 32 x 32 (32x32x16 instruction);
+// K slab = 64 halves (an A row is 128 B = 8 chunks of 16 B, swizzled with (row>>1)&7); A fragment: ds_read_b128 =
+// A[row = l&31][8 consecutive k at 8*(l>>5)] -- exactly the operand; one barrier per slab, fragments double-buffered.
+using GeoH = GeoHT<4, 2, 2>;   // 256 x 256, 8 wavefronts of 64 x 128 (2 per SIMD)
+using GeoHS = GeoHT<2, 2, 2>;            // 128 x 256, 4 wavefronts of 64 x 128: small / mid-size shapes
+using GeoHXS = GeoHT<2, 2, 1>;           // 64 x 256, 4 wavefronts of 32 x 128: below a round of the 128 x 256 tile (round 3)
+
+// LDS-DMA issued from inline asm.  hipcc waits vmcnt(0) before every ds_read_b64_tr_b16 that
+// follows a __builtin_amdgcn_global_load_lds (the transpose-read builtin carries no alias
+// information, so the pending-DMA hazard check is conservative), which would serialise the ring.
+// An asm DMA is invisible to that bookkeeping; its completion is tracked by the kernel's own
+// counted s_waitcnt vmcnt(N) + barrier.  M0 (LDS base of the DMA) is saved and restored inside the
+// same statement because the compiler owns it.
+__device__ __forceinline__ void dma16(const void *gsrc, unsigned lds_byte_addr) {
+  unsigned keep;
+  asm volatile(
+      "s_mov_b32 %0, m0\n\t"
+      "s_mov_b32 m0, %2\n\t"
+      "s_nop 0\n\t"
+      "global_load_lds_dwordx4 %1, off\n\t"
+      "s_mov_b32 m0, %0"
+      : "=&s"(keep)
+      : "v"(gsrc), "s"(lds_byte_addr)
+      : "memory");
+}
+
+__device__ __forceinline__ h8 join(s4 lo, s4 hi) {
+  union { s4 s[2]; h8 h; } u;
+  u.s[0] = lo;
+  u.s[1] = hi;
+  return u.h;
+}
+
+template <Form F, typename G, bool AT, typename CT = _Float16>
 __global__ __launch_bounds__(G::THREADS) void mfma_f16_kernel(const _Float16 *__restrict__ A,
                                                                  const _Float16 *__restrict__ B,
-                                                                 _Float16 *__restrict__ C, unsigned N, unsigned K,
+                                                                 CT *__restrict__ C, unsigned N, unsigned K,
                                                                  unsigned M, unsigned tiles_n, unsigned tiles_m, unsigned kBand,
                                                                  unsigned batch, size_t stride_a, size_t stride_b, size_t stride_c) {
   constexpr int TM = G::TM, TN = G::TN, BK = G::BK, NS = G::NS, CPR = G::CPR;
@@ -166,7 +228,20 @@ __global__ __launch_bounds__(G::THREADS) void mfma_f16_kernel(const _Float16 *__
   // LDS ring so that global stores are 16 B per lane and 256 contiguous bytes per row instead of
   // one half per lane (the MFMA result layout gives a lane ONE column of 16 rows).
   __builtin_amdgcn_s_barrier();  // every wave has finished reading the last slab
-  {
+  if constexpr (sizeof(CT) == 4) {
+    // wide output (CT is the accumulators' type): straight from the C/D registers, one 32-row block at a time, its seeds
+    // all read before its stores
+    const unsigned wrow = row0 + wm * (TM * 32) + 4 * hi, wcol = col0 + wn * 128 + lo;
+#pragma unroll
+    for (int mi = 0; mi < TM; ++mi) {
+      if constexpr (F == Form::Seeded) {
+#pragma unroll
+        for (int ni = 0; ni < TN; ++ni) wide_seed_32x32(C, N, M, wrow + mi * 32, wcol + ni * 32, acc[mi][ni]);
+      }
+#pragma unroll
+      for (int ni = 0; ni < TN; ++ni) wide_store_32x32(C, N, M, wrow + mi * 32, wcol + ni * 32, acc[mi][ni]);
+    }
+  } else {
     constexpr int ROWS = TM * 32;                       // rows of this wave's tile, 128 columns = 256 B each
     char *slice = smem + wave * (ROWS * 256);
     if constexpr (F == Form::Seeded) {
@@ -245,10 +320,10 @@ struct GeoPP {
 // one LDS-DMA piece: 64 lanes x 16 B from (uniform base + per-lane 32-bit offset) to LDS at m0
 #define MM_DMA_PIECE(vo, sb, la) "s_mov_b32 m0, " la "\n\ts_nop 0\n\tglobal_load_lds_dwordx4 " vo ", " sb "\n\t"
 
-template <Form F, bool AT>  // AT: A stored K x N (MM_TRANSPOSED_A): the A slab is staged and gathered exactly like B's
+template <Form F, bool AT, typename CT = _Float16>  // AT: A stored K x N (MM_TRANSPOSED_A): the A slab is staged and gathered exactly like B's
 __global__ __launch_bounds__(GeoPP::THREADS) void mfma_f16_pp_kernel(const _Float16 *__restrict__ A,
                                                                        const _Float16 *__restrict__ B,
-                                                                       _Float16 *__restrict__ C, unsigned N, unsigned K,
+                                                                       CT *__restrict__ C, unsigned N, unsigned K,
                                                                        unsigned M, unsigned tiles_n, unsigned tiles_m,
                                                                        unsigned kBand, unsigned batch, size_t stride_a,
                                                                        size_t stride_b, size_t stride_c) {
@@ -380,7 +455,20 @@ __global__ __launch_bounds__(GeoPP::THREADS) void mfma_f16_pp_kernel(const _Floa
 
   // ---- epilogue: one rounding f32 -> binary16, staged through this wave's 16 KiB slice of the ring
   //      (C/D of the 16x16 form: column l15, rows 4*g + i)
-  {
+  if constexpr (sizeof(CT) == 4) {
+    // wide output (CT is the accumulators' type): straight from the C/D registers, every seed read before any store
+    const unsigned wrow = row0 + wm * 128 + 4 * g, wcol = col0 + wn * 64 + l15;
+    if constexpr (F == Form::Seeded) {
+#pragma unroll
+      for (int rb = 0; rb < RB; ++rb)
+#pragma unroll
+        for (int nb = 0; nb < NB; ++nb) wide_seed_16x16(C, N, M, wrow + rb * 16, wcol + nb * 16, acc[rb][nb]);
+    }
+#pragma unroll
+    for (int rb = 0; rb < RB; ++rb)
+#pragma unroll
+      for (int nb = 0; nb < NB; ++nb) wide_store_16x16(C, N, M, wrow + rb * 16, wcol + nb * 16, acc[rb][nb]);
+  } else {
     char *slice = smem + wave * (128 * 128);
     if constexpr (F == Form::Seeded) {
       // accumulate: C's tile enters the slice in the coalesced store layout (a lane reads the 16 bytes it later writes back),
@@ -440,10 +528,10 @@ struct GeoPP2 {
   static constexpr int BROW = BN * 2;
 };
 
-template <Form F>
+template <Form F, typename CT = _Float16>
 __global__ __launch_bounds__(GeoPP2::THREADS) void mfma_f16_pp2_kernel(const _Float16 *__restrict__ A,
                                                                          const _Float16 *__restrict__ B,
-                                                                         _Float16 *__restrict__ C, unsigned N, unsigned K,
+                                                                         CT *__restrict__ C, unsigned N, unsigned K,
                                                                          unsigned M, unsigned tiles_n, unsigned tiles_m,
                                                                          unsigned kBand, unsigned batch, size_t stride_a,
                                                                          size_t stride_b, size_t stride_c) {
@@ -590,7 +678,20 @@ __global__ __launch_bounds__(GeoPP2::THREADS) void mfma_f16_pp2_kernel(const _Fl
   if (!shifted) sync();
   sync();
 
-  {
+  if constexpr (sizeof(CT) == 4) {
+    // wide output (CT is the accumulators' type): straight from the C/D registers, one 32-row block at a time, its seeds
+    // all read before its stores
+    const unsigned wrow = row0 + wm * 128 + 4 * hi, wcol = col0 + wn * 64 + lo;
+#pragma unroll
+    for (int mi = 0; mi < TM; ++mi) {
+      if constexpr (F == Form::Seeded) {
+#pragma unroll
+        for (int ni = 0; ni < TN; ++ni) wide_seed_32x32(C, N, M, wrow + mi * 32, wcol + ni * 32, acc[mi][ni]);
+      }
+#pragma unroll
+      for (int ni = 0; ni < TN; ++ni) wide_store_32x32(C, N, M, wrow + mi * 32, wcol + ni * 32, acc[mi][ni]);
+    }
+  } else {
     char *slice = smem + wave * (128 * 128);
     if constexpr (F == Form::Seeded) {
       // accumulate: C's tile enters the slice in the coalesced store layout (a lane reads the 16 bytes it later writes back),
@@ -650,10 +751,10 @@ __global__ __launch_bounds__(GeoPP2::THREADS) void mfma_f16_pp2_kernel(const _Fl
 //     half-wave touches fall into 8 different 32-byte octants of the 256-byte bank row.
 // Accumulation order per output element: k ascending in steps of 32, inside an MFMA the hardware's order;
 // results are within the same 1-ulp-of-binary16 bound as the 32x32x16 kernels (not bit-identical to them).
-template <Form F>
+template <Form F, typename CT = _Float16>
 __global__ __launch_bounds__(GeoPP2::THREADS) void mfma_f16_pp2s_kernel(const _Float16 *__restrict__ A,
                                                                           const _Float16 *__restrict__ B,
-                                                                          _Float16 *__restrict__ C, unsigned N, unsigned K,
+                                                                          CT *__restrict__ C, unsigned N, unsigned K,
                                                                           unsigned M, unsigned tiles_n, unsigned tiles_m,
                                                                           unsigned kBand, unsigned batch, size_t stride_a,
                                                                           size_t stride_b, size_t stride_c) {
@@ -788,7 +889,20 @@ __global__ __launch_bounds__(GeoPP2::THREADS) void mfma_f16_pp2s_kernel(const _F
   if (!shifted) sync();
   sync();
 
-  {  // epilogue: C/D of the 16x16 form: column l15, rows 4*g + i
+  if constexpr (sizeof(CT) == 4) {
+    // wide output (CT is the accumulators' type): straight from the C/D registers, every seed read before any store
+    const unsigned wrow = row0 + wm * 128 + 4 * g, wcol = col0 + wn * 64 + l15;
+    if constexpr (F == Form::Seeded) {
+#pragma unroll
+      for (int rb = 0; rb < RB; ++rb)
+#pragma unroll
+        for (int nb = 0; nb < NB; ++nb) wide_seed_16x16(C, N, M, wrow + rb * 16, wcol + nb * 16, acc[rb][nb]);
+    }
+#pragma unroll
+    for (int rb = 0; rb < RB; ++rb)
+#pragma unroll
+      for (int nb = 0; nb < NB; ++nb) wide_store_16x16(C, N, M, wrow + rb * 16, wcol + nb * 16, acc[rb][nb]);
+  } else {  // epilogue: C/D of the 16x16 form: column l15, rows 4*g + i
     char *slice = smem + wave * (128 * 128);
     if constexpr (F == Form::Seeded) {
       // accumulate: C's tile enters the slice in the coalesced store layout (a lane reads the 16 bytes it later writes back),
@@ -826,4 +940,17 @@ __global__ __launch_bounds__(GeoPP2::THREADS) void mfma_f16_pp2s_kernel(const _F
       if (grow < N && gcol < M) *(u32x4 *)(C + (size_t)grow * M + gcol) = v;
     }
   }
+}
+
+// One launch of the kernel KERN, an instantiation for form F: the problem at (a, b, c), or (F != Form::Single) p.batch copies of
+// the tile grid over the elements of p
+template <Form F, auto KERN, typename CT = _Float16>
+static int launch_tile(hipStream_t s, const Problem &p, unsigned bm, unsigned bn, unsigned threads, int lds) {
+  const unsigned tiles_n = (p.n + bm - 1) / bm, tiles_m = (p.m + bn - 1) / bn;
+  static unsigned long long configured = 0;   // one per instantiation of this function, so one per kernel
+  if (int e = ensure_dynamic_lds((const void *)KERN, lds, configured)) return e;
+  hipLaunchKernelGGL(KERN, dim3(tiles_n * tiles_m * (F == Form::Single ? 1u : p.batch)), dim3(threads), lds, s,
+                     (const _Float16 *)p.a, (const _Float16 *)p.b, (CT *)p.c, p.n, p.k, p.m, tiles_n, tiles_m,
+                     band_rows(bm, bn, 1), F == Form::Single ? 1u : p.batch, p.stride_a, p.stride_b, p.stride_c);
+  return (int)hipGetLastError();
 }

@@ -30,58 +30,11 @@
 namespace mm {
 namespace {
 
-using i32x4 = __attribute__((ext_vector_type(4))) int;
-using i32x16 = __attribute__((ext_vector_type(16))) int;
-typedef int v2i __attribute__((vector_size(8)));
-typedef __attribute__((address_space(3))) void *lptr_t;
-
-template <int WM_, int WN_, int TM_>
-struct GeoI8T {
-  static constexpr int WM = WM_, WN = WN_, NS = 2, TM = TM_, TN = 4;
-  static constexpr int NW = WM * WN, THREADS = NW * 64;
-  static constexpr int BM = WM * TM * 32, BN = WN * TN * 32, BK = 128;   // BK in elements == bytes
-  static_assert(BN == 256, "B swizzle / chunk math assumes 256-column slabs");
-  static constexpr int CPR = 8;                                // 16-B chunks per A row
-  static constexpr int BROW = BN, BCH = BROW / 16;             // B k-row bytes / chunks
-  static constexpr int A_BYTES = BM * BK, B_BYTES = BK * BROW;
-  static constexpr int STAGE_BYTES = A_BYTES + B_BYTES, LDS_BYTES = NS * STAGE_BYTES;
-  static constexpr int NA = A_BYTES / 1024, NB = B_BYTES / 1024;
-  static constexpr int LA = NA / NW, LB = NB / NW;
-  static constexpr int KS = BK / 32;                           // MFMA k-steps per slab
-};
-using GeoI8 = GeoI8T<4, 2, 2>;    // 256 x 256, 8 wavefronts of 64 x 128
-using GeoI8S = GeoI8T<2, 2, 1>;   // 64 x 256, 4 wavefronts of 32 x 128: problems below a round of the 256 x 256 tile (round 3; row-major A only)
-
-// asm LDS-DMA (see mm_mfma_f16.hip: transpose-read builtins make hipcc drain builtin DMAs)
-__device__ __forceinline__ void dma16(const void *gsrc, unsigned lds_byte_addr) {
-  unsigned keep;
-  asm volatile(
-      "s_mov_b32 %0, m0\n\t"
-      "s_mov_b32 m0, %2\n\t"
-      "s_nop 0\n\t"
-      "global_load_lds_dwordx4 %1, off\n\t"
-      "s_mov_b32 m0, %0"
-      : "=&s"(keep)
-      : "v"(gsrc), "s"(lds_byte_addr)
-      : "memory");
-}
-
-__device__ __forceinline__ i32x4 join(v2i lo, v2i hi) {
-  i32x4 r;
-  r[0] = lo[0]; r[1] = lo[1]; r[2] = hi[0]; r[3] = hi[1];
-  return r;
-}
-
-// Accumulate (Form::Seeded): the seed plus the i32 sum, low 8 bits -- which only the low 8 bits of either
-// decide, so the two C images are added bytewise, mod 2^8 per byte (sign or zero extension of the seed does not matter).
-__device__ __forceinline__ __attribute__((ext_vector_type(4))) unsigned add_bytes(__attribute__((ext_vector_type(4))) unsigned x,
-                                                                                 __attribute__((ext_vector_type(4))) unsigned y) {
-  return ((x & 0x7f7f7f7fu) + (y & 0x7f7f7f7fu)) ^ ((x ^ y) & 0x80808080u);
-}
-
 #include "mm_mfma_i8_kernels.inc"
 #undef MM_DMA_PIECE
 
+// (mm_mfma_i8_wide.hip finds its instantiations by these names: a kernel added or renamed here needs its twin there --
+// tests/test_widen_capi.py compares the tables)
 enum Kind { K_PP16, K_PP32, K_PPK64, K_PPK64_AT, K_SLAB128, K_SLAB128_AT, K_SLAB128_64, K_NONE };
 const char *const kNames[] = {"mfma_i8_256x256_pingpong_16x16x64", "mfma_i8_256x256_pingpong_32x32x32", "mfma_i8_256x256_pingpong_k64",
                               "mfma_i8_256x256_pingpong_k64_KxN", "mfma_i8_256x256x128_slab128", "mfma_i8_256x256x128_slab128_KxN",
@@ -137,19 +90,6 @@ static Kind resolve(const Problem &p) {
 }
 
 const char *mfma_i8_name(const Problem &p) { return kNames[resolve(p)]; }
-
-// One launch of the kernel KERN, an instantiation for form F: the problem at (a, b, c), or (F != Form::Single) p.batch copies of
-// the tile grid over the elements of p
-template <Form F, auto KERN>
-static int launch_tile(hipStream_t s, const Problem &p, unsigned threads, int lds, unsigned bm = 256) {
-  const unsigned tiles_n = (p.n + bm - 1) / bm, tiles_m = (p.m + 255) / 256;
-  static unsigned long long configured = 0;   // one per instantiation of this function, so one per kernel
-  if (int e = ensure_dynamic_lds((const void *)KERN, lds, configured)) return e;
-  hipLaunchKernelGGL(KERN, dim3(tiles_n * tiles_m * (F == Form::Single ? 1u : p.batch)), dim3(threads), lds, s,
-                     (const signed char *)p.a, (const signed char *)p.b, (signed char *)p.c, p.n, p.k, p.m, tiles_n, tiles_m,
-                     band_rows(bm, 256, 1), F == Form::Single ? 1u : p.batch, p.stride_a, p.stride_b, p.stride_c);
-  return (int)hipGetLastError();
-}
 
 // The kernel of each Kind, in form F
 template <Form F>

@@ -1,9 +1,59 @@
-// The kernels of mm_mfma_i8.hip.  F (mm_common.h) is the form of each: the single-problem kernel, its strided-batched form,
-// or the batched form that accumulates into C.
-template <Form F, typename G, bool AT>
+// The kernels of mm_mfma_i8.hip and mm_mfma_i8_wide.hip, their geometries and their launch.  F (mm_common.h) is the form of each:
+// the single-problem kernel, its strided-batched form, or the batched form that accumulates into C.  CT is C's element type:
+// signed char -- the low 8 bits of the i32 sums, the reference's contract -- or int, the sums themselves (mm_gemm_widen_*).
+using i32x4 = __attribute__((ext_vector_type(4))) int;
+using i32x16 = __attribute__((ext_vector_type(16))) int;
+typedef int v2i __attribute__((vector_size(8)));
+typedef __attribute__((address_space(3))) void *lptr_t;
+
+template <int WM_, int WN_, int TM_>
+struct GeoI8T {
+  static constexpr int WM = WM_, WN = WN_, NS = 2, TM = TM_, TN = 4;
+  static constexpr int NW = WM * WN, THREADS = NW * 64;
+  static constexpr int BM = WM * TM * 32, BN = WN * TN * 32, BK = 128;   // BK in elements == bytes
+  static_assert(BN == 256, "B swizzle / chunk math assumes 256-column slabs");
+  static constexpr int CPR = 8;                                // 16-B chunks per A row
+  static constexpr int BROW = BN, BCH = BROW / 16;             // B k-row bytes / chunks
+  static constexpr int A_BYTES = BM * BK, B_BYTES = BK * BROW;
+  static constexpr int STAGE_BYTES = A_BYTES + B_BYTES, LDS_BYTES = NS * STAGE_BYTES;
+  static constexpr int NA = A_BYTES / 1024, NB = B_BYTES / 1024;
+  static constexpr int LA = NA / NW, LB = NB / NW;
+  static constexpr int KS = BK / 32;                           // MFMA k-steps per slab
+};
+using GeoI8 = GeoI8T<4, 2, 2>;    // 256 x 256, 8 wavefronts of 64 x 128
+using GeoI8S = GeoI8T<2, 2, 1>;   // 64 x 256, 4 wavefronts of 32 x 128: problems below a round of the 256 x 256 tile (round 3; row-major A only)
+
+// asm LDS-DMA (see mm_mfma_f16.hip: transpose-read builtins make hipcc drain builtin DMAs)
+__device__ __forceinline__ void dma16(const void *gsrc, unsigned lds_byte_addr) {
+  unsigned keep;
+  asm volatile(
+      "s_mov_b32 %0, m0\n\t"
+      "s_mov_b32 m0, %2\n\t"
+      "s_nop 0\n\t"
+      "global_load_lds_dwordx4 %1, off\n\t"
+      "s_mov_b32 m0, %0"
+      : "=&s"(keep)
+      : "v"(gsrc), "s"(lds_byte_addr)
+      : "memory");
+}
+
+__device__ __forceinline__ i32x4 join(v2i lo, v2i hi) {
+  i32x4 r;
+  r[0] = lo[0]; r[1] = lo[1]; r[2] = hi[0]; r[3] = hi[1];
+  return r;
+}
+
+// Accumulate (Form::Seeded): the seed plus the i32 sum, low 8 bits -- which only the low 8 bits of either
+// decide, so the two C images are added bytewise, mod 2^8 per byte (sign or zero extension of the seed does not matter).
+__device__ __forceinline__ __attribute__((ext_vector_type(4))) unsigned add_bytes(__attribute__((ext_vector_type(4))) unsigned x,
+                                                                                 __attribute__((ext_vector_type(4))) unsigned y) {
+  return ((x & 0x7f7f7f7fu) + (y & 0x7f7f7f7fu)) ^ ((x ^ y) & 0x80808080u);
+}
+
+template <Form F, typename G, bool AT, typename CT = signed char>
 __global__ __launch_bounds__(G::THREADS) void mfma_i8_kernel(const signed char *__restrict__ A,
                                                                  const signed char *__restrict__ B,
-                                                                 signed char *__restrict__ C, unsigned N, unsigned K,
+                                                                 CT *__restrict__ C, unsigned N, unsigned K,
                                                                  unsigned M, unsigned tiles_n, unsigned tiles_m,
                                                                  unsigned kBand, unsigned batch, size_t stride_a,
                                                                  size_t stride_b, size_t stride_c) {
@@ -156,7 +206,20 @@ __global__ __launch_bounds__(G::THREADS) void mfma_i8_kernel(const signed char *
 
   // ---- epilogue: low 8 bits of the i32 sums, through the wave's LDS slice, 16-B global stores ----
   __builtin_amdgcn_s_barrier();
-  {
+  if constexpr (sizeof(CT) == 4) {
+    // wide output (CT is the accumulators' type): straight from the C/D registers, one 32-row block at a time, its seeds
+    // all read before its stores
+    const unsigned wrow = row0 + wm * (TM * 32) + 4 * hi, wcol = col0 + wn * 128 + lo;
+#pragma unroll
+    for (int mi = 0; mi < TM; ++mi) {
+      if constexpr (F == Form::Seeded) {
+#pragma unroll
+        for (int ni = 0; ni < TN; ++ni) wide_seed_32x32(C, N, M, wrow + mi * 32, wcol + ni * 32, acc[mi][ni]);
+      }
+#pragma unroll
+      for (int ni = 0; ni < TN; ++ni) wide_store_32x32(C, N, M, wrow + mi * 32, wcol + ni * 32, acc[mi][ni]);
+    }
+  } else {
     constexpr int ROWS = TM * 32;
     char *slice = smem + wave * (ROWS * 128);
 #pragma unroll
@@ -203,10 +266,10 @@ struct GeoI8PP {
 };
 #define MM_DMA_PIECE(vo, sb, la) "s_mov_b32 m0, " la "\n\ts_nop 0\n\tglobal_load_lds_dwordx4 " vo ", " sb "\n\t"
 
-template <Form F, bool AT>  // AT: A stored K x N, staged and gathered like B
+template <Form F, bool AT, typename CT = signed char>  // AT: A stored K x N, staged and gathered like B
 __global__ __launch_bounds__(GeoI8PP::THREADS) void mfma_i8_pp_kernel(const signed char *__restrict__ A,
                                                                         const signed char *__restrict__ B,
-                                                                        signed char *__restrict__ C, unsigned N, unsigned K,
+                                                                        CT *__restrict__ C, unsigned N, unsigned K,
                                                                         unsigned M, unsigned tiles_n, unsigned tiles_m,
                                                                         unsigned kBand, unsigned batch, size_t stride_a,
                                                                         size_t stride_b, size_t stride_c) {
@@ -326,7 +389,20 @@ __global__ __launch_bounds__(GeoI8PP::THREADS) void mfma_i8_pp_kernel(const sign
   sync();
 
   // epilogue: low 8 bits of the i32 sums through this wave's 8 KiB slice, 16-B global stores (C/D: column l15, rows 4*g + i)
-  {
+  if constexpr (sizeof(CT) == 4) {
+    // wide output (CT is the accumulators' type): straight from the C/D registers, every seed read before any store
+    const unsigned wrow = row0 + wm * 128 + 4 * g, wcol = col0 + wn * 64 + l15;
+    if constexpr (F == Form::Seeded) {
+#pragma unroll
+      for (int rb = 0; rb < RB; ++rb)
+#pragma unroll
+        for (int nb = 0; nb < NB; ++nb) wide_seed_16x16(C, N, M, wrow + rb * 16, wcol + nb * 16, acc[rb][nb]);
+    }
+#pragma unroll
+    for (int rb = 0; rb < RB; ++rb)
+#pragma unroll
+      for (int nb = 0; nb < NB; ++nb) wide_store_16x16(C, N, M, wrow + rb * 16, wcol + nb * 16, acc[rb][nb]);
+  } else {
     char *slice = smem + wave * (128 * 64);
 #pragma unroll
     for (int rb = 0; rb < RB; ++rb)
@@ -363,10 +439,10 @@ struct GeoI8PP2 {
   static constexpr int BROW = BN;
 };
 
-template <Form F>
+template <Form F, typename CT = signed char>
 __global__ __launch_bounds__(GeoI8PP2::THREADS) void mfma_i8_pp2_kernel(const signed char *__restrict__ A,
                                                                          const signed char *__restrict__ B,
-                                                                         signed char *__restrict__ C, unsigned N, unsigned K,
+                                                                         CT *__restrict__ C, unsigned N, unsigned K,
                                                                          unsigned M, unsigned tiles_n, unsigned tiles_m,
                                                                          unsigned kBand, unsigned batch, size_t stride_a,
                                                                          size_t stride_b, size_t stride_c) {
@@ -501,7 +577,20 @@ __global__ __launch_bounds__(GeoI8PP2::THREADS) void mfma_i8_pp2_kernel(const si
   if (!shifted) sync();
   sync();
 
-  {
+  if constexpr (sizeof(CT) == 4) {
+    // wide output (CT is the accumulators' type): straight from the C/D registers, one 32-row block at a time, its seeds
+    // all read before its stores
+    const unsigned wrow = row0 + wm * 128 + 4 * hi, wcol = col0 + wn * 64 + lo;
+#pragma unroll
+    for (int mi = 0; mi < TM; ++mi) {
+      if constexpr (F == Form::Seeded) {
+#pragma unroll
+        for (int ni = 0; ni < TN; ++ni) wide_seed_32x32(C, N, M, wrow + mi * 32, wcol + ni * 32, acc[mi][ni]);
+      }
+#pragma unroll
+      for (int ni = 0; ni < TN; ++ni) wide_store_32x32(C, N, M, wrow + mi * 32, wcol + ni * 32, acc[mi][ni]);
+    }
+  } else {
     char *slice = smem + wave * (128 * 64);
 #pragma unroll
     for (int mi = 0; mi < TM; ++mi)
@@ -540,10 +629,10 @@ __global__ __launch_bounds__(GeoI8PP2::THREADS) void mfma_i8_pp2_kernel(const si
 // instead of in column by 16, so the chunk index is XORed with ((k&7)<<1) | ((k>>4)&1): the 16 k-rows a half-wave
 // touches fall into the 16 different chunks of the 256-byte bank row.  Integer sums: bit-identical to every
 // other schedule and to Naive.
-template <Form F>
+template <Form F, typename CT = signed char>
 __global__ __launch_bounds__(GeoI8PP2::THREADS) void mfma_i8_pp2s_kernel(const signed char *__restrict__ A,
                                                                           const signed char *__restrict__ B,
-                                                                          signed char *__restrict__ C, unsigned N, unsigned K,
+                                                                          CT *__restrict__ C, unsigned N, unsigned K,
                                                                           unsigned M, unsigned tiles_n, unsigned tiles_m,
                                                                           unsigned kBand, unsigned batch, size_t stride_a,
                                                                           size_t stride_b, size_t stride_c) {
@@ -672,7 +761,20 @@ __global__ __launch_bounds__(GeoI8PP2::THREADS) void mfma_i8_pp2s_kernel(const s
   if (!shifted) sync();
   sync();
 
-  {  // C/D of the 16x16 form: column l15, rows 4*g + i
+  if constexpr (sizeof(CT) == 4) {
+    // wide output (CT is the accumulators' type): straight from the C/D registers, every seed read before any store
+    const unsigned wrow = row0 + wm * 128 + 4 * g, wcol = col0 + wn * 64 + l15;
+    if constexpr (F == Form::Seeded) {
+#pragma unroll
+      for (int rb = 0; rb < RB; ++rb)
+#pragma unroll
+        for (int nb = 0; nb < NB; ++nb) wide_seed_16x16(C, N, M, wrow + rb * 16, wcol + nb * 16, acc[rb][nb]);
+    }
+#pragma unroll
+    for (int rb = 0; rb < RB; ++rb)
+#pragma unroll
+      for (int nb = 0; nb < NB; ++nb) wide_store_16x16(C, N, M, wrow + rb * 16, wcol + nb * 16, acc[rb][nb]);
+  } else {  // C/D of the 16x16 form: column l15, rows 4*g + i
     char *slice = smem + wave * (128 * 64);
 #pragma unroll
     for (int rb = 0; rb < RB; ++rb)
@@ -696,4 +798,17 @@ __global__ __launch_bounds__(GeoI8PP2::THREADS) void mfma_i8_pp2s_kernel(const s
       }
     }
   }
+}
+
+// One launch of the kernel KERN, an instantiation for form F: the problem at (a, b, c), or (F != Form::Single) p.batch copies of
+// the tile grid over the elements of p
+template <Form F, auto KERN, typename CT = signed char>
+static int launch_tile(hipStream_t s, const Problem &p, unsigned threads, int lds, unsigned bm = 256) {
+  const unsigned tiles_n = (p.n + bm - 1) / bm, tiles_m = (p.m + 255) / 256;
+  static unsigned long long configured = 0;   // one per instantiation of this function, so one per kernel
+  if (int e = ensure_dynamic_lds((const void *)KERN, lds, configured)) return e;
+  hipLaunchKernelGGL(KERN, dim3(tiles_n * tiles_m * (F == Form::Single ? 1u : p.batch)), dim3(threads), lds, s,
+                     (const signed char *)p.a, (const signed char *)p.b, (CT *)p.c, p.n, p.k, p.m, tiles_n, tiles_m,
+                     band_rows(bm, 256, 1), F == Form::Single ? 1u : p.batch, p.stride_a, p.stride_b, p.stride_c);
+  return (int)hipGetLastError();
 }

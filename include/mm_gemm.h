@@ -307,6 +307,58 @@ int mm_gemm_logsumexp_launch(int device, const mm_config_t *cfg, const void *a_d
 const char *mm_kernel_name_logsumexp(const mm_config_t *cfg, unsigned size_n, unsigned size_k, unsigned size_m,
                                      unsigned batch);
 
+/* Widening product: the matrix cores' own sums.  cfg->dtype is the OPERAND type, half or int8_t; C has the type
+ * mm_widen_dtype() names -- float for half, int for int8_t -- and cfg is otherwise (Multiply, Add).  The narrow entry points keep
+ * the reference's single Data_t: they store (int8_t)sum, defined mod 2^8 only, and (half)sum, 11 of the 24 bits the
+ * accumulator holds, rounded again on every pass of a K-split through mm_gemm_accumulate_*.  Here nothing is discarded.
+ * For output (e, i, j) of a strided batch, with acc's start C's input value when accumulating and 0 otherwise:
+ *   int8_t -> int    C = start + sum_k (int)A[e,i,k] * (int)B[e,k,j], taken mod 2^32: the same bits on every kernel and path,
+ *                    for every batch position and chunking.  No wrap can occur in the plain form while K <= 131071
+ *                    (131071 * 2^14 < 2^31).
+ *   half -> float    MM_PATH_ORDERED: acc = start; for k ascending: acc = acc + (float)a * (float)b in f32.  A product of two
+ *                    binary16 values is exact in f32, so fused and unfused evaluation give the same bits and a float32 loop
+ *                    on the host reproduces C bit for bit.
+ *                    MM_PATH_AUTO: exact products, f32 accumulation in an unspecified fixed order, NO rounding on store:
+ *                    |C - C*| <= 1e-6 (|C_in| + |A||B|)_ij -- the f32-accumulation term of the half family's bound without
+ *                    its 2^-11 store rounding.  The same bits on every run, independent of batch position and chunking.  In
+ *                    the plain form, rounding C once to binary16 gives bit for bit what mm_gemm_batched_launch returns for
+ *                    the same operands: the same kernel and schedule with a different store.  A launch demoted for
+ *                    misalignment (below) sums the same terms in blocks of k and keeps this bound.  One exception, stated
+ *                    because it is one: a SHAPE the matrix cores do not take (K % 16 != 0 or M % 8 != 0) runs k ascending
+ *                    like MM_PATH_ORDERED -- the order of the narrow call's own fallback on that shape, so that rounding C
+ *                    to binary16 still gives the narrow call's bits -- and is bounded by (K - 1) 2^-24 (|C_in| + |A||B|); it
+ *                    stays within 1e-6 while K is a few hundred (1.02e-6 was measured at K = 512 on same-sign operands).
+ *   Non-finite half operands: the result follows IEEE arithmetic on the f32 sum.
+ * uint8_t is refused on purpose: the signed-int8 matrix core serves uint8_t in the narrow calls only because their result is
+ * taken mod 2^8, where both types agree; unsigned 32-bit sums need a bias correction with the row sums of A and the column
+ * sums of B -- a different kernel, not this one.  The "half_contract" knob does not apply: it picks between two NARROW contracts.
+ * Kernels (mm_kernel_name_widen): under MM_PATH_AUTO the kernel mm_kernel_name_batched(cfg, n, k, m, batch) names for the
+ * narrow type -- for batch = 1 too, as in the accumulating calls -- instantiated with the wide output: that name + "_wide";
+ * no workspace, no transposition pre-pass, no split of K.  "widen_ordered" (k ascending, one wide accumulator, fully
+ * predicated: any shape, any element-aligned pointer or stride) serves MM_PATH_ORDERED, every shape for which the narrow
+ * batched resolver names no matrix-core kernel, and -- silently, same contract; the name is decided by shape and path --
+ * MM_PATH_AUTO launches where some element's A, B or C is not 16-byte aligned.  A K x N A that the narrow single launch would
+ * transpose into workspace first (M >= 6144, knob "kxn_prepass_min_m") has no batched matrix-core kernel either: such a call
+ * runs widen_ordered, at VALU speed -- transpose A once and call with a row-major A instead.
+ * Arguments as for mm_gemm_logsumexp_*: strides count elements of each buffer's own type, 0 = broadcast, stride_c >= N * M
+ * when batch > 1.  Refused before any device is touched: a dtype other than half and int8_t, a (map, reduce) other than
+ * (Multiply, Add), MM_PATH_SPLIT (MM_ERR_UNSUPPORTED); a null pointer, overlapping outputs and C's span overlapping A's or
+ * B's (MM_ERR_BAD_ARGUMENT).  batch, N or M 0: MM_OK; K = 0: MM_ERR_BAD_ARGUMENT in the plain form, MM_OK (C unchanged) when
+ * accumulating.  The batch is launched in chunks (knob "batch_chunk"); the kernel is resolved once on the whole batch.
+ * _enqueue: asynchronous on a hipStream_t of the CURRENT device, never synchronises the host; _launch: blocking,
+ * *elapsed_seconds (may be NULL) timed with HIP events. */
+int mm_gemm_widen_enqueue(void *hip_stream, const mm_config_t *cfg, const void *a_dev, const void *b_dev, void *c_dev,
+                          unsigned size_n, unsigned size_k, unsigned size_m, unsigned batch,
+                          size_t stride_a, size_t stride_b, size_t stride_c, int accumulate);
+int mm_gemm_widen_launch(int device, const mm_config_t *cfg, const void *a_dev, const void *b_dev, void *c_dev,
+                         unsigned size_n, unsigned size_k, unsigned size_m, unsigned batch,
+                         size_t stride_a, size_t stride_b, size_t stride_c, int accumulate, double *elapsed_seconds);
+/* A "..._wide" matrix-core kernel or "widen_ordered"; "unsupported" for a configuration the calls refuse with
+ * MM_ERR_UNSUPPORTED; "invalid" for a bad configuration.  Static string, pure arithmetic. */
+const char *mm_kernel_name_widen(const mm_config_t *cfg, unsigned size_n, unsigned size_k, unsigned size_m, unsigned batch);
+/* C's mm_dtype_t for operands of `dtype`: MM_DTYPE_F32 for half, MM_DTYPE_I32 for int8_t; -1 for every other type. */
+int mm_widen_dtype(mm_dtype_t dtype);
+
 /* Closure: all-pairs shortest / widest / longest paths and transitive closure -- blocked Floyd-Warshall, in place.
  * D is n x n, row-major; graph e of the batch starts at d_dev + e * stride_d (elements; stride_d >= n * n when batch > 1).
  * The call runs the recurrence D[i][j] <- D[i][j] (+) D[i][v] (x) D[v][j] over every v, with Reduce = cfg->reduce_op in
