@@ -13,7 +13,6 @@
 #include <mutex>
 #include <random>
 #include <unordered_map>
-#include <string>
 #include <vector>
 
 #include "mm_common.h"
@@ -362,12 +361,13 @@ int dispatch_batched(hipStream_t s, const mm_config_t &cfg, const mm::Problem &p
 }
 
 mm::Problem batched_problem(const mm_config_t *cfg, const void *a, const void *b, void *c, unsigned n, unsigned k,
-                            unsigned m, unsigned batch, size_t stride_a, size_t stride_b, size_t stride_c) {
+                            unsigned m, unsigned batch, size_t stride_a, size_t stride_b, size_t stride_c, bool seed = false) {
   mm::Problem p{a, b, c, n, k, m, cfg && cfg->layout_a == MM_A_TRANSPOSED};
   p.batch = batch;
   p.stride_a = stride_a;
   p.stride_b = stride_b;
   p.stride_c = stride_c;
+  p.seed = seed;
   return p;
 }
 
@@ -814,6 +814,58 @@ template <class F> int launch_timed(int device, bool nothing, double *elapsed, F
   return MM_OK;
 }
 
+// Where a checked call runs: the caller's stream (mm_*_enqueue), or `device`'s null stream, timed (mm_*_launch).  Each entry-point
+// pair writes its body once, against a Target.
+struct Target {
+  bool timed;
+  void *stream;
+  int device;
+  double *elapsed;
+};
+Target on_stream(void *stream) { return {false, stream, 0, nullptr}; }
+Target timed_on(int device, double *elapsed) { return {true, nullptr, device, elapsed}; }
+template <class F> int run(const Target &t, bool nothing, F &&dispatch) {
+  return t.timed ? launch_timed(t.device, nothing, t.elapsed, dispatch) : enqueue_on(t.stream, nothing, dispatch);
+}
+
+// ---- the entry points' bodies: checks first (no device is touched before they pass), then the dispatch on the target -------------
+int run_gemm(const Target &t, const mm_config_t *cfg, const void *a, const void *b, void *c, unsigned n, unsigned k, unsigned m) {
+  if (int rc = t.timed ? check_device(t.device) : ensure_init()) return rc;   // (mm_gemm_launch: the device first, then the arguments)
+  if (int rc = check_problem(cfg, a, b, c, n, k, m)) return rc;
+  const mm::Problem p{a, b, c, n, k, m, cfg->layout_a == MM_A_TRANSPOSED};
+  return run(t, false, [&](hipStream_t s) { return dispatch(s, *cfg, p); });
+}
+
+int run_batched(const Target &t, const mm_config_t *cfg, const mm::Problem &p) {   // p.seed: the accumulating calls
+  Family fam;
+  if (int rc = p.seed ? check_accumulate(cfg, p, &fam) : check_batched(cfg, p, &fam)) return rc;
+  return run(t, fam == FAM_NONE, [&](hipStream_t s) { return dispatch_batched(s, *cfg, p, fam); });
+}
+
+int run_argreduce(const Target &t, const mm_config_t *cfg, const mm::Problem &p, int *c_index, int index_base) {
+  ArKernel ker;
+  if (int rc = check_argreduce(cfg, p, c_index, index_base, &ker)) return rc;
+  return run(t, ker == AR_NONE, [&](hipStream_t s) { return dispatch_argreduce(s, *cfg, p, c_index, index_base, ker); });
+}
+
+int run_lse(const Target &t, const mm_config_t *cfg, const mm::Problem &p) {
+  LseKernel ker;
+  if (int rc = check_lse(cfg, p, &ker)) return rc;
+  return run(t, ker == LSE_NONE, [&](hipStream_t s) { return dispatch_lse(s, *cfg, p, ker); });
+}
+
+int run_widen(const Target &t, const mm_config_t *cfg, const mm::Problem &p) {
+  WidenKernel ker;
+  if (int rc = check_widen(cfg, p, &ker)) return rc;
+  return run(t, ker == WD_NONE, [&](hipStream_t s) { return dispatch_widen(s, *cfg, p, ker); });
+}
+
+int run_closure(const Target &t, const mm_config_t *cfg, void *d, int *witness, unsigned n, unsigned batch, size_t stride_d) {
+  unsigned block;   // 0: n or batch 0, nothing to do
+  if (int rc = check_closure(cfg, d, witness, n, batch, stride_d, &block)) return rc;
+  return run(t, block == 0, [&](hipStream_t s) { return dispatch_closure(s, *cfg, d, witness, n, batch, stride_d, block); });
+}
+
 }  // namespace
 
 // One library-owned memory pool per device for stream-ordered workspace (the packed planes of MM_PATH_SPLIT, the
@@ -1001,59 +1053,36 @@ int mm_fill_device(int device, mm_dtype_t dtype, void *ptr, size_t elements, uns
 
 int mm_gemm_enqueue(void *hip_stream, const mm_config_t *cfg, const void *a, const void *b, void *c, unsigned n,
                     unsigned k, unsigned m) {
-  int rc = ensure_init();
-  if (rc) return rc;
-  rc = check_problem(cfg, a, b, c, n, k, m);
-  if (rc) return rc;
-  mm::Problem p{a, b, c, n, k, m, cfg->layout_a == MM_A_TRANSPOSED};
-  return dispatch((hipStream_t)hip_stream, *cfg, p);
+  return run_gemm(on_stream(hip_stream), cfg, a, b, c, n, k, m);
 }
 
 int mm_gemm_launch(int device, const mm_config_t *cfg, const void *a, const void *b, void *c, unsigned n, unsigned k,
                    unsigned m, double *elapsed_seconds) {
-  int rc = check_device(device);   // the device first, then the arguments
-  if (rc) return rc;
-  rc = check_problem(cfg, a, b, c, n, k, m);
-  if (rc) return rc;
-  const mm::Problem p{a, b, c, n, k, m, cfg->layout_a == MM_A_TRANSPOSED};
-  return launch_timed(device, false, elapsed_seconds, [&](hipStream_t s) { return dispatch(s, *cfg, p); });
+  return run_gemm(timed_on(device, elapsed_seconds), cfg, a, b, c, n, k, m);
 }
 
 int mm_gemm_batched_enqueue(void *hip_stream, const mm_config_t *cfg, const void *a, const void *b, void *c, unsigned n,
                             unsigned k, unsigned m, unsigned batch, size_t stride_a, size_t stride_b, size_t stride_c) {
-  const mm::Problem p = batched_problem(cfg, a, b, c, n, k, m, batch, stride_a, stride_b, stride_c);
-  Family fam;
-  if (int rc = check_batched(cfg, p, &fam)) return rc;
-  return enqueue_on(hip_stream, fam == FAM_NONE, [&](hipStream_t s) { return dispatch_batched(s, *cfg, p, fam); });
+  return run_batched(on_stream(hip_stream), cfg, batched_problem(cfg, a, b, c, n, k, m, batch, stride_a, stride_b, stride_c));
 }
 
 int mm_gemm_batched_launch(int device, const mm_config_t *cfg, const void *a, const void *b, void *c, unsigned n,
                            unsigned k, unsigned m, unsigned batch, size_t stride_a, size_t stride_b, size_t stride_c,
                            double *elapsed_seconds) {
-  const mm::Problem p = batched_problem(cfg, a, b, c, n, k, m, batch, stride_a, stride_b, stride_c);
-  Family fam;
-  if (int rc = check_batched(cfg, p, &fam)) return rc;
-  return launch_timed(device, fam == FAM_NONE, elapsed_seconds, [&](hipStream_t s) { return dispatch_batched(s, *cfg, p, fam); });
+  return run_batched(timed_on(device, elapsed_seconds), cfg, batched_problem(cfg, a, b, c, n, k, m, batch, stride_a, stride_b, stride_c));
 }
 
 int mm_gemm_batched_accumulate_enqueue(void *hip_stream, const mm_config_t *cfg, const void *a, const void *b, void *c,
                                        unsigned n, unsigned k, unsigned m, unsigned batch, size_t stride_a, size_t stride_b,
                                        size_t stride_c) {
-  mm::Problem p = batched_problem(cfg, a, b, c, n, k, m, batch, stride_a, stride_b, stride_c);
-  p.seed = true;
-  Family fam;
-  if (int rc = check_accumulate(cfg, p, &fam)) return rc;
-  return enqueue_on(hip_stream, fam == FAM_NONE, [&](hipStream_t s) { return dispatch_batched(s, *cfg, p, fam); });
+  return run_batched(on_stream(hip_stream), cfg, batched_problem(cfg, a, b, c, n, k, m, batch, stride_a, stride_b, stride_c, true));
 }
 
 int mm_gemm_batched_accumulate_launch(int device, const mm_config_t *cfg, const void *a, const void *b, void *c, unsigned n,
                                       unsigned k, unsigned m, unsigned batch, size_t stride_a, size_t stride_b,
                                       size_t stride_c, double *elapsed_seconds) {
-  mm::Problem p = batched_problem(cfg, a, b, c, n, k, m, batch, stride_a, stride_b, stride_c);
-  p.seed = true;
-  Family fam;
-  if (int rc = check_accumulate(cfg, p, &fam)) return rc;
-  return launch_timed(device, fam == FAM_NONE, elapsed_seconds, [&](hipStream_t s) { return dispatch_batched(s, *cfg, p, fam); });
+  return run_batched(timed_on(device, elapsed_seconds), cfg,
+                     batched_problem(cfg, a, b, c, n, k, m, batch, stride_a, stride_b, stride_c, true));
 }
 
 // The single accumulating launch is a batch of one: the batched kernel mm_kernel_name_batched(cfg, n, k, m, 1) names.
@@ -1070,43 +1099,28 @@ int mm_gemm_accumulate_launch(int device, const mm_config_t *cfg, const void *a,
 int mm_gemm_argreduce_enqueue(void *hip_stream, const mm_config_t *cfg, const void *a, const void *b, void *c, int *c_index,
                               unsigned n, unsigned k, unsigned m, unsigned batch, size_t stride_a, size_t stride_b,
                               size_t stride_c, int index_base, int accumulate) {
-  mm::Problem p = batched_problem(cfg, a, b, c, n, k, m, batch, stride_a, stride_b, stride_c);
-  p.seed = accumulate != 0;
-  ArKernel ker;
-  if (int rc = check_argreduce(cfg, p, c_index, index_base, &ker)) return rc;
-  return enqueue_on(hip_stream, ker == AR_NONE,
-                    [&](hipStream_t s) { return dispatch_argreduce(s, *cfg, p, c_index, index_base, ker); });
+  return run_argreduce(on_stream(hip_stream), cfg,
+                       batched_problem(cfg, a, b, c, n, k, m, batch, stride_a, stride_b, stride_c, accumulate != 0), c_index, index_base);
 }
 
 int mm_gemm_argreduce_launch(int device, const mm_config_t *cfg, const void *a, const void *b, void *c, int *c_index,
                              unsigned n, unsigned k, unsigned m, unsigned batch, size_t stride_a, size_t stride_b,
                              size_t stride_c, int index_base, int accumulate, double *elapsed_seconds) {
-  mm::Problem p = batched_problem(cfg, a, b, c, n, k, m, batch, stride_a, stride_b, stride_c);
-  p.seed = accumulate != 0;
-  ArKernel ker;
-  if (int rc = check_argreduce(cfg, p, c_index, index_base, &ker)) return rc;
-  return launch_timed(device, ker == AR_NONE, elapsed_seconds,
-                      [&](hipStream_t s) { return dispatch_argreduce(s, *cfg, p, c_index, index_base, ker); });
+  return run_argreduce(timed_on(device, elapsed_seconds), cfg,
+                       batched_problem(cfg, a, b, c, n, k, m, batch, stride_a, stride_b, stride_c, accumulate != 0), c_index, index_base);
 }
 
 int mm_gemm_logsumexp_enqueue(void *hip_stream, const mm_config_t *cfg, const void *a, const void *b, void *c, unsigned n,
                               unsigned k, unsigned m, unsigned batch, size_t stride_a, size_t stride_b, size_t stride_c,
                               int accumulate) {
-  mm::Problem p = batched_problem(cfg, a, b, c, n, k, m, batch, stride_a, stride_b, stride_c);
-  p.seed = accumulate != 0;
-  LseKernel ker;
-  if (int rc = check_lse(cfg, p, &ker)) return rc;
-  return enqueue_on(hip_stream, ker == LSE_NONE, [&](hipStream_t s) { return dispatch_lse(s, *cfg, p, ker); });
+  return run_lse(on_stream(hip_stream), cfg, batched_problem(cfg, a, b, c, n, k, m, batch, stride_a, stride_b, stride_c, accumulate != 0));
 }
 
 int mm_gemm_logsumexp_launch(int device, const mm_config_t *cfg, const void *a, const void *b, void *c, unsigned n,
                              unsigned k, unsigned m, unsigned batch, size_t stride_a, size_t stride_b, size_t stride_c,
                              int accumulate, double *elapsed_seconds) {
-  mm::Problem p = batched_problem(cfg, a, b, c, n, k, m, batch, stride_a, stride_b, stride_c);
-  p.seed = accumulate != 0;
-  LseKernel ker;
-  if (int rc = check_lse(cfg, p, &ker)) return rc;
-  return launch_timed(device, ker == LSE_NONE, elapsed_seconds, [&](hipStream_t s) { return dispatch_lse(s, *cfg, p, ker); });
+  return run_lse(timed_on(device, elapsed_seconds), cfg,
+                 batched_problem(cfg, a, b, c, n, k, m, batch, stride_a, stride_b, stride_c, accumulate != 0));
 }
 
 int mm_widen_dtype(mm_dtype_t dtype) { return dtype == MM_DTYPE_F16 ? (int)MM_DTYPE_F32 : dtype == MM_DTYPE_I8 ? (int)MM_DTYPE_I32 : -1; }
@@ -1114,37 +1128,24 @@ int mm_widen_dtype(mm_dtype_t dtype) { return dtype == MM_DTYPE_F16 ? (int)MM_DT
 int mm_gemm_widen_enqueue(void *hip_stream, const mm_config_t *cfg, const void *a, const void *b, void *c, unsigned n,
                           unsigned k, unsigned m, unsigned batch, size_t stride_a, size_t stride_b, size_t stride_c,
                           int accumulate) {
-  mm::Problem p = batched_problem(cfg, a, b, c, n, k, m, batch, stride_a, stride_b, stride_c);
-  p.seed = accumulate != 0;
-  WidenKernel ker;
-  if (int rc = check_widen(cfg, p, &ker)) return rc;
-  return enqueue_on(hip_stream, ker == WD_NONE, [&](hipStream_t s) { return dispatch_widen(s, *cfg, p, ker); });
+  return run_widen(on_stream(hip_stream), cfg, batched_problem(cfg, a, b, c, n, k, m, batch, stride_a, stride_b, stride_c, accumulate != 0));
 }
 
 int mm_gemm_widen_launch(int device, const mm_config_t *cfg, const void *a, const void *b, void *c, unsigned n, unsigned k,
                          unsigned m, unsigned batch, size_t stride_a, size_t stride_b, size_t stride_c, int accumulate,
                          double *elapsed_seconds) {
-  mm::Problem p = batched_problem(cfg, a, b, c, n, k, m, batch, stride_a, stride_b, stride_c);
-  p.seed = accumulate != 0;
-  WidenKernel ker;
-  if (int rc = check_widen(cfg, p, &ker)) return rc;
-  return launch_timed(device, ker == WD_NONE, elapsed_seconds, [&](hipStream_t s) { return dispatch_widen(s, *cfg, p, ker); });
+  return run_widen(timed_on(device, elapsed_seconds), cfg,
+                   batched_problem(cfg, a, b, c, n, k, m, batch, stride_a, stride_b, stride_c, accumulate != 0));
 }
 
 int mm_closure_enqueue(void *hip_stream, const mm_config_t *cfg, void *d, int *witness, unsigned n, unsigned batch,
                        size_t stride_d) {
-  unsigned block;   // 0: n or batch 0, nothing to do
-  if (int rc = check_closure(cfg, d, witness, n, batch, stride_d, &block)) return rc;
-  return enqueue_on(hip_stream, block == 0,
-                    [&](hipStream_t s) { return dispatch_closure(s, *cfg, d, witness, n, batch, stride_d, block); });
+  return run_closure(on_stream(hip_stream), cfg, d, witness, n, batch, stride_d);
 }
 
 int mm_closure_launch(int device, const mm_config_t *cfg, void *d, int *witness, unsigned n, unsigned batch, size_t stride_d,
                       double *elapsed_seconds) {
-  unsigned block;
-  if (int rc = check_closure(cfg, d, witness, n, batch, stride_d, &block)) return rc;
-  return launch_timed(device, block == 0, elapsed_seconds,
-                      [&](hipStream_t s) { return dispatch_closure(s, *cfg, d, witness, n, batch, stride_d, block); });
+  return run_closure(timed_on(device, elapsed_seconds), cfg, d, witness, n, batch, stride_d);
 }
 
 // Rows per device of the N split: ceil(N / G) rounded up to whole tile rows of the kernel that will run on a slab of that
@@ -1442,24 +1443,7 @@ const char *mm_kernel_name(const mm_config_t *cfg, unsigned n, unsigned k, unsig
     // every family answers through the same resolver its launcher uses, so the name IS the kernel that runs
     case FAM_MFMA_F32: {
       const int v = f32_variant_for(p);
-      if (v < 0) return "unsupported";
-      static const char *const split_names[] = {nullptr, nullptr, "mfma_f32_128x128x32_w4x2_splitk2", "mfma_f32_128x128x32_w4x2_splitk3",
-                                                "mfma_f32_128x128x32_w4x2_splitk4", "mfma_f32_128x128x32_w4x2_splitk5",
-                                                "mfma_f32_128x128x32_w4x2_splitk6", "mfma_f32_128x128x32_w4x2_splitk7",
-                                                "mfma_f32_128x128x32_w4x2_splitk8"};
-      const int splits = mm::mfma_f32_splitk(p, v);
-      if (v == 64 && splits > 1) {
-        static const char *const small_split_names[] = {nullptr, nullptr, "mfma_f32_64x64x32_w4x2_splitk2", "mfma_f32_64x64x32_w4x2_splitk3",
-                                                        "mfma_f32_64x64x32_w4x2_splitk4", "mfma_f32_64x64x32_w4x2_splitk5",
-                                                        "mfma_f32_64x64x32_w4x2_splitk6", "mfma_f32_64x64x32_w4x2_splitk7",
-                                                        "mfma_f32_64x64x32_w4x2_splitk8"};
-        return small_split_names[splits];
-      }
-      if (splits == 0) return "mfma_f32_128x128x32_w4x2_streamk";            // teams, the last part to arrive gathers: what MM_PATH_AUTO runs
-      if (splits == 9) return "mfma_f32_128x128x32_w4x2_streamk_fixup";      // single ranges + fix-up kernel (cross-check, its own bits)
-      if (splits == 11) return "mfma_f32_128x128x32_w4x2_streamk_two_kernels";   // teams + fix-up kernel (cross-check); the bits of `streamk`
-      if (splits == 12) return "mfma_f32_128x128x32_w4x2_streamk_ticket";        // teams, one counter ticket per part, the last ticket gathers; the bits of `streamk`
-      return splits > 1 ? split_names[splits] : mm::mfma_f32_name(v);
+      return v < 0 ? "unsupported" : mm::mfma_f32_launch_name(p, v);
     }
     case FAM_MFMA_F64: return mm::mfma_f64_name(p);
     case FAM_MFMA_F16: return mm::mfma_f16_name(p);
@@ -1537,43 +1521,17 @@ static void kernel_info_for(const mm_config_t *cfg, const mm::Problem &p, mm_ker
   if (g_init_status != MM_OK || hipGetDevice(&cur) != hipSuccess) { (void)hipGetLastError(); cur = 0; }
   r.compute_units = (unsigned)mm::device_compute_units(cur);
   r.max_clock_mhz = 2400.0;
+  const mm::KernelRow *row = nullptr;
   switch (choose(*cfg, p)) {
     case FAM_MFMA_F32:
       mm::mfma_f32_geometry(f32_variant_for(p), &r.tile_n, &r.tile_m, &r.tile_k, &r.wavefronts);
       r.inst_n = 32; r.inst_m = 32; r.inst_k = 2; r.ops_per_clk_per_cu = 256.0;   // 64 FLOP/clk/SIMD
       r.measured_issue_efficiency = 0.967;  // 152.2 TF of 157.3 (profiles/r02z_f32_scalar_base_dma.log)
       break;
-    case FAM_MFMA_F64:
-      switch (mm::mfma_f64_tile(p)) {
-        case 4: r.tile_n = 64; r.tile_m = 64; r.wavefronts = 4; break;
-        case 1: r.tile_n = 128; r.tile_m = 128; r.wavefronts = 4; break;
-        default: r.tile_n = 256; r.tile_m = 128; r.wavefronts = 8; break;
-      }
-      r.tile_k = 16;
-      r.inst_n = 16; r.inst_m = 16; r.inst_k = 4; r.ops_per_clk_per_cu = 128.0;
-      r.measured_issue_efficiency = 0.97;  // pinned schedule + scalar-base DMA: 76.4 TF of 78.6 (profiles/r02z_f64_scalar_base_dma.log)
-      break;
-    case FAM_MFMA_F16: {
-      const std::string name = mm::mfma_f16_name(p);   // geometry read off the resolved kernel's name
-      const bool s16 = name.find("16x16x32") != std::string::npos, pp = name.find("pingpong") != std::string::npos;
-      r.tile_n = name.find("_64x256") != std::string::npos ? 64 : name.find("128x256") != std::string::npos ? 128 : 256;
-      r.tile_m = 256; r.wavefronts = r.tile_n == 256 ? 8 : 4;
-      r.tile_k = pp ? 32 : 64;
-      r.inst_n = r.inst_m = s16 ? 16 : 32; r.inst_k = s16 ? 32 : 16; r.ops_per_clk_per_cu = 4096.0;
-      // ping-pong schedule: MfmaUtil 91.4 % (16x16x32, profiles/r03g_pmc_f16_32768_16x16x32.json) / 89.7 % (32x32x16) at
-      // 32768^3; the chip is power-limited there and delivers ~1.5 GHz, so 0.91 x 2.4 GHz over-predicts wall throughput
-      r.measured_issue_efficiency = pp ? (s16 ? 0.91 : 0.90) : 0.67;
-      break;
-    }
-    case FAM_MFMA_I8: {
-      const std::string name = mm::mfma_i8_name(p);
-      const bool s16 = name.find("16x16x64") != std::string::npos, pp = name.find("pingpong") != std::string::npos;
-      r.tile_n = name.find("_64x256") != std::string::npos ? 64 : 256; r.tile_m = 256; r.wavefronts = r.tile_n == 256 ? 8 : 4;
-      r.tile_k = pp ? 64 : 128;
-      r.inst_n = r.inst_m = s16 ? 16 : 32; r.inst_k = s16 ? 64 : 32; r.ops_per_clk_per_cu = 8192.0;
-      r.measured_issue_efficiency = pp ? 0.92 : 0.68;  // profiles/r02i_pmc_i8_32768.json / r01_pmc_i8.json
-      break;
-    }
+    // the other matrix-core families: the resolved kernel's row of the family's table
+    case FAM_MFMA_F64: row = &mm::mfma_f64_row(p); r.ops_per_clk_per_cu = 128.0; break;
+    case FAM_MFMA_F16: row = &mm::mfma_f16_row(p); r.ops_per_clk_per_cu = 4096.0; break;
+    case FAM_MFMA_I8: row = &mm::mfma_i8_row(p); r.ops_per_clk_per_cu = 8192.0; break;
     case FAM_F32_SPLIT:
       {  // the 128 x 128 geometry runs only in the launcher's default branch (no schedule / product / flush bits set)
         const int sv = mm::tuning(mm::TUNE_SPLIT_VARIANT);
@@ -1611,6 +1569,11 @@ static void kernel_info_for(const mm_config_t *cfg, const mm::Problem &p, mm_ker
       r.tile_n = 64; r.tile_m = 64; r.tile_k = 16; r.wavefronts = 4;
       r.inst_n = 1; r.inst_m = 64; r.inst_k = 1; r.ops_per_clk_per_cu = 128.0;
       break;
+  }
+  if (row) {
+    r.tile_n = row->tile_n; r.tile_m = row->tile_m; r.tile_k = row->tile_k; r.wavefronts = row->wavefronts;
+    r.inst_n = row->inst_n; r.inst_m = row->inst_m; r.inst_k = row->inst_k;
+    r.measured_issue_efficiency = row->measured_issue_efficiency;
   }
   *info = r;
 }

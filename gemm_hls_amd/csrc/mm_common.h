@@ -200,6 +200,7 @@ int workspace_release(int device);                       // hands its cached mem
 int flags_alloc(int device, hipStream_t stream, size_t bytes, void **flags, unsigned long long *epoch);
 int device_compute_units(int device);                    // as reported by the device when the library initialised
 int mfma_f32_splitk(const Problem &p, int variant);      // K chunks the fp32 MFMA launcher uses for (problem, resolved variant)
+const char *mfma_f32_launch_name(const Problem &p, int variant);   // what that pair runs: the geometry's name, or its split-K / stream-K form's
 bool mfma_f32_serves(const Problem &p);
 bool mfma_f64_serves(const Problem &p);
 bool mfma_f16_serves(const Problem &p);
@@ -212,12 +213,26 @@ int mfma_f32_resolve(const Problem &p, int variant);     // variant id a (proble
 const char *mfma_f16_name(const Problem &p);
 const char *mfma_f64_name(const Problem &p);
 const char *mfma_i8_name(const Problem &p);
+// One row of a matrix-core family's kernel table (mm_mfma_*_kernels.inc): the one place that describes a kernel.  The launch,
+// the names, the wide twin and mm_kernel_info all read it.
+struct KernelRow {
+  const char *name, *wide_name;   // literals; wide_name: the instantiation with a wide C (mm_gemm_widen_*), null where there is none
+  unsigned tile_n, tile_m, tile_k, wavefronts, inst_n, inst_m, inst_k;
+  double measured_issue_efficiency;
+};
+// The row of the kernel mfma_*_name(p) names; where it names none ("unsupported": a knob value the library does not have),
+// the row of the family's catch-all kernel.
+const KernelRow &mfma_f16_row(const Problem &p);
+const KernelRow &mfma_f64_row(const Problem &p);
+const KernelRow &mfma_i8_row(const Problem &p);
 int mfma_f32_auto_variant(const Problem &p);
-int mfma_f64_tile(const Problem &p);  // 0: 256x128, 1: 128x128
 int mfma_f16_tile(const Problem &p);  // 0: 256x256, 4: 128x256  // shape-adaptive pick (variant < 0)
 // dst[n][k] = src[k][n] for 1- and 2-byte elements (mm_transpose.hip); N and K multiples of 16 bytes' worth of elements
 int launch_transpose_kxn(hipStream_t s, const void *src, void *dst, unsigned K, unsigned N, unsigned elem_size);
 bool transposes_first_small(const Problem &p, unsigned elem_size);   // K x N A of half / int8: pre-pass + the row-major default
+// That pre-pass: A into N x K pool workspace, row_major() on the copy, free.  A full pool is no error: in_place() serves the K x N A.
+typedef int (*ProblemLauncher)(hipStream_t s, const Problem &p);
+int launch_transposed_first(hipStream_t s, const Problem &p, unsigned elem_size, ProblemLauncher row_major, ProblemLauncher in_place);
 int launch_fill(hipStream_t s, mm_dtype_t dtype, void *ptr, size_t elements, unsigned long long seed);
 
 constexpr int kErrNotSupported = 801;  // hipErrorNotSupported
@@ -325,6 +340,25 @@ __device__ __forceinline__ unsigned xcd_remap(unsigned bid, unsigned nwg) {
 // implies batched).  Every form takes the batched argument list (..., batch, stride_a, stride_b, stride_c); Form::Single
 // never reads that tail, so its machine code is that of a kernel without it.
 enum class Form { Single, Batched, Seeded };
+
+// One launch of KERN, the form-F instantiation of a half / int8 matrix-core kernel with geometry G, operands of type T and a C of
+// type CT: the problem at (a, b, c), or (F != Form::Single) p.batch copies of the tile grid over the elements of p.
+template <Form F, typename G, auto KERN, typename T, typename CT>
+int launch_tile(hipStream_t s, const Problem &p) {
+  const unsigned tiles_n = (p.n + G::BM - 1) / G::BM, tiles_m = (p.m + G::BN - 1) / G::BN;
+  static unsigned long long configured = 0;   // one per instantiation of this function, so one per kernel
+  if (int e = ensure_dynamic_lds((const void *)KERN, G::LDS_BYTES, configured)) return e;
+  hipLaunchKernelGGL(KERN, dim3(tiles_n * tiles_m * (F == Form::Single ? 1u : p.batch)), dim3(G::THREADS), G::LDS_BYTES, s,
+                     (const T *)p.a, (const T *)p.b, (CT *)p.c, p.n, p.k, p.m, tiles_n, tiles_m, band_rows(G::BM, G::BN, 1),
+                     F == Form::Single ? 1u : p.batch, p.stride_a, p.stride_b, p.stride_c);
+  return (int)hipGetLastError();
+}
+
+// A table row from the kernel's geometry struct G, its instruction shape (inst x inst x inst_k) and its measured efficiency
+template <typename G>
+constexpr KernelRow kernel_row(const char *name, const char *wide_name, unsigned inst, unsigned inst_k, double efficiency) {
+  return {name, wide_name, G::BM, G::BN, G::BK, G::THREADS / 64, inst, inst, inst_k, efficiency};
+}
 
 // Batched launches (Form::Batched, Form::Seeded): `batch` elements of one shape, `batch` copies of the tile grid in one
 // launch.  The XCD-remapped linear id is decomposed as (element, tile), so one element's tiles stay contiguous in an XCD's

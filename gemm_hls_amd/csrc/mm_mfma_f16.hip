@@ -13,6 +13,8 @@
 //                       cross-check of the default (f16_variant 100); also what round 2 shipped
 //   pingpong_k32        32-deep slabs with 64-byte A rows (K % 32 == 0, K >= 128), row-major and K x N A
 //   slab64              one barrier per 64-deep slab (K % 16 == 0; any N; 256 x 256, or 128 x 256 for small problems)
+// Each is one row of kTable at the end of mm_mfma_f16_kernels.inc (name, wide twin, geometry, instruction, efficiency); this unit
+// holds the rules that pick a row (resolve) and launches it through the include's launch_kind.
 // The schedules and ablations these went through (lock step, early barrier, DMA cache policies, no-DMA / no-read power
 // breakdown, the 384 x 256 tile) live in tools/lab/lab_mfma_f16.hip -> tools/lab/libmm_gemm_amd_lab.so.
 //
@@ -37,14 +39,6 @@ namespace {
 #include "mm_mfma_f16_kernels.inc"
 
 #undef MM_DMA_PIECE
-
-// (mm_mfma_f16_wide.hip finds its instantiations by these names: a kernel added or renamed here needs its twin there --
-// tests/test_widen_capi.py compares the tables)
-enum Kind { K_PP16, K_PP32, K_PPK32, K_PPK32_AT, K_SLAB64, K_SLAB64_AT, K_SLAB64_128, K_SLAB64_64, K_NONE };
-const char *const kNames[] = {"mfma_f16_256x256_pingpong_16x16x32", "mfma_f16_256x256_pingpong_32x32x16",
-                              "mfma_f16_256x256_pingpong_k32", "mfma_f16_256x256_pingpong_k32_KxN",
-                              "mfma_f16_256x256x64_slab64", "mfma_f16_256x256x64_slab64_KxN", "mfma_f16_128x256x64_slab64",
-                              "mfma_f16_64x256x64_slab64", "unsupported"};
 
 }  // namespace
 
@@ -97,54 +91,17 @@ static Kind resolve(const Problem &p) {
   return K_SLAB64;
 }
 
-const char *mfma_f16_name(const Problem &p) { return kNames[resolve(p)]; }
-
-// The kernel of each Kind, in form F
-template <Form F>
-static int launch_kind(hipStream_t s, const Problem &p, Kind k) {
-  switch (k) {
-    case K_PP16: return launch_tile<F, mfma_f16_pp2s_kernel<F>>(s, p, 256, 256, GeoPP2::THREADS, GeoPP2::LDS_BYTES);
-    case K_PP32: return launch_tile<F, mfma_f16_pp2_kernel<F>>(s, p, 256, 256, GeoPP2::THREADS, GeoPP2::LDS_BYTES);
-    case K_PPK32: return launch_tile<F, mfma_f16_pp_kernel<F, false>>(s, p, 256, 256, GeoPP::THREADS, GeoPP::LDS_BYTES);
-    case K_PPK32_AT: return launch_tile<F, mfma_f16_pp_kernel<F, true>>(s, p, 256, 256, GeoPP::THREADS, GeoPP::LDS_BYTES);
-    case K_SLAB64: return launch_tile<F, mfma_f16_kernel<F, GeoH, false>>(s, p, GeoH::BM, GeoH::BN, GeoH::THREADS, GeoH::LDS_BYTES);
-    case K_SLAB64_AT: return launch_tile<F, mfma_f16_kernel<F, GeoH, true>>(s, p, GeoH::BM, GeoH::BN, GeoH::THREADS, GeoH::LDS_BYTES);
-    case K_SLAB64_128: return launch_tile<F, mfma_f16_kernel<F, GeoHS, false>>(s, p, GeoHS::BM, GeoHS::BN, GeoHS::THREADS, GeoHS::LDS_BYTES);
-    case K_SLAB64_64: return launch_tile<F, mfma_f16_kernel<F, GeoHXS, false>>(s, p, GeoHXS::BM, GeoHXS::BN, GeoHXS::THREADS, GeoHXS::LDS_BYTES);
-    default: return kErrNotSupported;
-  }
-}
+const char *mfma_f16_name(const Problem &p) { return kTable[resolve(p)].name; }
+const KernelRow &mfma_f16_row(const Problem &p) { return kTable[resolve(p)]; }
 
 // A K x N A served where it lies (no workspace): the ping-pong K x N kernel where its shape rules allow, else slab64's
 static int launch_kxn_in_place(hipStream_t s, const Problem &p) {
-  return launch_kind<Form::Single>(s, p, tuning(TUNE_F16_VARIANT) != 0 && ppk32_serves(p) ? K_PPK32_AT : K_SLAB64_AT);
+  return launch_kind<Form::Single, _Float16>(s, p, tuning(TUNE_F16_VARIANT) != 0 && ppk32_serves(p) ? K_PPK32_AT : K_SLAB64_AT);
 }
 
 int launch_mfma_f16(hipStream_t s, const Problem &p) {
-  if (transposes_first(p)) {
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess) return (int)e;
-    hipMemPool_t pool = nullptr;
-    if (int rc = workspace_pool(dev, &pool)) return rc;
-    void *an = nullptr;
-    if ((e = hipMallocFromPoolAsync(&an, (size_t)p.n * p.k * 2, pool, s)) != hipSuccess) {
-      // no room for the N x K copy (up to 4 GiB next to a nearly full device): not an error -- the K x N kernels serve the
-      // call without extra memory, as they did before the pre-pass existed; same contract, ~2-3 % slower
-      (void)hipGetLastError();
-      return launch_kxn_in_place(s, p);
-    }
-    int rc = launch_transpose_kxn(s, p.a, an, p.k, p.n, 2);
-    if (rc == 0) {
-      Problem q = p;
-      q.a = an;
-      q.a_transposed = false;
-      rc = launch_mfma_f16(s, q);
-    }
-    const hipError_t f = hipFreeAsync(an, s);
-    return rc ? rc : (int)f;
-  }
-  return launch_kind<Form::Single>(s, p, resolve(p));
+  if (transposes_first(p)) return launch_transposed_first(s, p, 2, launch_mfma_f16, launch_kxn_in_place);
+  return launch_kind<Form::Single, _Float16>(s, p, resolve(p));
 }
 
 // Batched (mm_gemm_batched_*): whole tiles of the in-place kernels, decided on the whole batch (Problem::batch copies of the
@@ -159,11 +116,11 @@ static Kind resolve_batched(const Problem &p) {
   return resolve(p);
 }
 int mfma_f16_batched_resolve(const Problem &p) { const Kind k = resolve_batched(p); return k == K_NONE ? -1 : (int)k; }
-const char *mfma_f16_batched_name(const Problem &p) { return kNames[resolve_batched(p)]; }
+const char *mfma_f16_batched_name(const Problem &p) { return kTable[resolve_batched(p)].name; }
 int launch_mfma_f16_batched(hipStream_t s, const Problem &p, int kind) {
   if (kind < 0 || kind >= (int)K_NONE) return kErrNotSupported;
   // an accumulating launch (p.seed): the same kernel with C's value in its epilogue
-  return p.seed ? launch_kind<Form::Seeded>(s, p, (Kind)kind) : launch_kind<Form::Batched>(s, p, (Kind)kind);
+  return p.seed ? launch_kind<Form::Seeded, _Float16>(s, p, (Kind)kind) : launch_kind<Form::Batched, _Float16>(s, p, (Kind)kind);
 }
 
 }  // namespace mm

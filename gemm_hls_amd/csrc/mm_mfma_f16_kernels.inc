@@ -1,6 +1,7 @@
-// The kernels of mm_mfma_f16.hip and mm_mfma_f16_wide.hip, their geometries and their launch.  F (mm_common.h) is the form of
-// each: the single-problem kernel, its strided-batched form, or the batched form that accumulates into C.  CT is C's element
-// type: _Float16 -- the f32 sums rounded once on store -- or float, the sums themselves (mm_gemm_widen_*).
+// The kernels of mm_mfma_f16.hip and mm_mfma_f16_wide.hip, their geometries, their table (one row per kernel) and their
+// launch.  F (mm_common.h) is the form of each: the single-problem kernel, its strided-batched form, or the batched form that
+// accumulates into C.  CT is C's element type: _Float16 -- the f32 sums rounded once on store -- or float, the sums themselves
+// (mm_gemm_widen_*).
 using h8 = __attribute__((ext_vector_type(8))) _Float16;
 using h4 = __attribute__((ext_vector_type(4))) _Float16;
 using f32x16 = __attribute__((ext_vector_type(16))) float;
@@ -942,15 +943,36 @@ __global__ __launch_bounds__(GeoPP2::THREADS) void mfma_f16_pp2s_kernel(const _F
   }
 }
 
-// One launch of the kernel KERN, an instantiation for form F: the problem at (a, b, c), or (F != Form::Single) p.batch copies of
-// the tile grid over the elements of p
-template <Form F, auto KERN, typename CT = _Float16>
-static int launch_tile(hipStream_t s, const Problem &p, unsigned bm, unsigned bn, unsigned threads, int lds) {
-  const unsigned tiles_n = (p.n + bm - 1) / bm, tiles_m = (p.m + bn - 1) / bn;
-  static unsigned long long configured = 0;   // one per instantiation of this function, so one per kernel
-  if (int e = ensure_dynamic_lds((const void *)KERN, lds, configured)) return e;
-  hipLaunchKernelGGL(KERN, dim3(tiles_n * tiles_m * (F == Form::Single ? 1u : p.batch)), dim3(threads), lds, s,
-                     (const _Float16 *)p.a, (const _Float16 *)p.b, (CT *)p.c, p.n, p.k, p.m, tiles_n, tiles_m,
-                     band_rows(bm, bn, 1), F == Form::Single ? 1u : p.batch, p.stride_a, p.stride_b, p.stride_c);
-  return (int)hipGetLastError();
+// ---- the table: one row per kernel, read by the launch, the names, the wide unit and mm_kernel_info ------------------------
+// Efficiencies: ping-pong schedule MfmaUtil 91.4 % (16x16x32, profiles/r03g_pmc_f16_32768_16x16x32.json) / 89.7 % (32x32x16) at
+// 32768^3; the chip is power-limited there and delivers ~1.5 GHz, so 0.91 x 2.4 GHz over-predicts wall throughput.
+enum Kind { K_PP16, K_PP32, K_PPK32, K_PPK32_AT, K_SLAB64, K_SLAB64_AT, K_SLAB64_128, K_SLAB64_64, K_NONE };
+constexpr KernelRow kTable[] = {
+    kernel_row<GeoPP2>("mfma_f16_256x256_pingpong_16x16x32", "mfma_f16_256x256_pingpong_16x16x32_wide", 16, 32, 0.91),
+    kernel_row<GeoPP2>("mfma_f16_256x256_pingpong_32x32x16", "mfma_f16_256x256_pingpong_32x32x16_wide", 32, 16, 0.90),
+    kernel_row<GeoPP>("mfma_f16_256x256_pingpong_k32", "mfma_f16_256x256_pingpong_k32_wide", 32, 16, 0.90),
+    kernel_row<GeoPP>("mfma_f16_256x256_pingpong_k32_KxN", "mfma_f16_256x256_pingpong_k32_KxN_wide", 32, 16, 0.90),
+    kernel_row<GeoH>("mfma_f16_256x256x64_slab64", "mfma_f16_256x256x64_slab64_wide", 32, 16, 0.67),
+    kernel_row<GeoH>("mfma_f16_256x256x64_slab64_KxN", "mfma_f16_256x256x64_slab64_KxN_wide", 32, 16, 0.67),
+    kernel_row<GeoHS>("mfma_f16_128x256x64_slab64", "mfma_f16_128x256x64_slab64_wide", 32, 16, 0.67),
+    kernel_row<GeoHXS>("mfma_f16_64x256x64_slab64", "mfma_f16_64x256x64_slab64_wide", 32, 16, 0.67),
+    kernel_row<GeoH>("unsupported", nullptr, 32, 16, 0.67),   // K_NONE: described as the catch-all, slab64
+};
+static_assert(sizeof(kTable) / sizeof(kTable[0]) == K_NONE + 1, "one row per Kind");
+
+// The kernel of each Kind in form F, with a C of type CT (_Float16, or float for the wide unit)
+template <Form F, typename CT>
+static int launch_kind(hipStream_t s, const Problem &p, Kind k) {
+  using T = _Float16;
+  switch (k) {
+    case K_PP16: return launch_tile<F, GeoPP2, mfma_f16_pp2s_kernel<F, CT>, T, CT>(s, p);
+    case K_PP32: return launch_tile<F, GeoPP2, mfma_f16_pp2_kernel<F, CT>, T, CT>(s, p);
+    case K_PPK32: return launch_tile<F, GeoPP, mfma_f16_pp_kernel<F, false, CT>, T, CT>(s, p);
+    case K_PPK32_AT: return launch_tile<F, GeoPP, mfma_f16_pp_kernel<F, true, CT>, T, CT>(s, p);
+    case K_SLAB64: return launch_tile<F, GeoH, mfma_f16_kernel<F, GeoH, false, CT>, T, CT>(s, p);
+    case K_SLAB64_AT: return launch_tile<F, GeoH, mfma_f16_kernel<F, GeoH, true, CT>, T, CT>(s, p);
+    case K_SLAB64_128: return launch_tile<F, GeoHS, mfma_f16_kernel<F, GeoHS, false, CT>, T, CT>(s, p);
+    case K_SLAB64_64: return launch_tile<F, GeoHXS, mfma_f16_kernel<F, GeoHXS, false, CT>, T, CT>(s, p);
+    default: return kErrNotSupported;
+  }
 }

@@ -422,6 +422,25 @@ const char *mfma_f32_name(int v) {
   return i ? i->name : "?";
 }
 
+// What a (problem, resolved variant) pair runs: the geometry's kernel, or the split-K / stream-K form mfma_f32_splitk picks
+const char *mfma_f32_launch_name(const Problem &p, int v) {
+  static const char *const split_names[] = {nullptr, nullptr, "mfma_f32_128x128x32_w4x2_splitk2", "mfma_f32_128x128x32_w4x2_splitk3",
+                                            "mfma_f32_128x128x32_w4x2_splitk4", "mfma_f32_128x128x32_w4x2_splitk5",
+                                            "mfma_f32_128x128x32_w4x2_splitk6", "mfma_f32_128x128x32_w4x2_splitk7",
+                                            "mfma_f32_128x128x32_w4x2_splitk8"};
+  static const char *const small_split_names[] = {nullptr, nullptr, "mfma_f32_64x64x32_w4x2_splitk2", "mfma_f32_64x64x32_w4x2_splitk3",
+                                                  "mfma_f32_64x64x32_w4x2_splitk4", "mfma_f32_64x64x32_w4x2_splitk5",
+                                                  "mfma_f32_64x64x32_w4x2_splitk6", "mfma_f32_64x64x32_w4x2_splitk7",
+                                                  "mfma_f32_64x64x32_w4x2_splitk8"};
+  const int splits = mfma_f32_splitk(p, v);
+  if (v == 64 && splits > 1) return small_split_names[splits];
+  if (splits == 0) return "mfma_f32_128x128x32_w4x2_streamk";            // teams, the last part to arrive gathers: what MM_PATH_AUTO runs
+  if (splits == 9) return "mfma_f32_128x128x32_w4x2_streamk_fixup";      // single ranges + fix-up kernel (cross-check, its own bits)
+  if (splits == 11) return "mfma_f32_128x128x32_w4x2_streamk_two_kernels";   // teams + fix-up kernel (cross-check); the bits of `streamk`
+  if (splits == 12) return "mfma_f32_128x128x32_w4x2_streamk_ticket";        // teams, one counter ticket per part, the last ticket gathers; the bits of `streamk`
+  return splits > 1 ? split_names[splits] : mfma_f32_name(v);
+}
+
 void mfma_f32_geometry(int v, unsigned *bm, unsigned *bn, unsigned *bk, unsigned *waves) {
   const VariantInfo *i = find_variant(v);
   if (!i) i = find_variant(8);

@@ -58,6 +58,16 @@ using D1R1 = GeoD<2, 2, 2, false>;
 // 32 KiB of LDS, compiled for four wavefronts per SIMD.  Same fma chain per element as the others: identical bits.
 using DS = GeoD<2, 2, 2, false, 2, 1, 4>;
 
+// The table: one row per answer of resolve(), read by the names and mm_kernel_info; launch_resolved pairs each with its geometry.
+// Efficiency: pinned schedule + scalar-base DMA, 76.4 TF of 78.6 (profiles/r02z_f64_scalar_base_dma.log)
+constexpr KernelRow kTable[] = {
+    kernel_row<D0>("mfma_f64_256x128x16_w8", nullptr, 16, 4, 0.97),
+    kernel_row<D1>("mfma_f64_128x128x16_w4x2", nullptr, 16, 4, 0.97),
+    kernel_row<D0R1>("mfma_f64_256x128x16_w8_compiler_placed", nullptr, 16, 4, 0.97),
+    kernel_row<D1R1>("mfma_f64_128x128x16_w4x2_compiler_placed", nullptr, 16, 4, 0.97),
+    kernel_row<DS>("mfma_f64_64x64x16_w4x4", nullptr, 16, 4, 0.97),
+};
+
 }  // namespace
 
 bool mfma_f64_serves(const Problem &p) {
@@ -84,7 +94,7 @@ static int launch_d(hipStream_t s, const Problem &p) {
   return p.a_transposed ? launch_at<F, G, true>(s, p) : launch_at<F, G, false>(s, p);
 }
 
-int mfma_f64_tile(const Problem &p) {  // 0: 256x128, 1: 128x128, 4: 64x64
+static int mfma_f64_tile(const Problem &p) {  // 0: 256x128, 1: 128x128, 4: 64x64
   const int v = tuning(TUNE_F64_VARIANT);
   if (v == 4) return 4;
   if (v >= 0) return v & 1;
@@ -108,11 +118,10 @@ static int resolve(const Problem &p) {
 }
 
 const char *mfma_f64_name(const Problem &p) {
-  static const char *const names[] = {"mfma_f64_256x128x16_w8", "mfma_f64_128x128x16_w4x2", "mfma_f64_256x128x16_w8_compiler_placed",
-                                      "mfma_f64_128x128x16_w4x2_compiler_placed", "mfma_f64_64x64x16_w4x4"};
   const int r = resolve(p);
-  return r < 0 ? "unsupported" : names[r];
+  return r < 0 ? "unsupported" : kTable[r].name;
 }
+const KernelRow &mfma_f64_row(const Problem &p) { return kTable[resolve(p) < 0 ? 0 : resolve(p)]; }   // (unsupported: the default tile)
 
 template <Form F>
 static int launch_resolved(hipStream_t s, const Problem &p, int r) {   // r: resolve()'s answer

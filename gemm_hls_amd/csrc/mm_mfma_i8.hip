@@ -11,7 +11,8 @@
 //
 // Kernels in this file, as in mm_mfma_f16.hip: pingpong_16x16x64 (default: K % 128 == 0, K >= 512, row-major A),
 // pingpong_32x32x32 (cross-check, i8_variant 100), pingpong_k64 (K % 64 == 0; row-major and K x N A), slab128 (K % 32 == 0).
-// Lock-step ablations: tools/lab/lab_mfma_i8.hip.
+// Each is one row of kTable at the end of mm_mfma_i8_kernels.inc; this unit picks the row (resolve) and launches it through the
+// include's launch_kind.  Lock-step ablations: tools/lab/lab_mfma_i8.hip.
 // Organisation of slab128 as mm_mfma_f16.hip's slab64: 256 x 256 x 128(bytes) slabs, 8 wavefronts of 64 x 128, A operand
 // by one ds_read_b128 (16 consecutive k of a row, rows swizzled with (row>>1)&7), B operand (16
 // consecutive k of ONE column of the row-major B) by two ds_read_b64_tr_b8: lane i of a 16-lane
@@ -32,13 +33,6 @@ namespace {
 
 #include "mm_mfma_i8_kernels.inc"
 #undef MM_DMA_PIECE
-
-// (mm_mfma_i8_wide.hip finds its instantiations by these names: a kernel added or renamed here needs its twin there --
-// tests/test_widen_capi.py compares the tables)
-enum Kind { K_PP16, K_PP32, K_PPK64, K_PPK64_AT, K_SLAB128, K_SLAB128_AT, K_SLAB128_64, K_NONE };
-const char *const kNames[] = {"mfma_i8_256x256_pingpong_16x16x64", "mfma_i8_256x256_pingpong_32x32x32", "mfma_i8_256x256_pingpong_k64",
-                              "mfma_i8_256x256_pingpong_k64_KxN", "mfma_i8_256x256x128_slab128", "mfma_i8_256x256x128_slab128_KxN",
-                              "mfma_i8_64x256x128_slab128", "unsupported"};
 
 }  // namespace
 
@@ -89,53 +83,17 @@ static Kind resolve(const Problem &p) {
   return K_SLAB128;
 }
 
-const char *mfma_i8_name(const Problem &p) { return kNames[resolve(p)]; }
-
-// The kernel of each Kind, in form F
-template <Form F>
-static int launch_kind(hipStream_t s, const Problem &p, Kind k) {
-  switch (k) {
-    case K_PP16: return launch_tile<F, mfma_i8_pp2s_kernel<F>>(s, p, GeoI8PP2::THREADS, GeoI8PP2::LDS_BYTES);
-    case K_PP32: return launch_tile<F, mfma_i8_pp2_kernel<F>>(s, p, GeoI8PP2::THREADS, GeoI8PP2::LDS_BYTES);
-    case K_PPK64: return launch_tile<F, mfma_i8_pp_kernel<F, false>>(s, p, GeoI8PP::THREADS, GeoI8PP::LDS_BYTES);
-    case K_PPK64_AT: return launch_tile<F, mfma_i8_pp_kernel<F, true>>(s, p, GeoI8PP::THREADS, GeoI8PP::LDS_BYTES);
-    case K_SLAB128: return launch_tile<F, mfma_i8_kernel<F, GeoI8, false>>(s, p, GeoI8::THREADS, GeoI8::LDS_BYTES);
-    case K_SLAB128_AT: return launch_tile<F, mfma_i8_kernel<F, GeoI8, true>>(s, p, GeoI8::THREADS, GeoI8::LDS_BYTES);
-    case K_SLAB128_64: return launch_tile<F, mfma_i8_kernel<F, GeoI8S, false>>(s, p, GeoI8S::THREADS, GeoI8S::LDS_BYTES, GeoI8S::BM);
-    default: return kErrNotSupported;
-  }
-}
+const char *mfma_i8_name(const Problem &p) { return kTable[resolve(p)].name; }
+const KernelRow &mfma_i8_row(const Problem &p) { return kTable[resolve(p)]; }
 
 // A K x N A served where it lies (no workspace): the ping-pong K x N kernel where its shape rules allow, else slab128's
 static int launch_kxn_in_place(hipStream_t s, const Problem &p) {
-  return launch_kind<Form::Single>(s, p, tuning(TUNE_I8_VARIANT) != 0 && ppk64_serves(p) ? K_PPK64_AT : K_SLAB128_AT);
+  return launch_kind<Form::Single, signed char>(s, p, tuning(TUNE_I8_VARIANT) != 0 && ppk64_serves(p) ? K_PPK64_AT : K_SLAB128_AT);
 }
 
 int launch_mfma_i8(hipStream_t s, const Problem &p) {
-  if (transposes_first(p)) {
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess) return (int)e;
-    hipMemPool_t pool = nullptr;
-    if (int rc = workspace_pool(dev, &pool)) return rc;
-    void *an = nullptr;
-    if ((e = hipMallocFromPoolAsync(&an, (size_t)p.n * p.k, pool, s)) != hipSuccess) {
-      // no room for the N x K copy (up to 4 GiB next to a nearly full device): not an error -- the K x N kernels serve the
-      // call without extra memory, as they did before the pre-pass existed; same contract, ~2-3 % slower
-      (void)hipGetLastError();
-      return launch_kxn_in_place(s, p);
-    }
-    int rc = launch_transpose_kxn(s, p.a, an, p.k, p.n, 1);
-    if (rc == 0) {
-      Problem q = p;
-      q.a = an;
-      q.a_transposed = false;
-      rc = launch_mfma_i8(s, q);
-    }
-    const hipError_t f = hipFreeAsync(an, s);
-    return rc ? rc : (int)f;
-  }
-  return launch_kind<Form::Single>(s, p, resolve(p));
+  if (transposes_first(p)) return launch_transposed_first(s, p, 1, launch_mfma_i8, launch_kxn_in_place);
+  return launch_kind<Form::Single, signed char>(s, p, resolve(p));
 }
 
 // Batched (mm_gemm_batched_*): whole tiles of the in-place kernels, decided on the whole batch (Problem::batch copies of the
@@ -150,11 +108,11 @@ static Kind resolve_batched(const Problem &p) {
   return resolve(p);
 }
 int mfma_i8_batched_resolve(const Problem &p) { const Kind k = resolve_batched(p); return k == K_NONE ? -1 : (int)k; }
-const char *mfma_i8_batched_name(const Problem &p) { return kNames[resolve_batched(p)]; }
+const char *mfma_i8_batched_name(const Problem &p) { return kTable[resolve_batched(p)].name; }
 int launch_mfma_i8_batched(hipStream_t s, const Problem &p, int kind) {
   if (kind < 0 || kind >= (int)K_NONE) return kErrNotSupported;
   // an accumulating launch (p.seed): the same kernel with C's value in its epilogue
-  return p.seed ? launch_kind<Form::Seeded>(s, p, (Kind)kind) : launch_kind<Form::Batched>(s, p, (Kind)kind);
+  return p.seed ? launch_kind<Form::Seeded, signed char>(s, p, (Kind)kind) : launch_kind<Form::Batched, signed char>(s, p, (Kind)kind);
 }
 
 }  // namespace mm

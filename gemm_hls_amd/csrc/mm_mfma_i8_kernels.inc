@@ -1,6 +1,7 @@
-// The kernels of mm_mfma_i8.hip and mm_mfma_i8_wide.hip, their geometries and their launch.  F (mm_common.h) is the form of each:
-// the single-problem kernel, its strided-batched form, or the batched form that accumulates into C.  CT is C's element type:
-// signed char -- the low 8 bits of the i32 sums, the reference's contract -- or int, the sums themselves (mm_gemm_widen_*).
+// The kernels of mm_mfma_i8.hip and mm_mfma_i8_wide.hip, their geometries, their table (one row per kernel) and their
+// launch.  F (mm_common.h) is the form of each: the single-problem kernel, its strided-batched form, or the batched form that
+// accumulates into C.  CT is C's element type: signed char -- the low 8 bits of the i32 sums, the reference's contract -- or
+// int, the sums themselves (mm_gemm_widen_*).
 using i32x4 = __attribute__((ext_vector_type(4))) int;
 using i32x16 = __attribute__((ext_vector_type(16))) int;
 typedef int v2i __attribute__((vector_size(8)));
@@ -800,15 +801,33 @@ __global__ __launch_bounds__(GeoI8PP2::THREADS) void mfma_i8_pp2s_kernel(const s
   }
 }
 
-// One launch of the kernel KERN, an instantiation for form F: the problem at (a, b, c), or (F != Form::Single) p.batch copies of
-// the tile grid over the elements of p
-template <Form F, auto KERN, typename CT = signed char>
-static int launch_tile(hipStream_t s, const Problem &p, unsigned threads, int lds, unsigned bm = 256) {
-  const unsigned tiles_n = (p.n + bm - 1) / bm, tiles_m = (p.m + 255) / 256;
-  static unsigned long long configured = 0;   // one per instantiation of this function, so one per kernel
-  if (int e = ensure_dynamic_lds((const void *)KERN, lds, configured)) return e;
-  hipLaunchKernelGGL(KERN, dim3(tiles_n * tiles_m * (F == Form::Single ? 1u : p.batch)), dim3(threads), lds, s,
-                     (const signed char *)p.a, (const signed char *)p.b, (CT *)p.c, p.n, p.k, p.m, tiles_n, tiles_m,
-                     band_rows(bm, 256, 1), F == Form::Single ? 1u : p.batch, p.stride_a, p.stride_b, p.stride_c);
-  return (int)hipGetLastError();
+// ---- the table: one row per kernel, read by the launch, the names, the wide unit and mm_kernel_info ------------------------
+// Efficiencies: profiles/r02i_pmc_i8_32768.json (ping-pong) / r01_pmc_i8.json (slab128)
+enum Kind { K_PP16, K_PP32, K_PPK64, K_PPK64_AT, K_SLAB128, K_SLAB128_AT, K_SLAB128_64, K_NONE };
+constexpr KernelRow kTable[] = {
+    kernel_row<GeoI8PP2>("mfma_i8_256x256_pingpong_16x16x64", "mfma_i8_256x256_pingpong_16x16x64_wide", 16, 64, 0.92),
+    kernel_row<GeoI8PP2>("mfma_i8_256x256_pingpong_32x32x32", "mfma_i8_256x256_pingpong_32x32x32_wide", 32, 32, 0.92),
+    kernel_row<GeoI8PP>("mfma_i8_256x256_pingpong_k64", "mfma_i8_256x256_pingpong_k64_wide", 32, 32, 0.92),
+    kernel_row<GeoI8PP>("mfma_i8_256x256_pingpong_k64_KxN", "mfma_i8_256x256_pingpong_k64_KxN_wide", 32, 32, 0.92),
+    kernel_row<GeoI8>("mfma_i8_256x256x128_slab128", "mfma_i8_256x256x128_slab128_wide", 32, 32, 0.68),
+    kernel_row<GeoI8>("mfma_i8_256x256x128_slab128_KxN", "mfma_i8_256x256x128_slab128_KxN_wide", 32, 32, 0.68),
+    kernel_row<GeoI8S>("mfma_i8_64x256x128_slab128", "mfma_i8_64x256x128_slab128_wide", 32, 32, 0.68),
+    kernel_row<GeoI8>("unsupported", nullptr, 32, 32, 0.68),   // K_NONE: described as the catch-all, slab128
+};
+static_assert(sizeof(kTable) / sizeof(kTable[0]) == K_NONE + 1, "one row per Kind");
+
+// The kernel of each Kind in form F, with a C of type CT (signed char, or int for the wide unit)
+template <Form F, typename CT>
+static int launch_kind(hipStream_t s, const Problem &p, Kind k) {
+  using T = signed char;
+  switch (k) {
+    case K_PP16: return launch_tile<F, GeoI8PP2, mfma_i8_pp2s_kernel<F, CT>, T, CT>(s, p);
+    case K_PP32: return launch_tile<F, GeoI8PP2, mfma_i8_pp2_kernel<F, CT>, T, CT>(s, p);
+    case K_PPK64: return launch_tile<F, GeoI8PP, mfma_i8_pp_kernel<F, false, CT>, T, CT>(s, p);
+    case K_PPK64_AT: return launch_tile<F, GeoI8PP, mfma_i8_pp_kernel<F, true, CT>, T, CT>(s, p);
+    case K_SLAB128: return launch_tile<F, GeoI8, mfma_i8_kernel<F, GeoI8, false, CT>, T, CT>(s, p);
+    case K_SLAB128_AT: return launch_tile<F, GeoI8, mfma_i8_kernel<F, GeoI8, true, CT>, T, CT>(s, p);
+    case K_SLAB128_64: return launch_tile<F, GeoI8S, mfma_i8_kernel<F, GeoI8S, false, CT>, T, CT>(s, p);
+    default: return kErrNotSupported;
+  }
 }

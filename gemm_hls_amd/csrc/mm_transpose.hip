@@ -71,4 +71,28 @@ bool transposes_first_small(const Problem &p, unsigned elem_size) {
   return p.a_transposed && p.m >= min_m && p.n >= 1024 && (unsigned long long)p.n * p.k * elem_size <= (4ull << 30);
 }
 
+int launch_transposed_first(hipStream_t s, const Problem &p, unsigned elem_size, ProblemLauncher row_major, ProblemLauncher in_place) {
+  int dev = 0;
+  hipError_t e = hipGetDevice(&dev);
+  if (e != hipSuccess) return (int)e;
+  hipMemPool_t pool = nullptr;
+  if (int rc = workspace_pool(dev, &pool)) return rc;
+  void *an = nullptr;
+  if ((e = hipMallocFromPoolAsync(&an, (size_t)p.n * p.k * elem_size, pool, s)) != hipSuccess) {
+    // no room for the N x K copy (up to 4 GiB next to a nearly full device): not an error -- the K x N kernels serve the
+    // call without extra memory, as they did before the pre-pass existed; same contract, ~2-3 % slower
+    (void)hipGetLastError();
+    return in_place(s, p);
+  }
+  int rc = launch_transpose_kxn(s, p.a, an, p.k, p.n, elem_size);
+  if (rc == 0) {
+    Problem q = p;
+    q.a = an;
+    q.a_transposed = false;
+    rc = row_major(s, q);
+  }
+  const hipError_t f = hipFreeAsync(an, s);
+  return rc ? rc : (int)f;
+}
+
 }  // namespace mm

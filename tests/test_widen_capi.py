@@ -96,21 +96,52 @@ def test_kernel_name_widen_table():
     assert g.kernel_name_widen(_cfg("half"), 512, 512, 512, 0) == g.kernel_name_widen(_cfg("half"), 512, 512, 512, 1)
 
 
+# A (knob value, K x N A, (n, k, m)) whose batched resolver picks each row of a family's kernel table
+ROW_SHAPES = {
+    "f16": ("f16_variant", {
+        "mfma_f16_256x256_pingpong_16x16x32": (-1, False, (256, 256, 256)), "mfma_f16_256x256_pingpong_32x32x16": (100, False, (256, 256, 256)),
+        "mfma_f16_256x256_pingpong_k32": (-1, False, (256, 128, 256)), "mfma_f16_256x256_pingpong_k32_KxN": (-1, True, (256, 256, 256)),
+        "mfma_f16_256x256x64_slab64": (0, False, (256, 48, 256)), "mfma_f16_256x256x64_slab64_KxN": (0, True, (256, 48, 256)),
+        "mfma_f16_128x256x64_slab64": (4, False, (256, 48, 256)), "mfma_f16_64x256x64_slab64": (5, False, (256, 48, 256))}),
+    "i8": ("i8_variant", {
+        "mfma_i8_256x256_pingpong_16x16x64": (-1, False, (512, 512, 512)), "mfma_i8_256x256_pingpong_32x32x32": (100, False, (512, 512, 512)),
+        "mfma_i8_256x256_pingpong_k64": (-1, False, (256, 256, 256)), "mfma_i8_256x256_pingpong_k64_KxN": (-1, True, (256, 256, 256)),
+        "mfma_i8_256x256x128_slab128": (0, False, (256, 96, 256)), "mfma_i8_256x256x128_slab128_KxN": (0, True, (256, 96, 256)),
+        "mfma_i8_64x256x128_slab128": (5, False, (256, 96, 256))}),
+}
+
+
 @pytest.mark.parametrize("family", ["i8", "f16"])
 def test_every_narrow_matrix_core_kernel_has_a_wide_instantiation(family):
-    """The wide units find their kernel by the NARROW kernel's name (the narrow units may not grow symbols): a narrow kernel
-    renamed or added without its wide twin would quietly send widening calls to widen_ordered."""
+    """A family's kernels are described in ONE table (mm_mfma_<family>_kernels.inc), which the narrow and the wide unit both
+    include: each row names the kernel and its wide twin, and one launch_kind serves both C types.  No unit keeps a second
+    name table or a second switch, and every row's shape resolves to that row's wide name."""
     csrc = os.path.join(ROOT, "gemm_hls_amd", "csrc")
-    narrow_unit = open(os.path.join(csrc, f"mm_mfma_{family}.hip")).read()
-    wide_unit = open(os.path.join(csrc, f"mm_mfma_{family}_wide.hip")).read()
-
-    def table(text, name):
-        body = re.search(rf"{name}\[\] = \{{(.*?)\}};", text, flags=re.S).group(1)
-        return re.findall(r'"([^"]+)"', body)
-    names = [x for x in table(narrow_unit, "kNames") if x != "unsupported"]
-    assert len(names) >= 7 and table(wide_unit, "kNarrow") == names
-    assert table(wide_unit, "kWide") == [x + "_wide" for x in names]
-    assert wide_unit.count("case ") == len(names)        # one launch per entry
+    inc, narrow_unit, wide_unit = (open(os.path.join(csrc, f)).read() for f in
+                                   (f"mm_mfma_{family}_kernels.inc", f"mm_mfma_{family}.hip", f"mm_mfma_{family}_wide.hip"))
+    everything = inc + narrow_unit + wide_unit
+    assert len(re.findall(r"\w+\[\] = \{\s*kernel_row<", everything)) == 1 and inc.count("kTable[] = {") == 1
+    for gone in ("kNarrow", "kWide", "kNames", "launch_index"):
+        assert gone not in everything, gone
+    assert inc.count("switch (") == 1 and "switch (" not in wide_unit and "case K_" not in narrow_unit + wide_unit
+    body = re.search(r"kTable\[\] = \{(.*?)\n\};", inc, flags=re.S).group(1)
+    rows = re.findall(r'kernel_row<\w+>\("([^"]+)", (?:"([^"]+)"|nullptr)', body)
+    assert len(rows) >= 8 and rows[-1] == ("unsupported", "")
+    assert inc.count("case K_") == len(rows) - 1          # one launch per kernel
+    knob, shapes = ROW_SHAPES[family]
+    assert sorted(shapes) == sorted(name for name, _ in rows[:-1])
+    dtype = {"i8": "int8_t", "f16": "half"}[family]
+    old = g.get_tuning(knob)
+    try:
+        for name, wide in rows[:-1]:
+            assert wide == name + "_wide"
+            value, transposed, (n, k, m) = shapes[name]
+            g.set_tuning(knob, value)
+            cfg = _cfg(dtype, transposed_a=transposed)
+            assert g.kernel_name_batched(cfg, n, k, m, 1) == name
+            assert g.kernel_name_widen(cfg, n, k, m, 1) == wide
+    finally:
+        g.set_tuning(knob, old)
 
 
 def test_kernel_name_widen_unsupported_and_invalid():

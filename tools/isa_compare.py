@@ -3,14 +3,18 @@
 to assembly with the flags the product is built with (build.COMMON without --offload-compress, plus build.EXTRA[unit]).
 
     python tools/isa_compare.py OLD_TREE NEW_TREE [unit ...]        # default: the nine units whose kernels take a Form
+    python tools/isa_compare.py --same-naming OLD_TREE NEW_TREE [unit ...]   # default: every .hip unit of NEW_TREE's csrc
 
-OLD_TREE names a kernel's form in its symbol (`*_batched`, `*_batched_seeded`), NEW_TREE in a template argument
+Without --same-naming, OLD_TREE names a kernel's form in its symbol (`*_batched`, `*_batched_seeded`), NEW_TREE in a template argument
 (`(mm::Form)N`; mfma_f32_batched_kernel: a trailing `bool SEED`).  Kernels are paired by (base name, form, the remaining
 template arguments).  A pair is identical when the instruction streams are equal line for line -- comments, assembler
 directives and blank lines dropped, local labels (.LBB<n>_<m>) renumbered in order of appearance -- and the .amdhsa_
 resource lines are equal (registers, LDS, private segment, user SGPRs).  Only .amdhsa_kernarg_size of a Form::Single
 kernel may differ: it gained the batch arguments it never loads.  Prints one line per unit; exit status 1 on any
 difference, unpaired kernel or changed kernel count.
+
+--same-naming: both trees name a kernel's form in a template argument (a host-side refactor, say).  Kernels are paired by
+their whole demangled name and nothing may differ, .amdhsa_kernarg_size included.
 """
 import concurrent.futures
 import os
@@ -58,13 +62,17 @@ def kernels(asm):
     return out
 
 
-def keyed(kerns, new):
-    """{(base name, form, other template arguments): symbol}"""
+def keyed(kerns, new, same_naming=False):
+    """{(base name, form, other template arguments): symbol}; same_naming: {(demangled name, "", ""): symbol}"""
     # _Float16 (DF16_) is newer than some c++filt; a builtin type takes no substitution slot, so `Dh` (half) stands in
     names = subprocess.run(["c++filt"], input="\n".join(k.replace("DF16_", "Dh") for k in kerns), capture_output=True,
                            text=True, check=True).stdout.split("\n")
     out = {}
     for sym, d in zip(kerns, names):
+        if same_naming:
+            assert (d, "", "") not in out, d
+            out[(d, "", "")] = sym
+            continue
         m = re.match(r"(?:void )?(?:[\w:]|\(anonymous namespace\))*?(\w+)(?:<(.*)>)?\((?:[^()]|\(anonymous namespace\))*\)$", d)
         assert m, d
         base, args, form = m.group(1), m.group(2) or "", 0
@@ -82,9 +90,9 @@ def keyed(kerns, new):
     return out
 
 
-def compare(old_tree, new_tree, unit):
+def compare(old_tree, new_tree, unit, same_naming=False):
     old, new = kernels(assembly(old_tree, unit)), kernels(assembly(new_tree, unit))
-    ko, kn = keyed(old, False), keyed(new, True)
+    ko, kn = keyed(old, False, same_naming), keyed(new, True, same_naming)
     notes, same = [], 0
     for key in sorted(ko.keys() & kn.keys()):
         (bo, ro), (bn, rn) = old[ko[key]], new[kn[key]]
@@ -103,11 +111,14 @@ def compare(old_tree, new_tree, unit):
 
 
 def main():
-    if len(sys.argv) < 3:
+    argv = [a for a in sys.argv[1:] if a != "--same-naming"]
+    same_naming = len(argv) < len(sys.argv) - 1
+    if len(argv) < 2:
         raise SystemExit(__doc__)
-    units = sys.argv[3:] or UNITS
+    every = sorted(f for f in os.listdir(os.path.join(argv[1], "gemm_hls_amd", "csrc")) if f.endswith(".hip"))
+    units = argv[2:] or (every if same_naming else UNITS)
     with concurrent.futures.ThreadPoolExecutor(max_workers=min(8, os.cpu_count() or 4) // 2 or 1) as ex:
-        results = list(ex.map(lambda u: compare(sys.argv[1], sys.argv[2], u), units))
+        results = list(ex.map(lambda u: compare(argv[0], argv[1], u, same_naming), units))
     for text, _ in results:
         print(text)
     return 0 if all(ok for _, ok in results) else 1

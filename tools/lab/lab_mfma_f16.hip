@@ -1186,6 +1186,10 @@ int mfma_f16_tile(const Problem &p) {  // 0: 256x256, 4: 128x256
 }
 
 const char *mfma_f16_name(const Problem &) { return "mfma_f16_lab"; }   // the lab does not name its schedules
+const KernelRow &mfma_f16_row(const Problem &) {   // ... nor describe them: the slab kernel's figures
+  static const KernelRow row = {"mfma_f16_lab", nullptr, 256, 256, 64, 8, 32, 32, 16, 0.67};
+  return row;
+}
 
 int launch_mfma_f16(hipStream_t s, const Problem &p) {
   if (!mfma_f16_serves(p)) return kErrNotSupported;

@@ -947,6 +947,7 @@ static bool sdma_fits(const Problem &p, unsigned bk) {
 }
 
 int mfma_f32_splitk(const Problem &, int) { return 1; }   // the lab edition never splits K
+const char *mfma_f32_launch_name(const Problem &, int v) { return mfma_f32_name(v); }
 // ... and has no batched form: mm_gemm_batched_* of this library run fp32 (Multiply, Add) on the VALU families
 int mfma_f32_batched_resolve(const Problem &, int) { return -1; }
 int launch_mfma_f32_batched(hipStream_t, const Problem &, int) { return kErrNotSupported; }

@@ -809,6 +809,10 @@ static int launch_i8_pp2s(hipStream_t s, const Problem &p) {
 }
 
 const char *mfma_i8_name(const Problem &) { return "mfma_i8_lab"; }   // the lab does not name its schedules
+const KernelRow &mfma_i8_row(const Problem &) {   // ... nor describe them: the slab kernel's figures
+  static const KernelRow row = {"mfma_i8_lab", nullptr, 256, 256, 128, 8, 32, 32, 32, 0.68};
+  return row;
+}
 
 int launch_mfma_i8(hipStream_t s, const Problem &p) {
   if (!mfma_i8_serves(p)) return kErrNotSupported;
