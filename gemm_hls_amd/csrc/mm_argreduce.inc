@@ -299,25 +299,12 @@ int ar_launch(hipStream_t s, const Problem &p, int *index, int index_base, bool 
   return (int)hipGetLastError();
 }
 
-template <typename T, int MAP>
-int ar_red(hipStream_t s, int red, const Problem &p, int *index, int index_base, bool tile) {
-  switch (red) {
-    case MM_OP_MIN: return ar_launch<T, MAP, MM_OP_MIN>(s, p, index, index_base, tile);
-    case MM_OP_MAX: return ar_launch<T, MAP, MM_OP_MAX>(s, p, index, index_base, tile);
-  }
-  return kErrNotSupported;
-}
-
-template <typename T>
-int ar_type(hipStream_t s, const mm_config_t &cfg, const Problem &p, int *index, int index_base, bool tile) {
-  switch (cfg.map_op) {
-    case MM_OP_ADD: return ar_red<T, MM_OP_ADD>(s, cfg.reduce_op, p, index, index_base, tile);
-    case MM_OP_MULTIPLY: return ar_red<T, MM_OP_MULTIPLY>(s, cfg.reduce_op, p, index, index_base, tile);
-    case MM_OP_AND: return ar_red<T, MM_OP_AND>(s, cfg.reduce_op, p, index, index_base, tile);
-    case MM_OP_MIN: return ar_red<T, MM_OP_MIN>(s, cfg.reduce_op, p, index, index_base, tile);
-    case MM_OP_MAX: return ar_red<T, MM_OP_MAX>(s, cfg.reduce_op, p, index, index_base, tile);
-  }
-  return kErrNotSupported;
+// TYPES: the element types the including unit instantiates
+template <typename TYPES>
+int ar_dispatch(hipStream_t s, const mm_config_t &cfg, const Problem &p, int *index, int index_base, bool tile) {
+  return switch_config<TYPES, AllOps, MinMaxOps>(cfg, [&](auto t, auto map, auto red) {
+    return ar_launch<type_of<decltype(t)>, decltype(map)::value, decltype(red)::value>(s, p, index, index_base, tile);
+  });
 }
 
 }  // namespace

@@ -3,11 +3,6 @@
 #include "mm_argreduce.inc"
 namespace mm {
 int launch_argreduce_fp(hipStream_t s, const mm_config_t &cfg, const Problem &p, int *index, int index_base, bool tile) {
-  switch (cfg.dtype) {
-    case MM_DTYPE_F32: return ar_type<float>(s, cfg, p, index, index_base, tile);
-    case MM_DTYPE_F64: return ar_type<double>(s, cfg, p, index, index_base, tile);
-    case MM_DTYPE_F16: return ar_type<half_t>(s, cfg, p, index, index_base, tile);
-    default: return kErrNotSupported;
-  }
+  return ar_dispatch<FpTypes>(s, cfg, p, index, index_base, tile);
 }
 }  // namespace mm

@@ -11,11 +11,7 @@ int launch_argreduce(hipStream_t s, const mm_config_t &cfg, const Problem &p, in
     case MM_DTYPE_F32: case MM_DTYPE_F64: case MM_DTYPE_F16: return launch_argreduce_fp(s, cfg, p, index, index_base, tile);
     case MM_DTYPE_I8: case MM_DTYPE_U8: case MM_DTYPE_I16: case MM_DTYPE_U16:
       return launch_argreduce_int_narrow(s, cfg, p, index, index_base, tile);
-    case MM_DTYPE_I32: return ar_type<int32_t>(s, cfg, p, index, index_base, tile);
-    case MM_DTYPE_U32: return ar_type<uint32_t>(s, cfg, p, index, index_base, tile);
-    case MM_DTYPE_I64: return ar_type<int64_t>(s, cfg, p, index, index_base, tile);
-    case MM_DTYPE_U64: return ar_type<uint64_t>(s, cfg, p, index, index_base, tile);
+    default: return ar_dispatch<WideIntTypes>(s, cfg, p, index, index_base, tile);
   }
-  return kErrNotSupported;
 }
 }  // namespace mm

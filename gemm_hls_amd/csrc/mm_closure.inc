@@ -227,26 +227,14 @@ int cl_launch(hipStream_t s, const ClosureStep &st) {
   return (int)hipGetLastError();
 }
 
-template <typename T, int MAP>
-int cl_red(hipStream_t s, int red, const ClosureStep &st) {
-  const bool wit = st.w != nullptr;
-  switch (red) {
-    case MM_OP_MIN: return wit ? cl_launch<T, MAP, MM_OP_MIN, true>(s, st) : cl_launch<T, MAP, MM_OP_MIN, false>(s, st);
-    case MM_OP_MAX: return wit ? cl_launch<T, MAP, MM_OP_MAX, true>(s, st) : cl_launch<T, MAP, MM_OP_MAX, false>(s, st);
-  }
-  return kErrNotSupported;
-}
-
-template <typename T>
-int cl_type(hipStream_t s, const mm_config_t &cfg, const ClosureStep &st) {
-  switch (cfg.map_op) {
-    case MM_OP_ADD: return cl_red<T, MM_OP_ADD>(s, cfg.reduce_op, st);
-    case MM_OP_MULTIPLY: return cl_red<T, MM_OP_MULTIPLY>(s, cfg.reduce_op, st);
-    case MM_OP_AND: return cl_red<T, MM_OP_AND>(s, cfg.reduce_op, st);
-    case MM_OP_MIN: return cl_red<T, MM_OP_MIN>(s, cfg.reduce_op, st);
-    case MM_OP_MAX: return cl_red<T, MM_OP_MAX>(s, cfg.reduce_op, st);
-  }
-  return kErrNotSupported;
+// TYPES: the element types the including unit instantiates
+template <typename TYPES>
+int cl_dispatch(hipStream_t s, const mm_config_t &cfg, const ClosureStep &st) {
+  return switch_config<TYPES, AllOps, MinMaxOps>(cfg, [&](auto t, auto map, auto red) {
+    using T = type_of<decltype(t)>;
+    constexpr int MAP = decltype(map)::value, RED = decltype(red)::value;
+    return st.w != nullptr ? cl_launch<T, MAP, RED, true>(s, st) : cl_launch<T, MAP, RED, false>(s, st);
+  });
 }
 
 }  // namespace

@@ -9,11 +9,7 @@ int launch_closure(hipStream_t s, const mm_config_t &cfg, const ClosureStep &st)
   switch (cfg.dtype) {
     case MM_DTYPE_F32: case MM_DTYPE_F64: case MM_DTYPE_F16: return launch_closure_fp(s, cfg, st);
     case MM_DTYPE_I8: case MM_DTYPE_U8: case MM_DTYPE_I16: case MM_DTYPE_U16: return launch_closure_int_narrow(s, cfg, st);
-    case MM_DTYPE_I32: return cl_type<int32_t>(s, cfg, st);
-    case MM_DTYPE_U32: return cl_type<uint32_t>(s, cfg, st);
-    case MM_DTYPE_I64: return cl_type<int64_t>(s, cfg, st);
-    case MM_DTYPE_U64: return cl_type<uint64_t>(s, cfg, st);
+    default: return cl_dispatch<WideIntTypes>(s, cfg, st);
   }
-  return kErrNotSupported;
 }
 }  // namespace mm

@@ -237,6 +237,76 @@ int launch_fill(hipStream_t s, mm_dtype_t dtype, void *ptr, size_t elements, uns
 
 constexpr int kErrNotSupported = 801;  // hipErrorNotSupported
 
+// ---- host dispatch: a config's run-time dtype, map and reduce to template arguments -----------
+// switch_dtype<Types<...>>(dtype, f) returns f(Tag<T>{}) for the element type T of `dtype`; switch_op<Ops<...>>(op, f)
+// returns f(std::integral_constant<int, OP>{}) (map_op and reduce_op are one enum, so one switch serves both).  A value
+// the list does not hold is kErrNotSupported and instantiates nothing: the lists a compile unit names are the kernels
+// it holds.
+template <typename T> struct Tag { using type = T; };
+template <typename TAG> using type_of = typename TAG::type;
+template <typename... Ts> struct Types {
+  template <typename T> static constexpr bool has = (std::is_same<T, Ts>::value || ...);
+};
+template <int... OPS> struct Ops {
+  template <int OP> static constexpr bool has = ((OP == OPS) || ...);
+};
+using FpTypes = Types<float, double, half_t>;
+using NarrowIntTypes = Types<int8_t, uint8_t, int16_t, uint16_t>;
+using WideIntTypes = Types<int32_t, uint32_t, int64_t, uint64_t>;
+using AllTypes = Types<float, double, half_t, int8_t, uint8_t, int16_t, uint16_t, int32_t, uint32_t, int64_t, uint64_t>;
+using AllOps = Ops<MM_OP_ADD, MM_OP_MULTIPLY, MM_OP_AND, MM_OP_MIN, MM_OP_MAX>;
+using MinMaxOps = Ops<MM_OP_MIN, MM_OP_MAX>;
+
+// In both switches a case the list does not hold leaves the switch (`else break`) for the kErrNotSupported below; it must be
+// the `else` of the `if constexpr`, so that f is not instantiated for it.
+template <typename TYPES, typename Fn>
+int switch_dtype(int dtype, Fn f) {
+  switch (dtype) {
+#define MM_CASE(D, T) \
+  case D:             \
+    if constexpr (TYPES::template has<T>) return f(Tag<T>{}); else break;
+    MM_CASE(MM_DTYPE_F32, float)
+    MM_CASE(MM_DTYPE_F64, double)
+    MM_CASE(MM_DTYPE_F16, half_t)
+    MM_CASE(MM_DTYPE_I8, int8_t)
+    MM_CASE(MM_DTYPE_U8, uint8_t)
+    MM_CASE(MM_DTYPE_I16, int16_t)
+    MM_CASE(MM_DTYPE_U16, uint16_t)
+    MM_CASE(MM_DTYPE_I32, int32_t)
+    MM_CASE(MM_DTYPE_U32, uint32_t)
+    MM_CASE(MM_DTYPE_I64, int64_t)
+    MM_CASE(MM_DTYPE_U64, uint64_t)
+#undef MM_CASE
+  }
+  return kErrNotSupported;
+}
+
+template <typename OPS, typename Fn>
+int switch_op(int op, Fn f) {
+  switch (op) {
+#define MM_CASE(OP) \
+  case OP:          \
+    if constexpr (OPS::template has<OP>) return f(std::integral_constant<int, OP>{}); else break;
+    MM_CASE(MM_OP_ADD)
+    MM_CASE(MM_OP_MULTIPLY)
+    MM_CASE(MM_OP_AND)
+    MM_CASE(MM_OP_MIN)
+    MM_CASE(MM_OP_MAX)
+#undef MM_CASE
+  }
+  return kErrNotSupported;
+}
+
+// f(Tag<T>, map, reduce) for cfg's (dtype, map_op, reduce_op), each from its list
+template <typename TYPES, typename MAPS, typename REDS, typename Fn>
+int switch_config(const mm_config_t &cfg, Fn f) {
+  return switch_dtype<TYPES>(cfg.dtype, [&](auto t) {
+    return switch_op<MAPS>(cfg.map_op, [&](auto map) {
+      return switch_op<REDS>(cfg.reduce_op, [&](auto red) { return f(t, map, red); });
+    });
+  });
+}
+
 // Kernels that need more than 64 KiB of dynamic LDS must opt in once per (function, device).
 // `mask` is a per-kernel static bitmask of devices already configured.
 inline int ensure_dynamic_lds(const void *func, int bytes, unsigned long long &mask) {

@@ -55,30 +55,22 @@ int lse_epilogue_launch(hipStream_t s, const LseEpilogue &ep) {
   return (int)hipGetLastError();
 }
 
-// (dtype, reduce) -> f<T, RED>(args...); kErrNotSupported outside half / float / double x Min / Max
-#define MM_LSE_SWITCH(cfg, fn, ...)                                                                  \
-  do {                                                                                               \
-    const bool mn_ = (cfg).reduce_op == MM_OP_MIN;                                                   \
-    if ((cfg).map_op != MM_OP_ADD || ((cfg).reduce_op != MM_OP_MIN && (cfg).reduce_op != MM_OP_MAX)) \
-      return kErrNotSupported;                                                                       \
-    switch ((cfg).dtype) {                                                                           \
-      case MM_DTYPE_F32: return mn_ ? fn<float, MM_OP_MIN>(__VA_ARGS__) : fn<float, MM_OP_MAX>(__VA_ARGS__);   \
-      case MM_DTYPE_F64: return mn_ ? fn<double, MM_OP_MIN>(__VA_ARGS__) : fn<double, MM_OP_MAX>(__VA_ARGS__); \
-      case MM_DTYPE_F16: return mn_ ? fn<half_t, MM_OP_MIN>(__VA_ARGS__) : fn<half_t, MM_OP_MAX>(__VA_ARGS__); \
-      default: return kErrNotSupported;                                                              \
-    }                                                                                                \
-  } while (0)
+// half / float / double x (Add, Min / Max) -> f(Tag<T>, Add, RED)
+template <typename Fn>
+int lse_dispatch(const mm_config_t &cfg, Fn f) {
+  return switch_config<FpTypes, Ops<MM_OP_ADD>, MinMaxOps>(cfg, f);
+}
 
 }  // namespace
 
 int launch_lse_exact(hipStream_t s, const mm_config_t &cfg, const Problem &p, const int *flags) {
-  MM_LSE_SWITCH(cfg, lse_exact_launch, s, p, flags);
+  return lse_dispatch(cfg, [&](auto t, auto, auto red) { return lse_exact_launch<type_of<decltype(t)>, decltype(red)::value>(s, p, flags); });
 }
 int launch_lse_prepass(hipStream_t s, const mm_config_t &cfg, const LseOperand &op) {
-  MM_LSE_SWITCH(cfg, lse_prepass_launch, s, op);
+  return lse_dispatch(cfg, [&](auto t, auto, auto red) { return lse_prepass_launch<type_of<decltype(t)>, decltype(red)::value>(s, op); });
 }
 int launch_lse_epilogue(hipStream_t s, const mm_config_t &cfg, const LseEpilogue &ep) {
-  MM_LSE_SWITCH(cfg, lse_epilogue_launch, s, ep);
+  return lse_dispatch(cfg, [&](auto t, auto, auto red) { return lse_epilogue_launch<type_of<decltype(t)>, decltype(red)::value>(s, ep); });
 }
 
 }  // namespace mm

@@ -126,46 +126,11 @@ int launch_t(hipStream_t s, const Problem &p) {
   return p.a_transposed ? launch_at<F, T, MAP, RED, true, ACC>(s, p) : launch_at<F, T, MAP, RED, false, ACC>(s, p);
 }
 
-template <Form F, typename T, int MAP>
-int launch_red(hipStream_t s, int red, const Problem &p) {
-  switch (red) {
-    case MM_OP_ADD: return launch_t<F, T, MAP, MM_OP_ADD>(s, p);
-    case MM_OP_MULTIPLY: return launch_t<F, T, MAP, MM_OP_MULTIPLY>(s, p);
-    case MM_OP_AND: return launch_t<F, T, MAP, MM_OP_AND>(s, p);
-    case MM_OP_MIN: return launch_t<F, T, MAP, MM_OP_MIN>(s, p);
-    case MM_OP_MAX: return launch_t<F, T, MAP, MM_OP_MAX>(s, p);
-  }
-  return kErrNotSupported;
-}
-
-template <Form F, typename T>
-int launch_map(hipStream_t s, const mm_config_t &cfg, const Problem &p) {
-  switch (cfg.map_op) {
-    case MM_OP_ADD: return launch_red<F, T, MM_OP_ADD>(s, cfg.reduce_op, p);
-    case MM_OP_MULTIPLY: return launch_red<F, T, MM_OP_MULTIPLY>(s, cfg.reduce_op, p);
-    case MM_OP_AND: return launch_red<F, T, MM_OP_AND>(s, cfg.reduce_op, p);
-    case MM_OP_MIN: return launch_red<F, T, MM_OP_MIN>(s, cfg.reduce_op, p);
-    case MM_OP_MAX: return launch_red<F, T, MM_OP_MAX>(s, cfg.reduce_op, p);
-  }
-  return kErrNotSupported;
-}
-
 template <Form F>
 int launch_type(hipStream_t s, const mm_config_t &cfg, const Problem &p) {
-  switch (cfg.dtype) {
-    case MM_DTYPE_F32: return launch_map<F, float>(s, cfg, p);
-    case MM_DTYPE_F64: return launch_map<F, double>(s, cfg, p);
-    case MM_DTYPE_F16: return launch_map<F, half_t>(s, cfg, p);
-    case MM_DTYPE_I8: return launch_map<F, int8_t>(s, cfg, p);
-    case MM_DTYPE_U8: return launch_map<F, uint8_t>(s, cfg, p);
-    case MM_DTYPE_I16: return launch_map<F, int16_t>(s, cfg, p);
-    case MM_DTYPE_U16: return launch_map<F, uint16_t>(s, cfg, p);
-    case MM_DTYPE_I32: return launch_map<F, int32_t>(s, cfg, p);
-    case MM_DTYPE_U32: return launch_map<F, uint32_t>(s, cfg, p);
-    case MM_DTYPE_I64: return launch_map<F, int64_t>(s, cfg, p);
-    case MM_DTYPE_U64: return launch_map<F, uint64_t>(s, cfg, p);
-  }
-  return kErrNotSupported;
+  return switch_config<AllTypes, AllOps, AllOps>(cfg, [&](auto t, auto map, auto red) {
+    return launch_t<F, type_of<decltype(t)>, decltype(map)::value, decltype(red)::value>(s, p);
+  });
 }
 
 }  // namespace

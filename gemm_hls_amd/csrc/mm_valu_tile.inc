@@ -362,27 +362,15 @@ int vt_launch(hipStream_t s, const Problem &p) {
   else return p.seed ? vt_launch_form<Form::Seeded, T, MAP, RED>(s, p) : vt_launch_form<Form::Batched, T, MAP, RED>(s, p);
 }
 
-template <typename T, int MAP, bool BATCHED>
-int vt_red(hipStream_t s, int red, const Problem &p) {
-  switch (red) {
-    case MM_OP_ADD: return vt_launch<T, MAP, MM_OP_ADD, BATCHED>(s, p);
-    case MM_OP_MIN: return vt_launch<T, MAP, MM_OP_MIN, BATCHED>(s, p);
-    case MM_OP_MAX: return vt_launch<T, MAP, MM_OP_MAX, BATCHED>(s, p);
-  }
-  return kErrNotSupported;  // Multiply / And reductions: ordered kernel
-}
-
-template <typename T, bool BATCHED = false>
-int vt_type(hipStream_t s, const mm_config_t &cfg, const Problem &p) {
+// TYPES: the element types the including unit instantiates.  An And map, a Multiply or And reduction: the ordered kernel
+template <typename TYPES, bool BATCHED>
+int vt_dispatch(hipStream_t s, const mm_config_t &cfg, const Problem &p) {
   if (p.k % 4 != 0 || p.m % 4 != 0 || (p.a_transposed && p.n % 4 != 0)) return kErrNotSupported;
-  switch (cfg.map_op) {
-    case MM_OP_MULTIPLY: return vt_red<T, MM_OP_MULTIPLY, BATCHED>(s, cfg.reduce_op, p);
-    case MM_OP_ADD: return vt_red<T, MM_OP_ADD, BATCHED>(s, cfg.reduce_op, p);
-    case MM_OP_MIN: return vt_red<T, MM_OP_MIN, BATCHED>(s, cfg.reduce_op, p);
-    case MM_OP_MAX: return vt_red<T, MM_OP_MAX, BATCHED>(s, cfg.reduce_op, p);
-    default: break;
-  }
-  return kErrNotSupported;  // And map: ordered kernel
+  using Maps = Ops<MM_OP_MULTIPLY, MM_OP_ADD, MM_OP_MIN, MM_OP_MAX>;
+  using Reds = Ops<MM_OP_ADD, MM_OP_MIN, MM_OP_MAX>;
+  return switch_config<TYPES, Maps, Reds>(cfg, [&](auto t, auto map, auto red) {
+    return vt_launch<type_of<decltype(t)>, decltype(map)::value, decltype(red)::value, BATCHED>(s, p);
+  });
 }
 
 }  // namespace

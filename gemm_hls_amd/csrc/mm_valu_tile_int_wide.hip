@@ -26,12 +26,8 @@ int launch_valu_tile(hipStream_t s, const mm_config_t &cfg, const Problem &p) {
     case MM_DTYPE_F32: case MM_DTYPE_F64: case MM_DTYPE_F16: return launch_valu_tile_fp(s, cfg, p);
     case MM_DTYPE_I8: case MM_DTYPE_U8: case MM_DTYPE_I16: case MM_DTYPE_U16:
       return launch_valu_tile_int_narrow(s, cfg, p);
-    case MM_DTYPE_I32: return vt_type<int32_t>(s, cfg, p);
-    case MM_DTYPE_U32: return vt_type<uint32_t>(s, cfg, p);
-    case MM_DTYPE_I64: return vt_type<int64_t>(s, cfg, p);
-    case MM_DTYPE_U64: return vt_type<uint64_t>(s, cfg, p);
+    default: return vt_dispatch<WideIntTypes, false>(s, cfg, p);
   }
-  return kErrNotSupported;
 }
 
 // the batched forms of the two launchers above (p.batch elements, strides p.stride_*): the same kernel per element
@@ -47,11 +43,7 @@ int launch_valu_tile_batched(hipStream_t s, const mm_config_t &cfg, const Proble
     case MM_DTYPE_F32: case MM_DTYPE_F64: case MM_DTYPE_F16: return launch_valu_tile_fp_batched(s, cfg, p);
     case MM_DTYPE_I8: case MM_DTYPE_U8: case MM_DTYPE_I16: case MM_DTYPE_U16:
       return launch_valu_tile_int_narrow_batched(s, cfg, p);
-    case MM_DTYPE_I32: return vt_type<int32_t, true>(s, cfg, p);
-    case MM_DTYPE_U32: return vt_type<uint32_t, true>(s, cfg, p);
-    case MM_DTYPE_I64: return vt_type<int64_t, true>(s, cfg, p);
-    case MM_DTYPE_U64: return vt_type<uint64_t, true>(s, cfg, p);
+    default: return vt_dispatch<WideIntTypes, true>(s, cfg, p);
   }
-  return kErrNotSupported;
 }
 }  // namespace mm
