@@ -1,13 +1,15 @@
 """CPU tests of the semiring closure (mm_closure_enqueue / _launch, mm_kernel_name_closure, closure_): the header, the binding
 and EXPORTS agree; bad arguments are refused before any device is touched, with their status codes; n = 0 and batch = 0 are
 no-ops; a valid call without a GPU fails with MM_ERR_NO_DEVICE; the kernel names follow n, the form and the block knob; no
-closure kernel uses scratch, AGPRs or a private segment; and the numpy restatement of the blocked algorithm that the GPU tests
-use as their oracle equals plain Floyd-Warshall on absorptive inputs."""
+closure kernel uses scratch, AGPRs or a private segment; the numpy restatement of the blocked algorithm that the GPU tests
+use as their oracle equals plain Floyd-Warshall on absorptive inputs; and the graphs those tests draw have a closure that a
+constant, or the input itself, could not pass for."""
 import concurrent.futures
 import ctypes
 import os
 import re
 import subprocess
+import zlib
 
 import numpy as np
 import pytest
@@ -236,3 +238,34 @@ def test_blocked_restatement_equals_floyd_warshall_on_absorptive_inputs(dtype, m
     assert sr.same_bits(got[gw < 0], d[gw < 0])
     # and the value-only form is the same
     assert sr.same_bits(cr.blocked(dtype, mp, rd, d, block)[0], want)
+
+
+@pytest.mark.parametrize("dtype,mp,rd", cr.CONFIGS)
+def test_closure_graphs_have_an_informative_closure(dtype, mp, rd):
+    """The criterion of _closure_ref.assert_informative on the restatement alone, for every configuration, at a size that
+    takes every step of the blocked algorithm (n = 293 = 2 * 128 + 37)."""
+    rng = np.random.default_rng(zlib.crc32(f"{dtype},{mp},{rd}".encode()))
+    d = cr.graphs(dtype, mp, rd, 293, rng)[0]
+    want, _ = cr.blocked(dtype, mp, rd, d, 128)
+    cr.assert_informative(dtype, mp, rd, d, want)
+
+
+@pytest.mark.parametrize("dtype,mp,rd", [("float", "Min", "Max"), ("half", "Max", "Min"), ("float", "Multiply", "Min"),
+                                         ("double", "Add", "Min"), ("uint8_t", "Add", "Min"), ("double", "Max", "Min")])
+def test_the_criterion_refuses_the_closure_of_a_dense_graph(dtype, mp, rd):
+    """What the criterion is for: dense random graphs close to (nearly) one value."""
+    d = cr.full_range(dtype, 293, np.random.default_rng(3))[0]
+    want, _ = cr.blocked(dtype, mp, rd, d, 128)
+    with pytest.raises(AssertionError):
+        cr.assert_informative(dtype, mp, rd, d, want)
+
+
+@pytest.mark.parametrize("dtype,mp,rd,full", [("float", "Multiply", "Min", False), ("float", "Multiply", "Max", False),
+                                              ("half", "Add", "Min", False), ("half", "Add", "Max", False),
+                                              ("int", "Add", "Min", True), ("uint8_t", "Multiply", "Max", True)])
+def test_rounded_and_wrapping_closures_depend_on_the_block_size(dtype, mp, rd, full):
+    """Why the GPU tests run every shipped block size: on rounded floating products and sums, and on wrapping integers
+    (the full-range set), the blocked algorithm at B = 256 and at B = 64 differ in bits."""
+    rng = np.random.default_rng(4)
+    d = (cr.full_range(dtype, 293, rng) if full else cr.graphs(dtype, mp, rd, 293, rng))[0]
+    assert not sr.same_bits(cr.blocked(dtype, mp, rd, d, 256)[0], cr.blocked(dtype, mp, rd, d, 64)[0])

@@ -15,8 +15,7 @@ import gemm_hls_amd as g
 pytestmark = pytest.mark.gpu
 
 GUARD = 64   # elements of guard pattern around D and W, and in the gaps between the graphs of a batch
-REDUCTIONS = ("Min", "Max")
-CONFIGS = [(d, mp, rd) for d in sr.DTYPES for mp in sr.OPS for rd in REDUCTIONS]   # 11 x 5 x 2 = 110
+CONFIGS = cr.CONFIGS   # 11 x 5 x 2 = 110
 
 
 @pytest.fixture
@@ -36,54 +35,57 @@ def _pattern(t, count):
     return (np.arange(count * np.dtype(t).itemsize) % 251 + 1).astype(np.uint8).view(t)
 
 
-def _operands(dtype, n, rng, batch=1):
-    """NaN-free graphs: floats in [1/16, 2] (no zero, so no inf * 0 when Max drives values to inf), integers over the type's
-    whole range (wrap-around is exact)."""
-    t = sr.NP_DTYPES[dtype]
-    shape = (batch, n, n)
-    if sr.is_float(dtype):
-        return (rng.integers(1, 33, size=shape) / 16).astype(t)
-    info = np.iinfo(t)
-    return rng.integers(info.min, info.max, size=shape, dtype=t, endpoint=True)
+def _operand_sets(dtype, mp, rd, n, rng, batch=1):
+    """[(graphs, informative)]: the sparse graphs whose closure keeps many values (_closure_ref.graphs), and for the integer
+    Add and Multiply maps the dense full-range set as well, whose wrap-around makes every bit depend on the pivot order."""
+    sets = [(cr.graphs(dtype, mp, rd, n, rng, batch), True)]
+    if cr.wrapping(dtype, mp):
+        sets.append((cr.full_range(dtype, n, rng, batch), False))
+    return sets
+
+
+def _bits(x):
+    return x.view(sr._UNSIGNED[x.dtype.itemsize])
 
 
 def closure_capi(cfg, d, witness, stride=None):
     """mm_closure_launch on (batch, n, n) host graphs, placed at `stride` elements apart inside guarded buffers; the guards
-    and the gaps between graphs must come back untouched.  Returns (D, W or None) as (batch, n, n)."""
+    and the gap after every graph must come back untouched.  Returns (D, W or None) as (batch, n, n)."""
     batch, n, _ = d.shape
     t = d.dtype
-    stride = n * n if stride is None else stride
-    gap = stride - n * n
+    nn = n * n
+    stride = nn if stride is None else stride
 
     def guarded(x, fill_t):
-        body = np.concatenate([np.concatenate([x[e].reshape(-1), _pattern(fill_t, gap)]) for e in range(batch)])
-        return np.concatenate([_pattern(fill_t, GUARD), body, _pattern(fill_t, GUARD)])
+        body = np.empty((batch, stride), dtype=fill_t)
+        body[:, :nn] = x.reshape(batch, nn)
+        body[:, nn:] = _pattern(fill_t, stride - nn)
+        return np.concatenate([_pattern(fill_t, GUARD), body.reshape(-1), _pattern(fill_t, GUARD)])
 
-    dbuf = guarded(d, t)
-    wbuf = guarded(np.full(d.shape, 12345, dtype=np.int32), np.int32) if witness else None
-    dd = _dev(dbuf)
-    dw = _dev(wbuf) if witness else None
+    dd = _dev(guarded(d, t))
+    dw = _dev(guarded(np.full(d.shape, 12345, dtype=np.int32), np.int32)) if witness else None
     rc = g.lib().mm_closure_launch(0, ctypes.byref(cfg), dd.data_ptr() + GUARD * t.itemsize,
                                    dw.data_ptr() + GUARD * 4 if witness else None, n, batch, stride, None)
     assert rc == 0, (rc, g.lib().mm_last_error().decode())
 
-    def unpack(buf, host, x_t):
+    def unpack(buf, x_t):
         out = buf.cpu().numpy().view(x_t)
-        assert out.tobytes()[:GUARD * np.dtype(x_t).itemsize] == host.tobytes()[:GUARD * np.dtype(x_t).itemsize]
-        assert out[-GUARD:].tobytes() == host[-GUARD:].tobytes(), "guard overwritten"
-        body = out[GUARD:-GUARD]
-        res = np.stack([body[e * stride:e * stride + n * n].reshape(n, n) for e in range(batch)])
-        for e in range(batch - 1):
-            assert body[e * stride + n * n:(e + 1) * stride].tobytes() == _pattern(x_t, gap).tobytes(), "gap overwritten"
-        return res
+        guard = _bits(_pattern(x_t, GUARD))
+        assert np.array_equal(_bits(out[:GUARD]), guard) and np.array_equal(_bits(out[-GUARD:]), guard), "guard overwritten"
+        body = out[GUARD:-GUARD].reshape(batch, stride)
+        gaps = _bits(body[:, nn:])
+        assert np.array_equal(gaps, np.broadcast_to(_bits(_pattern(x_t, stride - nn)), gaps.shape)), "gap overwritten"
+        return body[:, :nn].reshape(batch, n, n).copy()
 
-    return unpack(dd, dbuf, t), (unpack(dw, wbuf, np.int32) if witness else None)
+    return unpack(dd, t), (unpack(dw, np.int32) if witness else None)
 
 
-def _check_against_restatement(dtype, mp, rd, path, witness, d, got_d, got_w, b):
+def _check_against_restatement(dtype, mp, rd, path, witness, d, got_d, got_w, b, informative=False):
     auto = path == g.PATH_AUTO and not witness
     for e in range(d.shape[0]):
         want_d, want_w = cr.blocked(dtype, mp, rd, d[e], b, witness=witness, auto=auto)
+        if informative:
+            cr.assert_informative(dtype, mp, rd, d[e], want_d, f"graph {e}")
         if auto and sr.is_float(dtype):
             assert sr.same_values(got_d[e], want_d), (e, sr.first_difference(got_d[e], want_d, by_value=True))
         else:
@@ -99,16 +101,103 @@ def test_bit_exact_against_blocked_restatement(dtype, mp, rd, path, witness, blo
     """Every configuration, closure_block = 64: n below B (on chip), n = B, n = 2B + 36 (aligned, the tile kernels in
     step 3 under AUTO), and a batch of 3 graphs of n = 2B + 37 with guard patterns in the gaps between them."""
     block(64)
+    _run_shapes(dtype, mp, rd, path, witness, 64, ((37, 1), (64, 1), (164, 1), (2 * 64 + 37, 3)))
+
+
+def _run_shapes(dtype, mp, rd, path, witness, b, shapes):
+    """Every operand set of the configuration at every (n, batch) of `shapes`, batches at a padded stride, compared bit
+    for bit (witnesses included) with the restatement at block size b; every primary reference must be informative."""
     cfg = g.make_config(dtype, mp, rd, path)
     rng = np.random.default_rng(zlib.crc32(f"{dtype},{mp},{rd}".encode()))
-    for n in (37, 64, 164):
-        d = _operands(dtype, n, rng)
-        got_d, got_w = closure_capi(cfg, d, witness)
-        _check_against_restatement(dtype, mp, rd, path, witness, d, got_d, got_w, 64)
-    n = 2 * 64 + 37
-    d = _operands(dtype, n, rng, batch=3)
-    got_d, got_w = closure_capi(cfg, d, witness, stride=(n * n + 15) // 16 * 16 + 16)
-    _check_against_restatement(dtype, mp, rd, path, witness, d, got_d, got_w, 64)
+    for n, batch in shapes:
+        for d, informative in _operand_sets(dtype, mp, rd, n, rng, batch):
+            got_d, got_w = closure_capi(cfg, d, witness, stride=None if batch == 1 else (n * n + 15) // 16 * 16 + 16)
+            _check_against_restatement(dtype, mp, rd, path, witness, d, got_d, got_w, b, informative)
+
+
+# The shipped forms, which closure_block = 64 never reaches.  B = 256 (value-only, elements of at most 4 bytes):
+# closure_diag_kernel<..., 256, 8> and closure_panel_kernel<..., 256>; B = 128: closure_diag_kernel<..., 128, 4> on 1024
+# threads and panels with bt = 128.  Shapes, the smallest that reach every branch -- B = 256: n = 200 on chip, ragged inside
+# class 256; n = 456 = 256 + 200: panels with a ragged bt in class 256, a last panel tile 8 wide, a rank update with K = 200;
+# n = 293 = 256 + 37 as a batch of 2 at a padded stride: a class-64 diagonal, a rank update with K % 4 != 0 on the predicated
+# kernels.  B = 128: the same at n = 100, 228 = 128 + 100 and 293 = 2 * 128 + 37.
+SHIPPED_SHAPES = {256: ((200, 1), (456, 1), (293, 2)), 128: ((100, 1), (228, 1), (293, 2))}
+
+
+def _shipped_block(dtype, witness):
+    """The block size closure_block = -1 chooses."""
+    return 256 if not witness and np.dtype(sr.NP_DTYPES[dtype]).itemsize <= 4 else 128
+
+
+@pytest.mark.parametrize("witness", [False, True], ids=["values", "witness"])
+@pytest.mark.parametrize("dtype,mp,rd", CONFIGS)
+def test_bit_exact_at_the_shipped_block_sizes(dtype, mp, rd, witness, block):
+    """Every configuration under MM_PATH_AUTO with the default closure_block (the diagonal and panel kernels do not depend
+    on the path): outside absorptive inputs the blocked algorithm at B itself fixes every bit."""
+    block(-1)
+    b = _shipped_block(dtype, witness)
+    _run_shapes(dtype, mp, rd, g.PATH_AUTO, witness, b, SHIPPED_SHAPES[b])
+
+
+# one (map, reduce) per dtype for the forms the matrix above does not reach
+ONE_PER_DTYPE = [("float", "Multiply", "Min"), ("double", "Add", "Max"), ("half", "Add", "Min"), ("int8_t", "Add", "Min"),
+                 ("uint8_t", "Multiply", "Max"), ("int16_t", "Max", "Min"), ("uint16_t", "Add", "Max"),
+                 ("int", "Multiply", "Min"), ("unsigned", "Min", "Max"), ("long", "Add", "Min"),
+                 ("unsigned long", "Multiply", "Max")]
+assert [c[0] for c in ONE_PER_DTYPE] == sr.DTYPES
+
+
+@pytest.mark.parametrize("witness", [False, True], ids=["values", "witness"])
+@pytest.mark.parametrize("dtype,mp,rd", ONE_PER_DTYPE)
+def test_bit_exact_at_the_shipped_block_sizes_ordered(dtype, mp, rd, witness, block):
+    block(-1)
+    b = _shipped_block(dtype, witness)
+    _run_shapes(dtype, mp, rd, g.PATH_ORDERED, witness, b, SHIPPED_SHAPES[b])
+
+
+@pytest.mark.parametrize("dtype,mp,rd", [c for c in ONE_PER_DTYPE if _shipped_block(c[0], False) == 256])
+def test_bit_exact_value_only_at_block_128(dtype, mp, rd, block):
+    """closure_diag_kernel<..., 128, 4> and the 128 panels without witnesses on elements of at most 4 bytes: reached by the
+    knob alone."""
+    block(128)
+    _run_shapes(dtype, mp, rd, g.PATH_AUTO, False, 128, SHIPPED_SHAPES[128])
+
+
+def _check_batch_equals_each_graph_alone(dtype, mp, rd, base, batch, stride, b):
+    """A batch of base[e % p] (p prime, so no chunk boundary falls on a period) against every base graph run alone, which in
+    turn equals the restatement: bit for bit, witnesses included, guards and gaps intact."""
+    cfg = g.make_config(dtype, mp, rd)
+    alone = [closure_capi(cfg, base[e:e + 1], True) for e in range(len(base))]
+    alone_d, alone_w = np.concatenate([a[0] for a in alone]), np.concatenate([a[1] for a in alone])
+    _check_against_restatement(dtype, mp, rd, g.PATH_AUTO, True, base, alone_d, alone_w, b)
+    which = np.arange(batch) % len(base)
+    got_d, got_w = closure_capi(cfg, base[which], True, stride=stride)
+    bad = np.flatnonzero((_bits(got_d) != _bits(alone_d)[which]).any(axis=(1, 2)) | (got_w != alone_w[which]).any(axis=(1, 2)))
+    assert bad.size == 0, f"{bad.size} graphs differ from the same graph run alone, the first at {bad[:4]}"
+
+
+def test_second_workspace_chunk_equals_each_graph_alone(block):
+    """dispatch_closure's second chunk of graphs (e0 > 0: the offsets of D and W, the pitch of the witness memset).  double
+    with witnesses at closure_block = 64 and n = 65: a snapshot is 4160 elements, so the 256 MiB of workspace hold
+    2^28 / (2 * 4160 * 8) = 4033 graphs, and 4040 run as 4033 + 7."""
+    block(64)
+    n, batch = 65, 4040
+    assert g.kernel_name_closure(g.make_config("double", "Add", "Min"), n, batch, True) == "closure_blocked"
+    base = cr.graphs("double", "Add", "Min", n, np.random.default_rng(17), batch=7)
+    for e in range(len(base)):
+        cr.assert_informative("double", "Add", "Min", base[e], cr.blocked("double", "Add", "Min", base[e], 64)[0], f"graph {e}")
+    _check_batch_equals_each_graph_alone("double", "Add", "Min", base, batch, n * n + 31, 64)
+
+
+def test_second_onchip_chunk_equals_each_graph_alone():
+    """The on-chip form launches 2^20 graphs at a time: 2^20 + 5 graphs of 2 vertices run as two launches.  (4 entries
+    cannot meet assert_informative; the 13 graphs differ, and their closures differ from them.)"""
+    n, batch = 2, (1 << 20) + 5
+    rng = np.random.default_rng(19)
+    base = np.where(rng.random((13, n, n)) < 0.4, np.inf, rng.integers(1, 4097, size=(13, n, n)) / 64.0).astype(np.float32)
+    want = np.stack([cr.blocked("float", "Add", "Min", x, 128)[0] for x in base])
+    assert len({x.tobytes() for x in want}) == 13 and (want != base).any(axis=(1, 2)).sum() >= 6
+    _check_batch_equals_each_graph_alone("float", "Add", "Min", base, batch, n * n + 3, 128)
 
 
 def _torch_closure(d, dtype, mp, rd, witness=False, path=g.PATH_AUTO):
@@ -162,10 +251,11 @@ def test_longest_path_in_a_dag_equals_floyd_warshall():
 def test_widest_and_minimax_paths_equal_floyd_warshall(dtype, mp, rd):
     rng = np.random.default_rng(9)
     n = 300
-    d = _operands(dtype, n, rng)[0]
+    d = cr.graphs(dtype, mp, rd, n, rng)[0]
+    want, _ = cr.floyd_warshall(dtype, mp, rd, d)
+    cr.assert_informative(dtype, mp, rd, d, want)
     for witness in (False, True):
         got, w = _torch_closure(d, dtype, mp, rd, witness)
-        want, _ = cr.floyd_warshall(dtype, mp, rd, d)
         assert sr.same_bits(got, want), witness
 
 
