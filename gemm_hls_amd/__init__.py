@@ -29,7 +29,8 @@ EXPORTS = ["mm_init", "mm_alloc", "mm_free", "mm_copy_to_device", "mm_copy_to_ho
            "mm_gemm_batched_accumulate_enqueue", "mm_gemm_batched_accumulate_launch", "mm_gemm_argreduce_enqueue",
            "mm_gemm_argreduce_launch", "mm_kernel_name_argreduce", "mm_closure_enqueue", "mm_closure_launch",
            "mm_kernel_name_closure", "mm_gemm_logsumexp_enqueue", "mm_gemm_logsumexp_launch", "mm_kernel_name_logsumexp",
-           "mm_gemm_widen_enqueue", "mm_gemm_widen_launch", "mm_kernel_name_widen", "mm_widen_dtype"]
+           "mm_gemm_widen_enqueue", "mm_gemm_widen_launch", "mm_kernel_name_widen", "mm_widen_dtype",
+           "mm_gemm_nt_enqueue", "mm_gemm_nt_launch", "mm_kernel_name_nt"]
 
 
 class MMError(RuntimeError):
@@ -125,6 +126,10 @@ def lib():
         L.mm_kernel_name_widen.argtypes = [cfgp, u, u, u, u]
         L.mm_kernel_name_widen.restype = ctypes.c_char_p
         L.mm_widen_dtype.argtypes = [i]
+        L.mm_gemm_nt_enqueue.argtypes = [vp, cfgp, vp, vp, vp, u, u, u, u, sz, sz, sz, i]
+        L.mm_gemm_nt_launch.argtypes = [i, cfgp, vp, vp, vp, u, u, u, u, sz, sz, sz, i, ctypes.POINTER(ctypes.c_double)]
+        L.mm_kernel_name_nt.argtypes = [cfgp, u, u, u, u]
+        L.mm_kernel_name_nt.restype = ctypes.c_char_p
         _lib = L
     return _lib
 
@@ -180,6 +185,10 @@ def kernel_name_logsumexp(cfg, n, k, m, batch=1):
 
 def kernel_name_widen(cfg, n, k, m, batch=1):
     return lib().mm_kernel_name_widen(ctypes.byref(cfg), n, k, m, batch).decode()
+
+
+def kernel_name_nt(cfg, n, k, m, batch=1):
+    return lib().mm_kernel_name_nt(ctypes.byref(cfg), n, k, m, batch).decode()
 
 
 def widen_dtype(dtype):
@@ -495,6 +504,59 @@ def addmm_wide_(c, a, b, dtype="half", path=PATH_AUTO, transposed_a=False):
     batch, sc = _inplace_batch(c, n, m, batch)
     cfg = make_config(dtype, "Multiply", "Add", path, transposed_a)
     _enqueue(a.device, lib().mm_gemm_widen_enqueue, ctypes.byref(cfg), a.data_ptr(), b.data_ptr(), c.data_ptr(),
+             n, k, m, batch, sa, sb, sc, 1)
+    return c
+
+
+def _nt_shapes(what, a, b):
+    """(n, k, m, batch, stride_a, stride_b) of A x B^T operands: a (N, K), b (M, K), each 2-D, 3-D, or expanded with batch
+    stride 0."""
+    if a.dim() not in (2, 3) or b.dim() not in (2, 3):
+        raise MMError(f"{what} takes 2-D or 3-D operands")
+    n, k, m = a.shape[-2], a.shape[-1], b.shape[-2]
+    if b.shape[-1] != k:
+        raise MMError(f"inner dimensions differ: A {tuple(a.shape)}, B {tuple(b.shape)} (M, K)")
+    ba, sa = _batched_operand(a, "a", n, k)
+    bb, sb = _batched_operand(b, "b (M, K)", m, k)
+    batches = {x for x in (ba, bb) if x is not None and x != 1}
+    if len(batches) > 1:
+        raise MMError(f"batch sizes differ: {ba} and {bb}")
+    return n, k, m, (batches.pop() if batches else 1), sa, sb
+
+
+def matmul_nt(a, b, dtype="float", map_op="Multiply", reduce_op="Add", path=PATH_AUTO, out=None):
+    """C = A (map, reduce) B^T on torch's current stream (mm_gemm_nt_enqueue): C[i][j] = reduce_k map(a[i][k], b[j][k]), both
+    operands stored with k contiguous -- pairwise products between two row-stored sets, without b.mT.contiguous().
+    a: (N, K) or (B, N, K); b: (M, K) or (B, M, K); either may be expanded with batch stride 0, and a and b may be one
+    buffer.  The output is (N, M) when both operands are 2-D, else (B, N, M); out: a contiguous tensor of that shape.
+    Asynchronous, like any torch op."""
+    import torch
+    tdt = torch_dtype(dtype)
+    _device_operands("matmul_nt", tdt, a, b)
+    n, k, m, batch, sa, sb = _nt_shapes("matmul_nt", a, b)
+    shape = (n, m) if a.dim() == 2 and b.dim() == 2 else (batch, n, m)
+    if out is None:
+        out = torch.empty(shape, dtype=tdt, device=a.device)
+    else:
+        _check_out(out, "out", shape, tdt, a.device)
+    cfg = make_config(dtype, map_op, reduce_op, path)
+    _enqueue(a.device, lib().mm_gemm_nt_enqueue, ctypes.byref(cfg), a.data_ptr(), b.data_ptr(), out.data_ptr(),
+             n, k, m, batch, sa, sb, n * m, 0)
+    return out
+
+
+def addmm_nt_(c, a, b, dtype="float", map_op="Multiply", reduce_op="Add", path=PATH_AUTO):
+    """In place C <- C (+) (A (x) B^T) on torch's current stream (mm_gemm_nt_enqueue, accumulate): each output's reduction
+    starts at the value C holds, so two calls on the halves of K compose to one call on all of it.  a and b as for matmul_nt;
+    c: (N, M), or (B, N, M) as for baddbmm_, not overlapping a or b.  Returns c.  Asynchronous."""
+    tdt = torch_dtype(dtype)
+    _device_operands("addmm_nt_", tdt, c, a, b)
+    if c.dim() not in (2, 3):
+        raise MMError("addmm_nt_ takes 2-D or 3-D operands")
+    n, k, m, batch, sa, sb = _nt_shapes("addmm_nt_", a, b)
+    batch, sc = _inplace_batch(c, n, m, batch)
+    cfg = make_config(dtype, map_op, reduce_op, path)
+    _enqueue(a.device, lib().mm_gemm_nt_enqueue, ctypes.byref(cfg), a.data_ptr(), b.data_ptr(), c.data_ptr(),
              n, k, m, batch, sa, sb, sc, 1)
     return c
 

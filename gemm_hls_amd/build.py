@@ -37,6 +37,8 @@ EXTRA = {
     "mm_valu_tile_fp_exact.hip": ["-ffp-contract=off"],
     # the widening fallback: f32 sums of exact products in k order, reproducible on the host
     "mm_widen_ordered.hip": ["-ffp-contract=off"],
+    # the parity anchor of the A x B^T calls
+    "mm_ordered_nt.hip": ["-ffp-contract=off"],
 }
 
 HOST_CONFIGS = [  # (Data_t, MM_MAP_OP, MM_REDUCE_OP): BASELINE.json configs + an integer semiring

@@ -765,6 +765,145 @@ int dispatch_widen(hipStream_t s, const mm_config_t &cfg, const mm::Problem &p, 
   });
 }
 
+// ---- A x B^T (mm_gemm_nt_*): B stored M x K row-major -----------------------------------------------------------------------
+enum NtKernel { NT_NONE, NT_ORDERED, NT_ORDERED_WIDE, NT_VALU_TILE, NT_PREPASS };   // ORDERED_WIDE: ordered_nt's ACC = float half form
+
+bool nt_serves(const mm_config_t &cfg) { return cfg.path != MM_PATH_SPLIT && cfg.layout_a != MM_A_TRANSPOSED; }
+
+// half (Multiply, Add) under MM_PATH_AUTO keeps ONE contract on every shape and alignment: exact products, f32 sums, one rounding
+bool nt_half_wide(const mm_config_t &cfg) {
+  return cfg.path == MM_PATH_AUTO && cfg.dtype == MM_DTYPE_F16 && cfg.map_op == MM_OP_MULTIPLY && cfg.reduce_op == MM_OP_ADD &&
+         mm::tuning(mm::TUNE_HALF_CONTRACT) != 1;
+}
+
+// The kernel by configuration, shape and path alone (mm_kernel_name_nt): the family the narrow batched call would run on
+// (n, k, m, batch), mapped.  A matrix-core family (its batched resolver names a kernel) with K and M multiples of the 16-byte
+// chunk: the transposition pre-pass and that kernel; the k-ordered contract (MM_PATH_ORDERED, half_contract = 1): ordered_nt;
+// half (Multiply, Add) otherwise: ordered_nt accumulating in f32; everything else: valu_tile_nt where it serves -- by ITS rule,
+// which asks nothing of M -- else ordered_nt.  Alignment and a full workspace pool may still demote at launch.
+NtKernel nt_kernel_for(const mm_config_t &cfg, const mm::Problem &p) {
+  if (!nt_serves(cfg)) return NT_NONE;
+  const bool mul_add = cfg.map_op == MM_OP_MULTIPLY && cfg.reduce_op == MM_OP_ADD;
+  // the k-ordered contract, as choose() reads it: asked for by path, or by half_contract = 1 for half (Multiply, Add)
+  if (cfg.path == MM_PATH_ORDERED || (mul_add && cfg.dtype == MM_DTYPE_F16 && mm::tuning(mm::TUNE_HALF_CONTRACT) == 1)) return NT_ORDERED;
+  const auto valu_or_ordered = [&] {
+    return nt_half_wide(cfg) ? NT_ORDERED_WIDE : mm::valu_tile_nt_serves(cfg, p) ? NT_VALU_TILE : NT_ORDERED;
+  };
+  switch (choose_batched(cfg, p)) {
+    case FAM_MFMA_F32: case FAM_MFMA_F64: case FAM_MFMA_F16: case FAM_MFMA_I8: {
+      const unsigned epc = (unsigned)(16 / mm_dtype_size(cfg.dtype));
+      return p.k % epc == 0 && p.m % epc == 0 ? NT_PREPASS : valu_or_ordered();
+    }
+    case FAM_NONE: case FAM_F32_SPLIT: return NT_NONE;
+    // FAM_HALF_WIDE; FAM_VALU_TILE; and FAM_ORDERED, which under MM_PATH_AUTO only means that the row-major kernel's K % 4 /
+    // M % 4 rule, or an operator it does not hold, sent the narrow call there
+    default: return valu_or_ordered();
+  }
+}
+
+// What a launch that cannot run its fast kernel (misaligned operands, no workspace) runs instead: the same contract
+NtKernel nt_demoted(const mm_config_t &cfg) { return nt_half_wide(cfg) ? NT_ORDERED_WIDE : NT_ORDERED; }
+
+// All argument checks of an A x B^T call, before any device is touched.  *ker = NT_NONE: nothing to launch (an empty batch,
+// or K = 0 when accumulating).  A and Bt may be the same buffer.
+int check_nt(const mm_config_t *cfg, const mm::Problem &p, NtKernel *ker) {
+  *ker = NT_NONE;
+  if (!valid_cfg(cfg)) return fail(MM_ERR_BAD_ARGUMENT, "invalid mm_config_t");
+  if (!nt_serves(*cfg))
+    return fail(MM_ERR_UNSUPPORTED, "the A x B^T calls serve a row-major A under MM_PATH_AUTO or MM_PATH_ORDERED (got path %d, "
+                "layout_a %d)", (int)cfg->path, (int)cfg->layout_a);
+  if (p.k == 0 && !p.seed) return fail(MM_ERR_BAD_ARGUMENT, "size_k must be positive");
+  if (empty_batch(p)) return MM_OK;
+  if (!p.c || (p.k && (!p.a || !p.b))) return fail(MM_ERR_BAD_ARGUMENT, "null matrix pointer");   // (K = 0: A, B unread)
+  if (int rc = check_stride_c(p)) return rc;
+  const size_t es = mm_dtype_size(cfg->dtype);
+  if (outputs_overlap(p, es))   // (B's extent is M * K in either layout)
+    return fail(MM_ERR_BAD_ARGUMENT, "c overlaps a or b (bases %p, %p, %p)", p.a, p.b, p.c);
+  if (p.k == 0) return MM_OK;   // accumulating over no k: C keeps its value
+  *ker = nt_kernel_for(*cfg, p);
+  // valu_tile_nt moves 16 bytes per lane of A and Bt (C goes element by element); the pre-pass and the matrix-core kernels
+  // 16 bytes of C as well: else ordered_nt, any element-aligned pointer
+  const size_t in_strides = p.batch > 1 ? (p.stride_a | p.stride_b) * es : 0;
+  const bool in_aligned = ((((uintptr_t)p.a | (uintptr_t)p.b) | in_strides) & 15u) == 0;
+  if ((*ker == NT_VALU_TILE && !in_aligned) || (*ker == NT_PREPASS && !batch_aligned16(p, es))) *ker = nt_demoted(*cfg);
+  return MM_OK;
+}
+
+// `ker` over the batch in launches of at most batch_chunk() elements
+int nt_chunks(hipStream_t s, const mm_config_t &cfg, const mm::Problem &p, NtKernel ker) {
+  return for_each_chunk(p, mm_dtype_size(cfg.dtype), batch_chunk(p), [&](const mm::Problem &q, unsigned) {
+    int e;
+    switch (ker) {
+      case NT_VALU_TILE:
+        e = mm::launch_valu_tile_nt(s, cfg, q);
+        if (e == mm::kErrNotSupported) e = mm::launch_ordered_nt(s, cfg, q);   // still the GPU
+        break;
+      case NT_ORDERED_WIDE: e = mm::launch_half_wide_nt(s, q); break;
+      default: e = mm::launch_ordered_nt(s, cfg, q); break;
+    }
+    return launch_status(e, cfg, "A x B^T ", "A x B^T kernel launch");
+  });
+}
+
+// Transposed copies of one chunk of the batch stay near this; an element that alone needs more runs alone.
+constexpr size_t kNtWorkspaceCap = 256ull << 20;
+
+// "nt_prepass", never synchronising the host: B = Bt^T (K x M per element) into stream-ordered workspace, then the batched
+// matrix-core kernel on it -- resolved once on the whole batch, so the bits are those of mm_gemm_batched_* /
+// mm_gemm_batched_accumulate_* on a materialised transpose, whatever the chunking.  A broadcast Bt is transposed once.
+// A full pool is no error: ordered_nt serves the call without extra memory, same contract.
+int dispatch_nt_prepass(hipStream_t s, const mm_config_t &cfg, const mm::Problem &p) {
+  const size_t es = mm_dtype_size(cfg.dtype), km = (size_t)p.k * p.m;   // (km * es is a multiple of 16: K and M are chunk multiples)
+  const bool b_shared = p.batch == 1 || p.stride_b == 0;
+  const unsigned chunk = b_shared ? p.batch : (unsigned)std::min<size_t>(p.batch, std::max<size_t>(1, kNtWorkspaceCap / (km * es)));
+  mm::Problem whole = p;   // the row-major problem the kernels see
+  whole.b_transposed = false;
+  whole.stride_b = b_shared ? 0 : km;
+  const Family fam = choose_batched(cfg, whole);
+  const int kernel = fam == FAM_MFMA_F32 ? mm::mfma_f32_batched_resolve(whole, f32_variant())
+                   : fam == FAM_MFMA_F64 ? mm::mfma_f64_batched_resolve(whole)
+                   : fam == FAM_MFMA_F16 ? mm::mfma_f16_batched_resolve(whole)
+                   : fam == FAM_MFMA_I8 ? mm::mfma_i8_batched_resolve(whole) : -1;
+  if (kernel < 0) return nt_chunks(s, cfg, p, nt_demoted(cfg));   // (a knob changed between the check and here)
+  int dev = 0;
+  MM_HIP(hipGetDevice(&dev));
+  hipMemPool_t pool = nullptr;
+  if (int e = mm::workspace_pool(dev, &pool)) return hip_fail((hipError_t)e, "workspace pool");
+  void *ws = nullptr;
+  if (hipMallocFromPoolAsync(&ws, (b_shared ? 1 : chunk) * km * es, pool, s) != hipSuccess) {
+    (void)hipGetLastError();
+    return nt_chunks(s, cfg, p, nt_demoted(cfg));
+  }
+  int rc = MM_OK;
+  for (unsigned e0 = 0; e0 < p.batch && rc == MM_OK; e0 += chunk) {
+    const mm::Problem src = batch_slice(p, e0, std::min(chunk, p.batch - e0), es);   // this chunk's elements
+    if (e0 == 0 || !b_shared)
+      rc = launch_status(mm::launch_transpose_batched(s, src.b, ws, p.m, p.k, (unsigned)es, b_shared ? 1 : src.batch, p.stride_b, km),
+                         cfg, "A x B^T ", "transposition pre-pass launch");
+    if (rc) break;
+    mm::Problem g = src;
+    g.b = ws;
+    g.b_transposed = false;
+    g.stride_b = whole.stride_b;
+    rc = for_each_chunk(g, es, batch_chunk(g), [&](const mm::Problem &q, unsigned) {
+      const int e = fam == FAM_MFMA_F32 ? mm::launch_mfma_f32_batched(s, q, kernel)
+                  : fam == FAM_MFMA_F64 ? mm::launch_mfma_f64_batched(s, q, kernel)
+                  : fam == FAM_MFMA_F16 ? mm::launch_mfma_f16_batched(s, q, kernel) : mm::launch_mfma_i8_batched(s, q, kernel);
+      return launch_status(e, cfg, "A x B^T ", "A x B^T product launch");
+    });
+  }
+  const hipError_t f = hipFreeAsync(ws, s);
+  if (rc == MM_OK && f != hipSuccess) rc = hip_fail(f, "hipFreeAsync (A x B^T workspace)");
+  return rc;
+}
+
+int dispatch_nt(hipStream_t s, const mm_config_t &cfg, const mm::Problem &p, NtKernel ker) {
+  (void)hipGetLastError();   // a stale error of the application's own calls must not be reported as this launch's
+  mm::Problem q = p;
+  if (q.batch == 1) q.stride_a = q.stride_b = q.stride_c = 0;
+  return ker == NT_PREPASS ? dispatch_nt_prepass(s, cfg, q) : nt_chunks(s, cfg, q, ker);
+}
+
 // The kernel of a family that is one kernel whatever the shape (the matrix-core families name theirs by shape)
 const char *family_name(Family f) {
   switch (f) {
@@ -858,6 +997,13 @@ int run_widen(const Target &t, const mm_config_t *cfg, const mm::Problem &p) {
   WidenKernel ker;
   if (int rc = check_widen(cfg, p, &ker)) return rc;
   return run(t, ker == WD_NONE, [&](hipStream_t s) { return dispatch_widen(s, *cfg, p, ker); });
+}
+
+int run_nt(const Target &t, const mm_config_t *cfg, mm::Problem p) {
+  p.b_transposed = true;
+  NtKernel ker;
+  if (int rc = check_nt(cfg, p, &ker)) return rc;
+  return run(t, ker == NT_NONE, [&](hipStream_t s) { return dispatch_nt(s, *cfg, p, ker); });
 }
 
 int run_closure(const Target &t, const mm_config_t *cfg, void *d, int *witness, unsigned n, unsigned batch, size_t stride_d) {
@@ -1136,6 +1282,18 @@ int mm_gemm_widen_launch(int device, const mm_config_t *cfg, const void *a, cons
                          double *elapsed_seconds) {
   return run_widen(timed_on(device, elapsed_seconds), cfg,
                    batched_problem(cfg, a, b, c, n, k, m, batch, stride_a, stride_b, stride_c, accumulate != 0));
+}
+
+int mm_gemm_nt_enqueue(void *hip_stream, const mm_config_t *cfg, const void *a, const void *bt, void *c, unsigned n, unsigned k,
+                       unsigned m, unsigned batch, size_t stride_a, size_t stride_b, size_t stride_c, int accumulate) {
+  return run_nt(on_stream(hip_stream), cfg, batched_problem(cfg, a, bt, c, n, k, m, batch, stride_a, stride_b, stride_c, accumulate != 0));
+}
+
+int mm_gemm_nt_launch(int device, const mm_config_t *cfg, const void *a, const void *bt, void *c, unsigned n, unsigned k,
+                      unsigned m, unsigned batch, size_t stride_a, size_t stride_b, size_t stride_c, int accumulate,
+                      double *elapsed_seconds) {
+  return run_nt(timed_on(device, elapsed_seconds), cfg,
+                batched_problem(cfg, a, bt, c, n, k, m, batch, stride_a, stride_b, stride_c, accumulate != 0));
 }
 
 int mm_closure_enqueue(void *hip_stream, const mm_config_t *cfg, void *d, int *witness, unsigned n, unsigned batch,
@@ -1494,6 +1652,18 @@ const char *mm_kernel_name_widen(const mm_config_t *cfg, unsigned n, unsigned k,
   const mm::Problem p = batched_problem(cfg, nullptr, nullptr, nullptr, n, k, m, batch ? batch : 1, 0, 0, 0);
   const char *wide = widen_mfma_name(*cfg, p);   // the choice check_widen makes, before alignment
   return wide ? wide : "widen_ordered";
+}
+
+const char *mm_kernel_name_nt(const mm_config_t *cfg, unsigned n, unsigned k, unsigned m, unsigned batch) {
+  if (!valid_cfg(cfg)) return "invalid";
+  if (!nt_serves(*cfg)) return "unsupported";
+  const mm::Problem p = batched_problem(cfg, nullptr, nullptr, nullptr, n, k, m, batch ? batch : 1, 0, 0, 0);
+  switch (nt_kernel_for(*cfg, p)) {   // the choice check_nt makes, before alignment
+    case NT_PREPASS: return "nt_prepass";
+    case NT_VALU_TILE: return "valu_tile_nt";
+    case NT_NONE: return "unsupported";
+    default: return "ordered_nt";
+  }
 }
 
 const char *mm_kernel_name_closure(const mm_config_t *cfg, unsigned n, unsigned batch, int with_witness) {

@@ -96,6 +96,9 @@ struct Problem {
   // accumulate (mm_gemm_*accumulate_*): C <- C (+) (A (x) B), each output's reduction starts at the value C holds instead
   // of identity().  Only the *_batched launchers read it (they then run the kernels' Form::Seeded instantiations).
   bool seed = false;
+  // A x B^T (mm_gemm_nt_*): b is M x K row-major per element (Bt[j][k]; stride_b counts its elements).  Only the *_nt
+  // launchers are handed such a problem; nothing else reads this.
+  bool b_transposed = false;
 };
 
 // Batched launches: `p.batch` copies of the tile grid in ONE launch; the kernel derives the element from the workgroup id
@@ -130,6 +133,17 @@ int launch_mfma_f16_wide(hipStream_t s, const Problem &p, int resolved);
 // "widen_ordered" (mm_widen_ordered.hip): k ascending, one accumulator in the wide type, fully predicated; dtype is the operands'.
 // blocked (half only): the terms summed in blocks of k instead -- MM_PATH_AUTO's bound where a misaligned launch was demoted
 int launch_widen_ordered(hipStream_t s, mm_dtype_t dtype, const Problem &p, bool blocked);
+
+// A x B^T (mm_gemm_nt_*): the p.batch elements of p, p.b M x K row-major per element, p.seed accumulating into C.
+// "ordered_nt" (mm_ordered_nt.hip): Naive on Bt[j][k], k ascending, one accumulator, unfused; any shape, any element-aligned
+// pointer.  launch_half_wide_nt: its half (Multiply, Add) instantiation with an f32 accumulator (one rounding on store).
+int launch_ordered_nt(hipStream_t s, const mm_config_t &cfg, const Problem &p);
+int launch_half_wide_nt(hipStream_t s, const Problem &p);
+// "valu_tile_nt" (mm_valu_tile_nt.inc): serves by configuration and shape (maps {Multiply, Add, Min, Max}, reductions {Add, Min,
+// Max}, K >= 64 bytes, K a multiple of 16 bytes, 128 rows of K below 4 GiB); the launch also needs every element's A and
+// Bt 16-byte aligned.  kErrNotSupported where it does not serve.
+bool valu_tile_nt_serves(const mm_config_t &cfg, const Problem &p);
+int launch_valu_tile_nt(hipStream_t s, const mm_config_t &cfg, const Problem &p);
 
 // Launchers (one translation unit each).  Return hipError_t as int; hipErrorNotSupported (801)
 // means "this family does not serve this (config, shape)".
@@ -229,6 +243,9 @@ int mfma_f32_auto_variant(const Problem &p);
 int mfma_f16_tile(const Problem &p);  // 0: 256x256, 4: 128x256  // shape-adaptive pick (variant < 0)
 // dst[n][k] = src[k][n] for 1- and 2-byte elements (mm_transpose.hip); N and K multiples of 16 bytes' worth of elements
 int launch_transpose_kxn(hipStream_t s, const void *src, void *dst, unsigned K, unsigned N, unsigned elem_size);
+// The same for 1-, 2-, 4- and 8-byte elements over `count` matrices at src + e * stride_src, dst + e * stride_dst (elements)
+int launch_transpose_batched(hipStream_t s, const void *src, void *dst, unsigned K, unsigned N, unsigned elem_size, unsigned count,
+                             size_t stride_src, size_t stride_dst);
 bool transposes_first_small(const Problem &p, unsigned elem_size);   // K x N A of half / int8: pre-pass + the row-major default
 // That pre-pass: A into N x K pool workspace, row_major() on the copy, free.  A full pool is no error: in_place() serves the K x N A.
 typedef int (*ProblemLauncher)(hipStream_t s, const Problem &p);

@@ -359,6 +359,47 @@ const char *mm_kernel_name_widen(const mm_config_t *cfg, unsigned size_n, unsign
 /* C's mm_dtype_t for operands of `dtype`: MM_DTYPE_F32 for half, MM_DTYPE_I32 for int8_t; -1 for every other type. */
 int mm_widen_dtype(mm_dtype_t dtype);
 
+/* A x B^T: C[e,i,j] = reduce_k map(A[e,i,k], Bt[e,j,k]) -- B stored M x K row-major, k contiguous in BOTH operands: pairwise
+ * products between two row-stored point or state sets (min-plus A (x) A^T, Gram matrices, Viterbi steps with a "to-state
+ * major" transition matrix) and the dA = G B^T half of a backward pass (dB = A^T G is MM_A_TRANSPOSED's), without the
+ * K x M copy and the extra pass of a transposition by the caller.  bt_dev: M x K row-major per element; stride_b counts ITS
+ * elements, 0 = broadcast.  accumulate != 0: C <- C (+) (A (x) Bt^T), each chain starting at the value C holds.
+ * Kernels (mm_kernel_name_nt), from the family mm_gemm_batched_* would run on (n, k, m, batch) -- for batch = 1 too:
+ *   "nt_prepass"    (Multiply, Add) on the matrix cores (float, double, half, int8_t / uint8_t) where the narrow batched
+ *                   resolver names a kernel and K, M are multiples of 16 bytes' worth of elements: Bt is transposed into the
+ *                   library's stream-ordered workspace (about 256 MiB per chunk of the batch, a broadcast Bt once) and that
+ *                   kernel runs on the copy, resolved once on the whole batch: bit for bit what mm_gemm_batched_* /
+ *                   mm_gemm_batched_accumulate_* returns on a materialised transpose, with that family's contract.
+ *   "valu_tile_nt"  every other configuration under MM_PATH_AUTO with map in {Multiply, Add, Min, Max} and reduce in {Add, Min,
+ *                   Max}, where K >= 64 bytes of elements, K is a multiple of 16 bytes of elements and 128 rows of K stay
+ *                   below 4 GiB; nothing is asked of N or M.  MM_PATH_AUTO's contract as "valu_tile" keeps it: k ascending on
+ *                   one accumulator, so integer and Min / Max results are Naive's bits; floating Min / Max are minNum /
+ *                   maxNum (a NaN operand is dropped, +0 / -0 ties unspecified); floating (x, Add) may fuse.
+ *   "ordered_nt"    MM_PATH_ORDERED, half_contract = 1, and every shape or operator the rows above do not take: Naive on
+ *                   Bt[j][k] -- k ascending, one accumulator, unfused -- bit-identical to the reference's Naive on the transposed
+ *                   operand for all 275 configurations; any shape, any element-aligned pointer or stride.  ONE exception, as
+ *                   in the row-major calls: half (Multiply, Add) under MM_PATH_AUTO (half_contract unset) accumulates in f32
+ *                   and rounds once on store -- the matrix cores' contract, kept on every shape.
+ * The name is decided by configuration, shape and path.  A launch whose A or Bt ("nt_prepass": or C) -- base or element stride --
+ * is not 16-byte aligned runs ordered_nt instead, silently and under the same contract, as does "nt_prepass" when the pool
+ * cannot give the workspace.
+ * Arguments as for mm_gemm_widen_*: strides count elements, stride_c >= N * M when batch > 1.  Refused before any device is
+ * touched: MM_PATH_SPLIT and MM_A_TRANSPOSED (MM_ERR_UNSUPPORTED: A^T B^T is not served); a null pointer, C's span overlapping
+ * A's or Bt's (MM_ERR_BAD_ARGUMENT).  A and Bt may be the same buffer (A (x) A^T).  batch, N or M 0: MM_OK; K = 0:
+ * MM_ERR_BAD_ARGUMENT in the plain form, MM_OK (C unchanged) when accumulating.  The batch is launched in chunks (knob
+ * "batch_chunk"); an element's bits do not depend on the chunk it falls in.
+ * _enqueue: asynchronous on a hipStream_t of the CURRENT device, never synchronises the host; _launch: blocking,
+ * *elapsed_seconds (may be NULL) timed with HIP events. */
+int mm_gemm_nt_enqueue(void *hip_stream, const mm_config_t *cfg, const void *a_dev, const void *bt_dev, void *c_dev,
+                       unsigned size_n, unsigned size_k, unsigned size_m, unsigned batch,
+                       size_t stride_a, size_t stride_b, size_t stride_c, int accumulate);
+int mm_gemm_nt_launch(int device, const mm_config_t *cfg, const void *a_dev, const void *bt_dev, void *c_dev,
+                      unsigned size_n, unsigned size_k, unsigned size_m, unsigned batch,
+                      size_t stride_a, size_t stride_b, size_t stride_c, int accumulate, double *elapsed_seconds);
+/* "nt_prepass", "valu_tile_nt" or "ordered_nt"; "unsupported" for a configuration the calls refuse with MM_ERR_UNSUPPORTED;
+ * "invalid" for a bad configuration.  Static string, pure arithmetic. */
+const char *mm_kernel_name_nt(const mm_config_t *cfg, unsigned size_n, unsigned size_k, unsigned size_m, unsigned batch);
+
 /* Closure: all-pairs shortest / widest / longest paths and transitive closure -- blocked Floyd-Warshall, in place.
  * D is n x n, row-major; graph e of the batch starts at d_dev + e * stride_d (elements; stride_d >= n * n when batch > 1).
  * The call runs the recurrence D[i][j] <- D[i][j] (+) D[i][v] (x) D[v][j] over every v, with Reduce = cfg->reduce_op in
