@@ -30,7 +30,9 @@ EXPORTS = ["mm_init", "mm_alloc", "mm_free", "mm_copy_to_device", "mm_copy_to_ho
            "mm_gemm_argreduce_launch", "mm_kernel_name_argreduce", "mm_closure_enqueue", "mm_closure_launch",
            "mm_kernel_name_closure", "mm_gemm_logsumexp_enqueue", "mm_gemm_logsumexp_launch", "mm_kernel_name_logsumexp",
            "mm_gemm_widen_enqueue", "mm_gemm_widen_launch", "mm_kernel_name_widen", "mm_widen_dtype",
-           "mm_gemm_nt_enqueue", "mm_gemm_nt_launch", "mm_kernel_name_nt"]
+           "mm_gemm_nt_enqueue", "mm_gemm_nt_launch", "mm_kernel_name_nt", "mm_gemm_argreduce_nt_enqueue",
+           "mm_gemm_argreduce_nt_launch", "mm_kernel_name_argreduce_nt", "mm_gemm_logsumexp_nt_enqueue",
+           "mm_gemm_logsumexp_nt_launch", "mm_kernel_name_logsumexp_nt"]
 
 
 class MMError(RuntimeError):
@@ -130,6 +132,14 @@ def lib():
         L.mm_gemm_nt_launch.argtypes = [i, cfgp, vp, vp, vp, u, u, u, u, sz, sz, sz, i, ctypes.POINTER(ctypes.c_double)]
         L.mm_kernel_name_nt.argtypes = [cfgp, u, u, u, u]
         L.mm_kernel_name_nt.restype = ctypes.c_char_p
+        L.mm_gemm_argreduce_nt_enqueue.argtypes = L.mm_gemm_argreduce_enqueue.argtypes
+        L.mm_gemm_argreduce_nt_launch.argtypes = L.mm_gemm_argreduce_launch.argtypes
+        L.mm_kernel_name_argreduce_nt.argtypes = [cfgp, u, u, u, u]
+        L.mm_kernel_name_argreduce_nt.restype = ctypes.c_char_p
+        L.mm_gemm_logsumexp_nt_enqueue.argtypes = L.mm_gemm_logsumexp_enqueue.argtypes
+        L.mm_gemm_logsumexp_nt_launch.argtypes = L.mm_gemm_logsumexp_launch.argtypes
+        L.mm_kernel_name_logsumexp_nt.argtypes = [cfgp, u, u, u, u]
+        L.mm_kernel_name_logsumexp_nt.restype = ctypes.c_char_p
         _lib = L
     return _lib
 
@@ -189,6 +199,14 @@ def kernel_name_widen(cfg, n, k, m, batch=1):
 
 def kernel_name_nt(cfg, n, k, m, batch=1):
     return lib().mm_kernel_name_nt(ctypes.byref(cfg), n, k, m, batch).decode()
+
+
+def kernel_name_argreduce_nt(cfg, n, k, m, batch=1):
+    return lib().mm_kernel_name_argreduce_nt(ctypes.byref(cfg), n, k, m, batch).decode()
+
+
+def kernel_name_logsumexp_nt(cfg, n, k, m, batch=1):
+    return lib().mm_kernel_name_logsumexp_nt(ctypes.byref(cfg), n, k, m, batch).decode()
 
 
 def widen_dtype(dtype):
@@ -557,6 +575,88 @@ def addmm_nt_(c, a, b, dtype="float", map_op="Multiply", reduce_op="Add", path=P
     batch, sc = _inplace_batch(c, n, m, batch)
     cfg = make_config(dtype, map_op, reduce_op, path)
     _enqueue(a.device, lib().mm_gemm_nt_enqueue, ctypes.byref(cfg), a.data_ptr(), b.data_ptr(), c.data_ptr(),
+             n, k, m, batch, sa, sb, sc, 1)
+    return c
+
+
+def matmul_argreduce_nt(a, b, dtype="float", map_op="Add", reduce_op="Min", path=PATH_AUTO, index_base=0, out=None,
+                        out_index=None):
+    """(values, indices) of a Min- or Max-reduced A x B^T product on torch's current stream (mm_gemm_argreduce_nt_enqueue):
+    matmul_argreduce on b.mT, bit for bit, without b.mT.contiguous() -- a Viterbi step and its backpointers from a to-state
+    major transition matrix.  a and b as for matmul_nt: (N, K) or (B, N, K) and (M, K) or (B, M, K), either expanded with
+    batch stride 0, possibly one buffer.  The outputs are (N, M) when both operands are 2-D, else (B, N, M).  out /
+    out_index: contiguous tensors of that shape (values' dtype, torch.int32).  Asynchronous."""
+    import torch
+    tdt = torch_dtype(dtype)
+    _device_operands("matmul_argreduce_nt", tdt, a, b)
+    n, k, m, batch, sa, sb = _nt_shapes("matmul_argreduce_nt", a, b)
+    shape = (n, m) if a.dim() == 2 and b.dim() == 2 else (batch, n, m)
+    if out is None:
+        out = torch.empty(shape, dtype=tdt, device=a.device)
+    if out_index is None:
+        out_index = torch.empty(shape, dtype=torch.int32, device=a.device)
+    _check_out(out, "out", shape, tdt, a.device)
+    _check_out(out_index, "out_index", shape, torch.int32, a.device)
+    cfg = make_config(dtype, map_op, reduce_op, path)
+    _enqueue(a.device, lib().mm_gemm_argreduce_nt_enqueue, ctypes.byref(cfg), a.data_ptr(), b.data_ptr(), out.data_ptr(),
+             out_index.data_ptr(), n, k, m, batch, sa, sb, n * m, int(index_base), 0)
+    return out, out_index
+
+
+def addmm_argreduce_nt_(c, c_index, a, b, dtype="float", map_op="Add", reduce_op="Min", path=PATH_AUTO, index_base=0):
+    """In place (C, I) <- the A x B^T argreduce seeded with (C, I) on torch's current stream (mm_gemm_argreduce_nt_enqueue,
+    accumulate): addmm_argreduce_ on b.mT.  a and b as for matmul_nt; c: (N, M), or (B, N, M) as for baddbmm_; c_index:
+    torch.int32 with c's shape and strides.  Returns (c, c_index).  Asynchronous, like any torch op."""
+    import torch
+    tdt = torch_dtype(dtype)
+    _device_operands("addmm_argreduce_nt_", tdt, c, a, b)
+    if not c_index.is_cuda or c_index.device != c.device or c_index.dtype != torch.int32:
+        raise MMError(f"c_index must be a torch.int32 tensor on {c.device}; got {c_index.dtype} on {c_index.device}")
+    if c.dim() not in (2, 3):
+        raise MMError("addmm_argreduce_nt_ takes 2-D or 3-D operands")
+    if tuple(c_index.shape) != tuple(c.shape) or c_index.stride() != c.stride():
+        raise MMError(f"c_index must have c's shape and strides: {tuple(c.shape)} {c.stride()}, got "
+                      f"{tuple(c_index.shape)} {c_index.stride()}")
+    n, k, m, batch, sa, sb = _nt_shapes("addmm_argreduce_nt_", a, b)
+    batch, sc = _inplace_batch(c, n, m, batch)
+    cfg = make_config(dtype, map_op, reduce_op, path)
+    _enqueue(a.device, lib().mm_gemm_argreduce_nt_enqueue, ctypes.byref(cfg), a.data_ptr(), b.data_ptr(), c.data_ptr(),
+             c_index.data_ptr(), n, k, m, batch, sa, sb, sc, int(index_base), 1)
+    return c, c_index
+
+
+def matmul_logsumexp_nt(a, b, dtype="float", reduce_op="Max", path=PATH_AUTO, out=None):
+    """Log-semiring A x B^T product on torch's current stream (mm_gemm_logsumexp_nt_enqueue): C = log sum_k exp(a[i,k] +
+    b[j,k]) for reduce_op="Max" (Min: the soft-min) -- matmul_logsumexp on b.mT, the forward step over a to-state major
+    transition matrix.  a and b as for matmul_nt; the output is (N, M) when both operands are 2-D, else (B, N, M); out: a
+    contiguous tensor of that shape.  Asynchronous."""
+    import torch
+    tdt = torch_dtype(dtype)
+    _device_operands("matmul_logsumexp_nt", tdt, a, b)
+    n, k, m, batch, sa, sb = _nt_shapes("matmul_logsumexp_nt", a, b)
+    shape = (n, m) if a.dim() == 2 and b.dim() == 2 else (batch, n, m)
+    if out is None:
+        out = torch.empty(shape, dtype=tdt, device=a.device)
+    else:
+        _check_out(out, "out", shape, tdt, a.device)
+    cfg = make_config(dtype, "Add", reduce_op, path)
+    _enqueue(a.device, lib().mm_gemm_logsumexp_nt_enqueue, ctypes.byref(cfg), a.data_ptr(), b.data_ptr(), out.data_ptr(),
+             n, k, m, batch, sa, sb, n * m, 0)
+    return out
+
+
+def addmm_logsumexp_nt_(c, a, b, dtype="float", reduce_op="Max", path=PATH_AUTO):
+    """In place C <- log(exp(C) + sum_k exp(a[i,k] + b[j,k])) (Min: the soft-min) on torch's current stream
+    (mm_gemm_logsumexp_nt_enqueue, accumulate): addmm_logsumexp_ on b.mT.  a and b as for matmul_nt; c: (N, M), or
+    (B, N, M) as for baddbmm_.  Returns c.  Asynchronous."""
+    tdt = torch_dtype(dtype)
+    _device_operands("addmm_logsumexp_nt_", tdt, c, a, b)
+    if c.dim() not in (2, 3):
+        raise MMError("addmm_logsumexp_nt_ takes 2-D or 3-D operands")
+    n, k, m, batch, sa, sb = _nt_shapes("addmm_logsumexp_nt_", a, b)
+    batch, sc = _inplace_batch(c, n, m, batch)
+    cfg = make_config(dtype, "Add", reduce_op, path)
+    _enqueue(a.device, lib().mm_gemm_logsumexp_nt_enqueue, ctypes.byref(cfg), a.data_ptr(), b.data_ptr(), c.data_ptr(),
              n, k, m, batch, sa, sb, sc, 1)
     return c
 

@@ -15,6 +15,10 @@
 //   * argreduce_kernel: 64 x 64 outputs per 256-thread workgroup, 4 x 4 per thread, fully predicated: any shape, any
 //     element-aligned pointer, every map.  The parity anchor (MM_PATH_ORDERED always runs it).
 // Both take the batch through the workgroup id (batched_tile()), and `seeded` at run time.
+// BT (mm_gemm_argreduce_nt_*, "argreduce_tile_nt" / "argreduce_nt"): B is stored M x K row-major (Bt[j][k]), which is A's
+// N x K geometry, so it is fetched and staged as that branch stages A -- into the same k-major Bs.  The LDS read side and
+// the per-(output, k) sequence are untouched: the bits are those of the row-major kernel on a materialised transpose.
+// BT = false compiles to what it did before the flag existed (profiles/nt_products_isa_identity.txt).
 // Included once per element-type group (mm_argreduce_*.hip) to keep compile units parallel; every unit says
 // `#pragma clang fp contract(off)` before including this: the map is one rounded operation, like Naive's.
 #include "mm_common.h"
@@ -39,7 +43,7 @@ template <int RED, typename T> __device__ __forceinline__ T ar_start() {
 
 constexpr int AR_BM = 128, AR_BN = 128, AR_BK = 16, AR_PAD = 4;
 
-template <typename T, int MAP, int RED, bool AT>
+template <typename T, int MAP, int RED, bool AT, bool BT>
 __global__ __launch_bounds__(256) void argreduce_tile_kernel(const T *__restrict__ A, const T *__restrict__ B,
                                                              T *__restrict__ C, int *__restrict__ I, unsigned N, unsigned K,
                                                              unsigned M, unsigned tiles_n, unsigned tiles_m, unsigned kBand,
@@ -89,9 +93,14 @@ __global__ __launch_bounds__(256) void argreduce_tile_kernel(const T *__restrict
     return v;
   };
   auto fetch_b = [&](unsigned k0, unsigned id) {
-    const unsigned kr = id / 32, c4 = (id % 32) * 4;
     V v = {};
-    if (k0 + kr < K && col0 + c4 < M) v = *(const V *)(B + (size_t)(k0 + kr) * M + col0 + c4);
+    if (BT) {   // B is M x K: 4 lanes cover one column's 16 k, as for an N x K A
+      const unsigned c = id / 4, kc = (id % 4) * 4;
+      if (col0 + c < M && k0 + kc < K) v = *(const V *)(B + (size_t)(col0 + c) * K + k0 + kc);
+    } else {
+      const unsigned kr = id / 32, c4 = (id % 32) * 4;
+      if (k0 + kr < K && col0 + c4 < M) v = *(const V *)(B + (size_t)(k0 + kr) * M + col0 + c4);
+    }
     return v;
   };
   auto stage = [&](unsigned id, const V &a, const V &b) {
@@ -102,7 +111,13 @@ __global__ __launch_bounds__(256) void argreduce_tile_kernel(const T *__restrict
 #pragma unroll
       for (int e = 0; e < 4; ++e) As[kc + e][r] = a.v[e];
     }
-    *(V *)&Bs[id / 32][(id % 32) * 4] = b;
+    if (BT) {
+      const unsigned c = id / 4, kc = (id % 4) * 4;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) Bs[kc + e][c] = b.v[e];
+    } else {
+      *(V *)&Bs[id / 32][(id % 32) * 4] = b;
+    }
   };
 
   V ra0 = fetch_a(0, tid), ra1 = fetch_a(0, tid + 256), rb0 = fetch_b(0, tid), rb1 = fetch_b(0, tid + 256);
@@ -179,13 +194,13 @@ __global__ __launch_bounds__(256) void argreduce_tile_kernel(const T *__restrict
 
 constexpr int AR_TILE = 64, AR_PBK = 16, AR_PT = 4;
 
-template <typename T, int MAP, int RED, bool AT>
+template <typename T, int MAP, int RED, bool AT, bool BT>
 __global__ __launch_bounds__(256) void argreduce_kernel(const T *__restrict__ A, const T *__restrict__ B, T *__restrict__ C,
                                                         int *__restrict__ I, unsigned N, unsigned K, unsigned M,
                                                         size_t stride_a, size_t stride_b, size_t stride_c, int index_base,
                                                         int seeded) {
   __shared__ T As[AR_PBK][AR_TILE + 1];  // [k][row], +1: column reads of a row-major source
-  __shared__ T Bs[AR_PBK][AR_TILE];      // [k][col]
+  __shared__ T Bs[AR_PBK][AR_TILE + (BT ? 1 : 0)];   // [k][col]; BT: +1, staged as a row-major A is
   const unsigned tid = threadIdx.x;
   const unsigned tx = tid % 16, ty = tid / 16;
   // element e of the batch: XCD-remapped ids e * tiles .. (e + 1) * tiles - 1, row-major over its tile grid; uniform
@@ -227,9 +242,11 @@ __global__ __launch_bounds__(256) void argreduce_kernel(const T *__restrict__ A,
     }
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-      const unsigned c = tid % 64, kk = tid / 64 + 4 * i;
+      unsigned c, kk;
+      if (BT) { kk = tid % 16; c = tid / 16 + 16 * i; }   // B is M x K: consecutive lanes along K
+      else    { c = tid % 64; kk = tid / 64 + 4 * i; }    // B is K x M: consecutive lanes along M
       const unsigned gc = col0 + c, gk = k0 + kk;
-      Bs[kk][c] = (gc < M && gk < K) ? B[(size_t)gk * M + gc] : (T)0;
+      Bs[kk][c] = (gc < M && gk < K) ? B[BT ? (size_t)gc * K + gk : (size_t)gk * M + gc] : (T)0;
     }
     __syncthreads();
     const unsigned kmax = (K - k0) < (unsigned)AR_PBK ? (K - k0) : (unsigned)AR_PBK;
@@ -267,43 +284,42 @@ __global__ __launch_bounds__(256) void argreduce_kernel(const T *__restrict__ A,
   }
 }
 
-template <typename T, int MAP, int RED>
+// One launch of KERN for p's layouts.  BT (the unit's): the M x K B instantiation, else the N x K or the K x N A one -- a
+// unit holds the kernels of one B layout (mm_argreduce_*.hip: K x M; mm_argreduce_nt_*.hip: M x K).
+#define MM_AR_LAUNCH(KERN, GRID, ...)                                                                                  \
+  do {                                                                                                                 \
+    if constexpr (BT) hipLaunchKernelGGL((KERN<T, MAP, RED, false, true>), GRID, dim3(256), 0, s, __VA_ARGS__);        \
+    else if (p.a_transposed) hipLaunchKernelGGL((KERN<T, MAP, RED, true, false>), GRID, dim3(256), 0, s, __VA_ARGS__); \
+    else hipLaunchKernelGGL((KERN<T, MAP, RED, false, false>), GRID, dim3(256), 0, s, __VA_ARGS__);                    \
+  } while (0)
+
+template <typename T, int MAP, int RED, bool BT>
 int ar_launch(hipStream_t s, const Problem &p, int *index, int index_base, bool tile) {
   const int seeded = p.seed ? 1 : 0;
+  if (p.b_transposed != BT || (BT && p.a_transposed)) return kErrNotSupported;
   if (tile) {
     if constexpr (MAP == MM_OP_AND || sizeof(T) > 4) {
       return kErrNotSupported;
     } else {
       const unsigned tiles_n = (p.n + AR_BM - 1) / AR_BM, tiles_m = (p.m + AR_BN - 1) / AR_BN;
-      const unsigned grid = tiles_n * tiles_m * p.batch;
-      if (p.a_transposed)
-        hipLaunchKernelGGL((argreduce_tile_kernel<T, MAP, RED, true>), dim3(grid), dim3(256), 0, s, (const T *)p.a,
-                           (const T *)p.b, (T *)p.c, index, p.n, p.k, p.m, tiles_n, tiles_m, band_rows(), p.batch,
-                           p.stride_a, p.stride_b, p.stride_c, index_base, seeded);
-      else
-        hipLaunchKernelGGL((argreduce_tile_kernel<T, MAP, RED, false>), dim3(grid), dim3(256), 0, s, (const T *)p.a,
-                           (const T *)p.b, (T *)p.c, index, p.n, p.k, p.m, tiles_n, tiles_m, band_rows(), p.batch,
-                           p.stride_a, p.stride_b, p.stride_c, index_base, seeded);
+      MM_AR_LAUNCH(argreduce_tile_kernel, dim3(tiles_n * tiles_m * p.batch), (const T *)p.a, (const T *)p.b, (T *)p.c, index,
+                   p.n, p.k, p.m, tiles_n, tiles_m, band_rows(), p.batch, p.stride_a, p.stride_b, p.stride_c, index_base,
+                   seeded);
       return (int)hipGetLastError();
     }
   }
   const unsigned tiles = ((p.m + AR_TILE - 1) / AR_TILE) * ((p.n + AR_TILE - 1) / AR_TILE);
-  if (p.a_transposed)
-    hipLaunchKernelGGL((argreduce_kernel<T, MAP, RED, true>), dim3(tiles * p.batch), dim3(256), 0, s, (const T *)p.a,
-                       (const T *)p.b, (T *)p.c, index, p.n, p.k, p.m, p.stride_a, p.stride_b, p.stride_c, index_base,
-                       seeded);
-  else
-    hipLaunchKernelGGL((argreduce_kernel<T, MAP, RED, false>), dim3(tiles * p.batch), dim3(256), 0, s, (const T *)p.a,
-                       (const T *)p.b, (T *)p.c, index, p.n, p.k, p.m, p.stride_a, p.stride_b, p.stride_c, index_base,
-                       seeded);
+  MM_AR_LAUNCH(argreduce_kernel, dim3(tiles * p.batch), (const T *)p.a, (const T *)p.b, (T *)p.c, index, p.n, p.k, p.m,
+               p.stride_a, p.stride_b, p.stride_c, index_base, seeded);
   return (int)hipGetLastError();
 }
+#undef MM_AR_LAUNCH
 
-// TYPES: the element types the including unit instantiates
-template <typename TYPES>
+// TYPES: the element types the including unit instantiates; BT: for an M x K B (mm_argreduce_nt_*.hip)
+template <typename TYPES, bool BT = false>
 int ar_dispatch(hipStream_t s, const mm_config_t &cfg, const Problem &p, int *index, int index_base, bool tile) {
   return switch_config<TYPES, AllOps, MinMaxOps>(cfg, [&](auto t, auto map, auto red) {
-    return ar_launch<type_of<decltype(t)>, decltype(map)::value, decltype(red)::value>(s, p, index, index_base, tile);
+    return ar_launch<type_of<decltype(t)>, decltype(map)::value, decltype(red)::value, BT>(s, p, index, index_base, tile);
   });
 }
 

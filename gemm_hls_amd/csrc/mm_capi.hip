@@ -395,11 +395,20 @@ int check_accumulate(const mm_config_t *cfg, const mm::Problem &p, Family *fam) 
   return MM_OK;
 }
 
-// ---- argreduce (mm_gemm_argreduce_*): Min / Max with the winning k ----------------------------------------------------
+// The A x B^T forms (p.b_transposed: mm_gemm_nt_*, mm_gemm_argreduce_nt_*, mm_gemm_logsumexp_nt_*) serve a row-major A only
+bool bt_refused(const mm_config_t &cfg, const mm::Problem &p) { return p.b_transposed && cfg.layout_a == MM_A_TRANSPOSED; }
+int fail_bt(const mm_config_t &cfg) {
+  return fail(MM_ERR_UNSUPPORTED, "the A x B^T calls serve a row-major A (got layout_a %d): A^T B^T is not served", (int)cfg.layout_a);
+}
+
+// ---- argreduce (mm_gemm_argreduce_*, mm_gemm_argreduce_nt_*): Min / Max with the winning k ---------------------------
 enum ArKernel { AR_NONE, AR_PLAIN, AR_TILE };
 
-// The kernel by configuration and shape alone (mm_kernel_name_argreduce); alignment may still demote AR_TILE at launch.
+// The kernel by configuration and shape alone (mm_kernel_name_argreduce, mm_kernel_name_argreduce_nt); alignment may still
+// demote AR_TILE at launch.  An M x K B asks what a K x M B asks: K % 4 == 0 for the 4-wide loads of A and Bt, M % 4 == 0
+// for the 4-wide stores of C and I.
 ArKernel argreduce_kernel_for(const mm_config_t &cfg, const mm::Problem &p) {
+  if (bt_refused(cfg, p)) return AR_NONE;
   if (cfg.reduce_op != MM_OP_MIN && cfg.reduce_op != MM_OP_MAX) return AR_NONE;
   if (cfg.path == MM_PATH_SPLIT) return AR_NONE;
   if (cfg.path == MM_PATH_ORDERED) return AR_PLAIN;
@@ -412,6 +421,7 @@ ArKernel argreduce_kernel_for(const mm_config_t &cfg, const mm::Problem &p) {
 int check_argreduce(const mm_config_t *cfg, const mm::Problem &p, const int *index, int index_base, ArKernel *ker) {
   *ker = AR_NONE;
   if (!valid_cfg(cfg)) return fail(MM_ERR_BAD_ARGUMENT, "invalid mm_config_t");
+  if (bt_refused(*cfg, p)) return fail_bt(*cfg);
   if (cfg->reduce_op != MM_OP_MIN && cfg->reduce_op != MM_OP_MAX)
     return fail(MM_ERR_UNSUPPORTED, "argreduce needs a Min or Max reduction (got reduce %d)", (int)cfg->reduce_op);
   if (cfg->path == MM_PATH_SPLIT) return fail(MM_ERR_UNSUPPORTED, "MM_PATH_SPLIT has no argreduce form");
@@ -565,7 +575,7 @@ int dispatch_closure(hipStream_t s, const mm_config_t &cfg, void *d, int *w, uns
   return rc;
 }
 
-// ---- log semiring (mm_gemm_logsumexp_*): log sum exp (A + B) -------------------------------------------------------------
+// ---- log semiring (mm_gemm_logsumexp_*, mm_gemm_logsumexp_nt_*): log sum exp (A + B) --------------------------------------
 enum LseKernel { LSE_NONE, LSE_EXACT, LSE_HYBRID };
 
 // The kernel by configuration and knob alone (mm_kernel_name_logsumexp).  *bad_knob: lse_variant holds a value it does not take.
@@ -584,6 +594,7 @@ LseKernel lse_kernel_for(const mm_config_t &cfg, bool *bad_knob) {
 int check_lse(const mm_config_t *cfg, const mm::Problem &p, LseKernel *ker) {
   *ker = LSE_NONE;
   if (!valid_cfg(cfg)) return fail(MM_ERR_BAD_ARGUMENT, "invalid mm_config_t");
+  if (bt_refused(*cfg, p)) return fail_bt(*cfg);
   bool bad_knob;
   const LseKernel k = lse_kernel_for(*cfg, &bad_knob);
   if (k == LSE_NONE)
@@ -616,7 +627,8 @@ int lse_exact_chunks(hipStream_t s, const mm_config_t &cfg, const mm::Problem &p
 // Workspace of one chunk of the hybrid stays near this; an element that alone needs more runs alone.
 constexpr size_t kLseWorkspaceCap = 256ull << 20;
 
-// The hybrid, never synchronising the host: per chunk of the batch, prepass (row maxima of A, column maxima of B, EA and EB
+// The hybrid, never synchronising the host: per chunk of the batch, prepass (row maxima of A, column maxima of B -- row maxima
+// of an M x K B: "lse_hybrid_nt", whose EB is K-major in the workspace all the same --, EA and EB
 // zero-padded to multiples of 64 in f32 / f64), S = EA @ EB on the matrix cores, the epilogue (C and one flag per tile) and
 // the exact kernel over the flagged tiles.  A broadcast operand is transformed once.  The product's kernel is resolved once on
 // the whole batch, so an element's bits do not depend on the chunk it falls in.
@@ -653,7 +665,7 @@ int dispatch_lse_hybrid(hipStream_t s, const mm_config_t &cfg, const mm::Problem
   mm::LseOperand opa{}, opb{};
   opa.rows = p.n; opa.k = p.k; opa.rows_p = np; opa.k_p = kp; opa.x_kmajor = p.a_transposed; opa.out_kmajor = false;
   opa.e = pea; opa.r = pra; opa.stride_x = p.stride_a; opa.stride_e = ea; opa.stride_r = ra;
-  opb.rows = p.m; opb.k = p.k; opb.rows_p = mp; opb.k_p = kp; opb.x_kmajor = true; opb.out_kmajor = true;
+  opb.rows = p.m; opb.k = p.k; opb.rows_p = mp; opb.k_p = kp; opb.x_kmajor = !p.b_transposed; opb.out_kmajor = true;
   opb.e = peb; opb.r = prb; opb.stride_x = p.stride_b; opb.stride_e = eb; opb.stride_r = rb;
   if (rc == MM_OK && a_shared) {
     opa.x = p.a; opa.count = 1;
@@ -981,13 +993,16 @@ int run_batched(const Target &t, const mm_config_t *cfg, const mm::Problem &p) {
   return run(t, fam == FAM_NONE, [&](hipStream_t s) { return dispatch_batched(s, *cfg, p, fam); });
 }
 
-int run_argreduce(const Target &t, const mm_config_t *cfg, const mm::Problem &p, int *c_index, int index_base) {
+// bt: the A x B^T form of the call (p.b is M x K per element)
+int run_argreduce(const Target &t, const mm_config_t *cfg, mm::Problem p, int *c_index, int index_base, bool bt = false) {
+  p.b_transposed = bt;
   ArKernel ker;
   if (int rc = check_argreduce(cfg, p, c_index, index_base, &ker)) return rc;
   return run(t, ker == AR_NONE, [&](hipStream_t s) { return dispatch_argreduce(s, *cfg, p, c_index, index_base, ker); });
 }
 
-int run_lse(const Target &t, const mm_config_t *cfg, const mm::Problem &p) {
+int run_lse(const Target &t, const mm_config_t *cfg, mm::Problem p, bool bt = false) {
+  p.b_transposed = bt;
   LseKernel ker;
   if (int rc = check_lse(cfg, p, &ker)) return rc;
   return run(t, ker == LSE_NONE, [&](hipStream_t s) { return dispatch_lse(s, *cfg, p, ker); });
@@ -1294,6 +1309,33 @@ int mm_gemm_nt_launch(int device, const mm_config_t *cfg, const void *a, const v
                       double *elapsed_seconds) {
   return run_nt(timed_on(device, elapsed_seconds), cfg,
                 batched_problem(cfg, a, bt, c, n, k, m, batch, stride_a, stride_b, stride_c, accumulate != 0));
+}
+
+int mm_gemm_argreduce_nt_enqueue(void *hip_stream, const mm_config_t *cfg, const void *a, const void *bt, void *c, int *c_index,
+                                 unsigned n, unsigned k, unsigned m, unsigned batch, size_t stride_a, size_t stride_b,
+                                 size_t stride_c, int index_base, int accumulate) {
+  return run_argreduce(on_stream(hip_stream), cfg,
+                       batched_problem(cfg, a, bt, c, n, k, m, batch, stride_a, stride_b, stride_c, accumulate != 0), c_index, index_base, true);
+}
+
+int mm_gemm_argreduce_nt_launch(int device, const mm_config_t *cfg, const void *a, const void *bt, void *c, int *c_index,
+                                unsigned n, unsigned k, unsigned m, unsigned batch, size_t stride_a, size_t stride_b,
+                                size_t stride_c, int index_base, int accumulate, double *elapsed_seconds) {
+  return run_argreduce(timed_on(device, elapsed_seconds), cfg,
+                       batched_problem(cfg, a, bt, c, n, k, m, batch, stride_a, stride_b, stride_c, accumulate != 0), c_index, index_base, true);
+}
+
+int mm_gemm_logsumexp_nt_enqueue(void *hip_stream, const mm_config_t *cfg, const void *a, const void *bt, void *c, unsigned n,
+                                 unsigned k, unsigned m, unsigned batch, size_t stride_a, size_t stride_b, size_t stride_c,
+                                 int accumulate) {
+  return run_lse(on_stream(hip_stream), cfg, batched_problem(cfg, a, bt, c, n, k, m, batch, stride_a, stride_b, stride_c, accumulate != 0), true);
+}
+
+int mm_gemm_logsumexp_nt_launch(int device, const mm_config_t *cfg, const void *a, const void *bt, void *c, unsigned n,
+                                unsigned k, unsigned m, unsigned batch, size_t stride_a, size_t stride_b, size_t stride_c,
+                                int accumulate, double *elapsed_seconds) {
+  return run_lse(timed_on(device, elapsed_seconds), cfg,
+                 batched_problem(cfg, a, bt, c, n, k, m, batch, stride_a, stride_b, stride_c, accumulate != 0), true);
 }
 
 int mm_closure_enqueue(void *hip_stream, const mm_config_t *cfg, void *d, int *witness, unsigned n, unsigned batch,
@@ -1626,24 +1668,44 @@ const char *mm_kernel_name_batched(const mm_config_t *cfg, unsigned n, unsigned 
   }
 }
 
-const char *mm_kernel_name_argreduce(const mm_config_t *cfg, unsigned n, unsigned k, unsigned m, unsigned batch) {
+static const char *argreduce_name(const mm_config_t *cfg, unsigned n, unsigned k, unsigned m, unsigned batch, bool bt) {
   if (!valid_cfg(cfg)) return "invalid";
-  const mm::Problem p = batched_problem(cfg, nullptr, nullptr, nullptr, n, k, m, batch ? batch : 1, 0, 0, 0);
+  mm::Problem p = batched_problem(cfg, nullptr, nullptr, nullptr, n, k, m, batch ? batch : 1, 0, 0, 0);
+  p.b_transposed = bt;
   switch (argreduce_kernel_for(*cfg, p)) {   // the choice check_argreduce makes, before alignment
-    case AR_TILE: return "argreduce_tile";
-    case AR_PLAIN: return "argreduce";
+    case AR_TILE: return bt ? "argreduce_tile_nt" : "argreduce_tile";
+    case AR_PLAIN: return bt ? "argreduce_nt" : "argreduce";
     default: return "unsupported";
   }
 }
 
-const char *mm_kernel_name_logsumexp(const mm_config_t *cfg, unsigned n, unsigned k, unsigned m, unsigned batch) {
-  (void)n, (void)k, (void)m, (void)batch;   // the choice is the configuration's and the knob's, not the shape's
+const char *mm_kernel_name_argreduce(const mm_config_t *cfg, unsigned n, unsigned k, unsigned m, unsigned batch) {
+  return argreduce_name(cfg, n, k, m, batch, false);
+}
+
+const char *mm_kernel_name_argreduce_nt(const mm_config_t *cfg, unsigned n, unsigned k, unsigned m, unsigned batch) {
+  return argreduce_name(cfg, n, k, m, batch, true);
+}
+
+// (the choice is the configuration's and the knob's, not the shape's)
+static const char *logsumexp_name(const mm_config_t *cfg, bool bt) {
   if (!valid_cfg(cfg)) return "invalid";
   bool bad_knob;
   const LseKernel ker = lse_kernel_for(*cfg, &bad_knob);   // the choice check_lse makes
-  if (ker == LSE_NONE) return "unsupported";
+  if (ker == LSE_NONE || (bt && cfg->layout_a == MM_A_TRANSPOSED)) return "unsupported";
   if (bad_knob) return "invalid";
+  if (bt) return ker == LSE_HYBRID ? "lse_hybrid_nt" : "lse_exact_nt";
   return ker == LSE_HYBRID ? "lse_hybrid" : "lse_exact";
+}
+
+const char *mm_kernel_name_logsumexp(const mm_config_t *cfg, unsigned n, unsigned k, unsigned m, unsigned batch) {
+  (void)n, (void)k, (void)m, (void)batch;
+  return logsumexp_name(cfg, false);
+}
+
+const char *mm_kernel_name_logsumexp_nt(const mm_config_t *cfg, unsigned n, unsigned k, unsigned m, unsigned batch) {
+  (void)n, (void)k, (void)m, (void)batch;
+  return logsumexp_name(cfg, true);
 }
 
 const char *mm_kernel_name_widen(const mm_config_t *cfg, unsigned n, unsigned k, unsigned m, unsigned batch) {

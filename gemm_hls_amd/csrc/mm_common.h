@@ -96,8 +96,9 @@ struct Problem {
   // accumulate (mm_gemm_*accumulate_*): C <- C (+) (A (x) B), each output's reduction starts at the value C holds instead
   // of identity().  Only the *_batched launchers read it (they then run the kernels' Form::Seeded instantiations).
   bool seed = false;
-  // A x B^T (mm_gemm_nt_*): b is M x K row-major per element (Bt[j][k]; stride_b counts its elements).  Only the *_nt
-  // launchers are handed such a problem; nothing else reads this.
+  // A x B^T (mm_gemm_nt_*, mm_gemm_argreduce_nt_*, mm_gemm_logsumexp_nt_*): b is M x K row-major per element (Bt[j][k];
+  // stride_b counts its elements), never together with a_transposed.  Only the *_nt launchers, launch_argreduce and
+  // launch_lse_exact are handed such a problem; nothing else reads this.
   bool b_transposed = false;
 };
 
@@ -158,7 +159,10 @@ int launch_valu_tile_exact(hipStream_t s, const mm_config_t &cfg, const Problem 
 // Min / Max reductions with the winning k (mm_gemm_argreduce_*, mm_argreduce_*.hip): the p.batch elements of p, C and the
 // int32 index matrix `index` with the same element strides (p.stride_c); p.seed starts from C and `index`.  tile: the
 // register-tiled argreduce_tile kernel (valu_tile_serves() and 16-byte aligned operands), else the predicated argreduce.
+// p.b_transposed: launch_argreduce_nt, their M x K B instantiations "argreduce_tile_nt" and "argreduce_nt"
+// (mm_argreduce_nt_*.hip).
 int launch_argreduce(hipStream_t s, const mm_config_t &cfg, const Problem &p, int *index, int index_base, bool tile);
+int launch_argreduce_nt(hipStream_t s, const mm_config_t &cfg, const Problem &p, int *index, int index_base, bool tile);
 // One launch of a closure round (mm_closure_*.hip): block K = [k0, k0 + bt) of `graphs` graphs at d + e * stride_d, n x n
 // each; w (int32, D's strides) null for the value-only form.  panels = false: step 1 (closure_diag_kernel, one workgroup per
 // graph; w_fresh: start the witnesses at -1 instead of reading w); true: step 2 (closure_panel_kernel).  cc / rc: the
@@ -177,7 +181,7 @@ struct ClosureStep {
 int launch_closure(hipStream_t s, const mm_config_t &cfg, const ClosureStep &st);
 // Log-semiring product (mm_gemm_logsumexp_*, mm_lse_fp.hip).  launch_lse_exact: the exact kernel over the p.batch elements of
 // p (p.seed: C's input is one more term); flags != null: the hybrid's fallback, tile t of element e runs only where
-// flags[e * tiles + t] != 0 (64 x 64 tiles).  The hybrid's prepass transforms `count` elements of one operand: r = the
+// flags[e * tiles + t] != 0 (64 x 64 tiles); p.b_transposed: launch_lse_exact_nt, "lse_exact_nt" (mm_lse_nt_fp.hip).  The hybrid's prepass transforms `count` elements of one operand: r = the
 // per-line maxima (NaN-propagating; Min: of the negated operand) and e = exp(X - r), zero-padded to rows_p x k_p
 // (out_kmajor: k_p x rows_p), in f32 (f64 for double).  X is rows x k row-major, or k x rows when x_kmajor.
 struct LseOperand {
@@ -198,6 +202,8 @@ struct LseEpilogue {
   bool seed, force;
 };
 int launch_lse_exact(hipStream_t s, const mm_config_t &cfg, const Problem &p, const int *flags);
+int launch_lse_exact_nt(hipStream_t s, const mm_config_t &cfg, const Problem &p, const int *flags);
+int launch_lse_expand_nt(hipStream_t s, const mm_config_t &cfg, const LseOperand &op);   // e of an M x K B: !x_kmajor, out_kmajor
 int launch_lse_prepass(hipStream_t s, const mm_config_t &cfg, const LseOperand &op);
 int launch_lse_epilogue(hipStream_t s, const mm_config_t &cfg, const LseEpilogue &ep);
 int launch_mfma_f32(hipStream_t s, const Problem &p, int variant);

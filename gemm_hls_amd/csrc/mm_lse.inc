@@ -9,6 +9,8 @@
 //     then s += exp2(fma(t, log2 e, -m log2 e)) (v_fma, v_exp_f32, v_add).  The shift is clamped to a finite value, so
 //     -inf - -inf never happens: an all -inf output keeps s = 0 and returns -inf.  It is the contract path, the hybrid's
 //     fallback (flags != null: a workgroup whose tile flag is clear exits at once) and what MM_PATH_ORDERED runs.
+//     BT ("lse_exact_nt", mm_gemm_logsumexp_nt_*): B is stored M x K row-major and staged as an N x K A is, into the same
+//     k-major Bs; the slabs, their order and every output's sequence are the row-major kernel's, so are the bits.
 //   * lse_rowmax_kernel / lse_colmax_kernel / lse_expand_kernel: the hybrid's prepass -- per-row (per-column) maxima of an
 //     operand, NaN-propagating, and E = exp(X - max) into a zero-padded row-major workspace matrix.
 //   * lse_epilogue_kernel: C = ra_i + rb_j + log S (S = EA @ EB from the matrix cores), combined with C's input by a stable
@@ -83,7 +85,7 @@ template <typename T> __device__ __forceinline__ typename LseType<T>::F lse_load
 
 constexpr int LSE_T = 64, LSE_BK = 16, LSE_SK = 4, LSE_PT = 4, LSE_APAD = 4;
 
-template <typename T, int RED, bool AT>
+template <typename T, int RED, bool AT, bool BT>
 __global__ __launch_bounds__(256) void lse_exact_kernel(const T *__restrict__ A, const T *__restrict__ B, T *__restrict__ C,
                                                         unsigned N, unsigned K, unsigned M, size_t stride_a, size_t stride_b,
                                                         size_t stride_c, int seeded, const int *__restrict__ flags) {
@@ -93,7 +95,7 @@ __global__ __launch_bounds__(256) void lse_exact_kernel(const T *__restrict__ A,
   // terms per slab: 4 for f32; f64 takes 1 (its ocml exp2 is long, and 4 x 4 outputs of f64 slabs spilled to AGPRs)
   constexpr int SK = sizeof(F) == 4 ? LSE_SK : 1;
   __shared__ __attribute__((aligned(16))) F As[LSE_BK][LSE_T + LSE_APAD];   // [k][row]; the pad spreads the transposing writes
-  __shared__ __attribute__((aligned(16))) F Bs[LSE_BK][LSE_T];              // [k][col]
+  __shared__ __attribute__((aligned(16))) F Bs[LSE_BK][LSE_T + (BT ? LSE_APAD : 0)];   // [k][col]; BT: padded as As is
   const unsigned tid = threadIdx.x, tx = tid % 16, ty = tid / 16;
   // element e of the batch: ids e * tiles .. (e + 1) * tiles - 1, row-major over its tile grid; uniform
   const unsigned tiles_m = (M + LSE_T - 1) / LSE_T, tiles = tiles_m * ((N + LSE_T - 1) / LSE_T);
@@ -134,9 +136,11 @@ __global__ __launch_bounds__(256) void lse_exact_kernel(const T *__restrict__ A,
     }
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-      const unsigned c = tid % 64, kk = tid / 64 + 4 * i;
+      unsigned c, kk;
+      if (BT) { kk = tid % 16; c = tid / 16 + 16 * i; }   // B is M x K: consecutive lanes along K
+      else    { c = tid % 64; kk = tid / 64 + 4 * i; }    // B is K x M: consecutive lanes along M
       const unsigned gc = col0 + c, gk = k0 + kk;
-      Bs[kk][c] = (gc < M && gk < K) ? sg * lse_load(B + (size_t)gk * M + gc) : (F)0;
+      Bs[kk][c] = (gc < M && gk < K) ? sg * lse_load(B + (BT ? (size_t)gc * K + gk : (size_t)gk * M + gc)) : (F)0;
     }
     __syncthreads();
 #pragma unroll 1
@@ -233,7 +237,8 @@ __global__ __launch_bounds__(256) void lse_colmax_kernel(const T *__restrict__ X
 }
 
 // E[e] = exp(sg X - r) into a zero-padded row-major workspace matrix: out_kmajor ? Kp x Rp : Rp x Kp; X is R x K
-// (x_kmajor = false) or K x R.  One thread per element of E.
+// (x_kmajor = false) or K x R.  One thread per element of E.  (XK, OK) = (false, true) is the M x K B of the A x B^T
+// call: lanes run along E's rows, so the stores are contiguous and the loads of X are K elements apart.
 template <typename T, int RED, bool XK, bool OK>
 __global__ __launch_bounds__(256) void lse_expand_kernel(const T *__restrict__ X, const typename LseType<T>::F *__restrict__ R,
                                                          typename LseType<T>::F *__restrict__ E, unsigned rows, unsigned K,
@@ -313,6 +318,32 @@ __global__ __launch_bounds__(256) void lse_epilogue_kernel(const typename LseTyp
       if (gc < M) C[(size_t)gr * M + gc] = (T)out[i][j];
     }
   }
+}
+
+// ---- host side, shared by the units that hold these kernels (mm_lse_fp.hip; mm_lse_nt_fp.hip for an M x K B) -----------
+template <typename T, int RED, bool AT, bool BT>
+int lse_exact_launch(hipStream_t s, const Problem &p, const int *flags) {
+  const unsigned tiles = ((p.m + LSE_T - 1) / LSE_T) * ((p.n + LSE_T - 1) / LSE_T);
+  hipLaunchKernelGGL((lse_exact_kernel<T, RED, AT, BT>), dim3(tiles * p.batch), dim3(256), 0, s, (const T *)p.a,
+                     (const T *)p.b, (T *)p.c, p.n, p.k, p.m, p.stride_a, p.stride_b, p.stride_c, p.seed ? 1 : 0, flags);
+  return (int)hipGetLastError();
+}
+
+template <typename T, int RED, bool XK, bool OK>
+int lse_expand_launch(hipStream_t s, const LseOperand &op) {
+  using F = typename LseType<T>::F;
+  const unsigned long long total = (unsigned long long)op.count * op.rows_p * op.k_p;
+  const unsigned long long blocks = (total + 255) / 256;
+  hipLaunchKernelGGL((lse_expand_kernel<T, RED, XK, OK>), dim3((unsigned)(blocks < (1ull << 20) ? blocks : 1ull << 20)),
+                     dim3(256), 0, s, (const T *)op.x, (const F *)op.r, (F *)op.e, op.rows, op.k, op.rows_p, op.k_p,
+                     op.stride_x, op.stride_r, op.stride_e, total);
+  return (int)hipGetLastError();
+}
+
+// half / float / double x (Add, Min / Max) -> f(Tag<T>, Add, RED)
+template <typename Fn>
+int lse_dispatch(const mm_config_t &cfg, Fn f) {
+  return switch_config<FpTypes, Ops<MM_OP_ADD>, MinMaxOps>(cfg, f);
 }
 
 }  // namespace

@@ -400,6 +400,62 @@ int mm_gemm_nt_launch(int device, const mm_config_t *cfg, const void *a_dev, con
  * "invalid" for a bad configuration.  Static string, pure arithmetic. */
 const char *mm_kernel_name_nt(const mm_config_t *cfg, unsigned size_n, unsigned size_k, unsigned size_m, unsigned batch);
 
+/* A x B^T forms of the two derived products: mm_gemm_argreduce_* and mm_gemm_logsumexp_* with B stored M x K row-major, as
+ * in mm_gemm_nt_* -- the backpointers of a Viterbi step and the forward / partition-function step over a "to-state major"
+ * transition matrix, without the K x M copy of a transposition by the caller.  bt_dev: M x K row-major per element; stride_b
+ * counts ITS elements, 0 = broadcast.  Each contract is the row-major call's with B[e,k,j] read as Bt[e,j,k]; every other
+ * argument (c_index, index_base, accumulate, the strides, the "batch_chunk" chunking) is the row-major call's.
+ * Argmin / argmax.  For output (e, i, j), with Reduce = cfg->reduce_op in {Min, Max}:
+ *     acc = accumulate ? C[e,i,j] : Reduce::identity();   idx = accumulate ? I[e,i,j] : -1
+ *     for k = 0 .. K-1 ascending:
+ *         s = Map(A[e,i,k], Bt[e,j,k])
+ *         if (Min: s < acc  /  Max: acc < s) { acc = s; idx = index_base + k; }
+ *     C[e,i,j] = acc;  I[e,i,j] = idx
+ * C and I are bit for bit what mm_gemm_argreduce_* returns on a materialised transpose, on both kernels and under both
+ * paths, NaN, +-inf and +-0 included: ties keep the smallest k, a NaN mapped value is never taken, a surviving seed keeps its
+ * index.  Kernels (mm_kernel_name_argreduce_nt): "argreduce_tile_nt" (the register-tiled kernel, Bt staged the way it stages
+ * an N x K A) under MM_PATH_AUTO for elements of at most 4 bytes with a map in {Add, Multiply, Min, Max}, K % 4 == 0 and
+ * M % 4 == 0; "argreduce_nt" (fully predicated, any shape, any element-aligned pointer, every map) for everything else --
+ * the 8-byte types, the And map, any other shape -- and always under MM_PATH_ORDERED.  The name is decided by
+ * configuration, shape and path alone: a tile launch whose a, bt, c or c_index -- base, or element stride in bytes -- is not
+ * 16-byte aligned runs "argreduce_nt" instead, the same bits, no error.
+ * Log semiring.  The terms are s_k = A[e,i,k] + Bt[e,j,k]; the error bound (with rb_j = max_k Bt[j,k]), the special-value
+ * rules and the determinism of mm_gemm_logsumexp_* hold unchanged.  Kernels (mm_kernel_name_logsumexp_nt), chosen exactly as
+ * mm_kernel_name_logsumexp chooses, "lse_variant" included: "lse_exact_nt" has the row-major exact kernel's per-output
+ * sequence and gives its bits on a materialised transpose; "lse_hybrid_nt" takes rb and EB from Bt as it lies (EB still
+ * K-major in the workspace), runs the same product and epilogue, and falls back to lse_exact_nt on the flagged tiles: the
+ * row-major hybrid's values, where only the sign of a zero may differ, because the maxima of Bt are reduced in another
+ * order.  Workspace, chunking and "never synchronises the host" as for the row-major hybrid.
+ * Refused before any device is touched: MM_A_TRANSPOSED (MM_ERR_UNSUPPORTED, as in mm_gemm_nt_*) and everything the
+ * row-major call of the product refuses, with its status: MM_PATH_SPLIT, a reduction other than Min / Max, for the log
+ * semiring a dtype other than half, float and double or a map other than Add (MM_ERR_UNSUPPORTED); a bad "lse_variant" or
+ * index_base, a null pointer, overlapping outputs, and the span of C (or of I) overlapping A's or Bt's
+ * (MM_ERR_BAD_ARGUMENT).  A and Bt may be the same buffer.  batch, N or M 0: MM_OK; K = 0: MM_ERR_BAD_ARGUMENT in the plain
+ * form, MM_OK (nothing written) when accumulating.
+ * _enqueue: asynchronous on a hipStream_t of the CURRENT device, never synchronises the host; _launch: blocking,
+ * *elapsed_seconds (may be NULL) timed with HIP events. */
+int mm_gemm_argreduce_nt_enqueue(void *hip_stream, const mm_config_t *cfg, const void *a_dev, const void *bt_dev, void *c_dev,
+                                 int *c_index, unsigned size_n, unsigned size_k, unsigned size_m, unsigned batch,
+                                 size_t stride_a, size_t stride_b, size_t stride_c, int index_base, int accumulate);
+int mm_gemm_argreduce_nt_launch(int device, const mm_config_t *cfg, const void *a_dev, const void *bt_dev, void *c_dev,
+                                int *c_index, unsigned size_n, unsigned size_k, unsigned size_m, unsigned batch,
+                                size_t stride_a, size_t stride_b, size_t stride_c, int index_base, int accumulate,
+                                double *elapsed_seconds);
+/* "argreduce_tile_nt" or "argreduce_nt"; "unsupported" for a configuration the calls refuse with MM_ERR_UNSUPPORTED;
+ * "invalid" for a bad configuration.  Static string, pure arithmetic. */
+const char *mm_kernel_name_argreduce_nt(const mm_config_t *cfg, unsigned size_n, unsigned size_k, unsigned size_m,
+                                        unsigned batch);
+int mm_gemm_logsumexp_nt_enqueue(void *hip_stream, const mm_config_t *cfg, const void *a_dev, const void *bt_dev, void *c_dev,
+                                 unsigned size_n, unsigned size_k, unsigned size_m, unsigned batch,
+                                 size_t stride_a, size_t stride_b, size_t stride_c, int accumulate);
+int mm_gemm_logsumexp_nt_launch(int device, const mm_config_t *cfg, const void *a_dev, const void *bt_dev, void *c_dev,
+                                unsigned size_n, unsigned size_k, unsigned size_m, unsigned batch,
+                                size_t stride_a, size_t stride_b, size_t stride_c, int accumulate, double *elapsed_seconds);
+/* "lse_hybrid_nt" or "lse_exact_nt"; "unsupported" for a configuration the calls refuse with MM_ERR_UNSUPPORTED; "invalid"
+ * for a bad configuration or knob value.  Pure arithmetic. */
+const char *mm_kernel_name_logsumexp_nt(const mm_config_t *cfg, unsigned size_n, unsigned size_k, unsigned size_m,
+                                        unsigned batch);
+
 /* Closure: all-pairs shortest / widest / longest paths and transitive closure -- blocked Floyd-Warshall, in place.
  * D is n x n, row-major; graph e of the batch starts at d_dev + e * stride_d (elements; stride_d >= n * n when batch > 1).
  * The call runs the recurrence D[i][j] <- D[i][j] (+) D[i][v] (x) D[v][j] over every v, with Reduce = cfg->reduce_op in

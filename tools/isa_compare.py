@@ -4,6 +4,7 @@ to assembly with the flags the product is built with (build.COMMON without --off
 
     python tools/isa_compare.py OLD_TREE NEW_TREE [unit ...]        # default: the nine units whose kernels take a Form
     python tools/isa_compare.py --same-naming OLD_TREE NEW_TREE [unit ...]   # default: every .hip unit of NEW_TREE's csrc
+    python tools/isa_compare.py --flag-added OLD_TREE NEW_TREE [unit ...]    # default: every .hip unit of OLD_TREE's csrc
 
 Without --same-naming, OLD_TREE names a kernel's form in its symbol (`*_batched`, `*_batched_seeded`), NEW_TREE in a template argument
 (`(mm::Form)N`; mfma_f32_batched_kernel: a trailing `bool SEED`).  Kernels are paired by (base name, form, the remaining
@@ -15,6 +16,10 @@ difference, unpaired kernel or changed kernel count.
 
 --same-naming: both trees name a kernel's form in a template argument (a host-side refactor, say).  Kernels are paired by
 their whole demangled name and nothing may differ, .amdhsa_kernarg_size included.
+
+--flag-added: --same-naming, where NEW_TREE gave some kernels one more trailing `bool` template parameter.  A NEW kernel
+whose name is not OLD's pairs with the OLD kernel of that name without a trailing `, false`; the `true` instantiations are
+new kernels, counted and not compared.  Every OLD kernel must be paired and identical.
 """
 import concurrent.futures
 import os
@@ -62,14 +67,17 @@ def kernels(asm):
     return out
 
 
-def keyed(kerns, new, same_naming=False):
-    """{(base name, form, other template arguments): symbol}; same_naming: {(demangled name, "", ""): symbol}"""
+def keyed(kerns, new, same_naming=False, known=None):
+    """{(base name, form, other template arguments): symbol}; same_naming: {(demangled name, "", ""): symbol}, a name
+    not in `known` (given) taken without its trailing `, false` template argument where that is in `known`"""
     # _Float16 (DF16_) is newer than some c++filt; a builtin type takes no substitution slot, so `Dh` (half) stands in
     names = subprocess.run(["c++filt"], input="\n".join(k.replace("DF16_", "Dh") for k in kerns), capture_output=True,
                            text=True, check=True).stdout.split("\n")
     out = {}
     for sym, d in zip(kerns, names):
         if same_naming:
+            if known is not None and d not in known and d.replace(", false>(", ">(", 1) in known:
+                d = d.replace(", false>(", ">(", 1)
             assert (d, "", "") not in out, d
             out[(d, "", "")] = sym
             continue
@@ -90,9 +98,10 @@ def keyed(kerns, new, same_naming=False):
     return out
 
 
-def compare(old_tree, new_tree, unit, same_naming=False):
+def compare(old_tree, new_tree, unit, same_naming=False, flag_added=False):
     old, new = kernels(assembly(old_tree, unit)), kernels(assembly(new_tree, unit))
-    ko, kn = keyed(old, False, same_naming), keyed(new, True, same_naming)
+    ko = keyed(old, False, same_naming)
+    kn = keyed(new, True, same_naming, {k[0] for k in ko} if flag_added else None)
     notes, same = [], 0
     for key in sorted(ko.keys() & kn.keys()):
         (bo, ro), (bn, rn) = old[ko[key]], new[kn[key]]
@@ -104,21 +113,26 @@ def compare(old_tree, new_tree, unit, same_naming=False):
         if diff:
             notes.append(f"  differs: {key}: {diff}")
     notes += [f"  only in OLD: {k}" for k in sorted(ko.keys() - kn.keys())]
-    notes += [f"  only in NEW: {k}" for k in sorted(kn.keys() - ko.keys())]
+    added = sorted(kn.keys() - ko.keys())
+    if not flag_added:
+        notes += [f"  only in NEW: {k}" for k in added]
     paired = len(ko.keys() & kn.keys())
     line = f"{unit}: kernels {len(old)} -> {len(new)}, paired {paired}, identical {same}, differing {paired - same}"
-    return "\n".join([line] + notes), not notes and len(old) == len(new)
+    if flag_added:
+        line += f", new {len(added)}"
+    return "\n".join([line] + notes), not notes and (flag_added or len(old) == len(new))
 
 
 def main():
-    argv = [a for a in sys.argv[1:] if a != "--same-naming"]
-    same_naming = len(argv) < len(sys.argv) - 1
+    argv = [a for a in sys.argv[1:] if a not in ("--same-naming", "--flag-added")]
+    flag_added = "--flag-added" in sys.argv[1:]
+    same_naming = flag_added or "--same-naming" in sys.argv[1:]
     if len(argv) < 2:
         raise SystemExit(__doc__)
-    every = sorted(f for f in os.listdir(os.path.join(argv[1], "gemm_hls_amd", "csrc")) if f.endswith(".hip"))
+    every = sorted(f for f in os.listdir(os.path.join(argv[0 if flag_added else 1], "gemm_hls_amd", "csrc")) if f.endswith(".hip"))
     units = argv[2:] or (every if same_naming else UNITS)
     with concurrent.futures.ThreadPoolExecutor(max_workers=min(8, os.cpu_count() or 4) // 2 or 1) as ex:
-        results = list(ex.map(lambda u: compare(argv[0], argv[1], u, same_naming), units))
+        results = list(ex.map(lambda u: compare(argv[0], argv[1], u, same_naming, flag_added), units))
     for text, _ in results:
         print(text)
     return 0 if all(ok for _, ok in results) else 1
