@@ -13,15 +13,17 @@
 //     8-byte values, their indices and the prefetch do not fit 256 VGPRs (the compiler spilled to AGPRs, and the kernel
 //     ran slower than argreduce), so the 8-byte types are not instantiated here.
 //   * argreduce_kernel: 64 x 64 outputs per 256-thread workgroup, 4 x 4 per thread, fully predicated: any shape, any
-//     element-aligned pointer, every map.  The parity anchor (MM_PATH_ORDERED always runs it).
+//     element-aligned pointer, every map.  The parity anchor (MM_PATH_ORDERED always runs it).  Tile origin and staging:
+//     mm_tile64.h.
 // Both take the batch through the workgroup id (batched_tile()), and `seeded` at run time.
 // BT (mm_gemm_argreduce_nt_*, "argreduce_tile_nt" / "argreduce_nt"): B is stored M x K row-major (Bt[j][k]), which is A's
-// N x K geometry, so it is fetched and staged as that branch stages A -- into the same k-major Bs.  The LDS read side and
+// N x K geometry, so it is fetched and staged as that branch stages A (argreduce_kernel: tile64_stage's k-contiguous
+// mapping) -- into the same k-major Bs.  The LDS read side and
 // the per-(output, k) sequence are untouched: the bits are those of the row-major kernel on a materialised transpose.
 // BT = false compiles to what it did before the flag existed (profiles/nt_products_isa_identity.txt).
 // Included once per element-type group (mm_argreduce_*.hip) to keep compile units parallel; every unit says
 // `#pragma clang fp contract(off)` before including this: the map is one rounded operation, like Naive's.
-#include "mm_common.h"
+#include "mm_tile64.h"
 
 namespace mm {
 namespace {
@@ -192,33 +194,24 @@ __global__ __launch_bounds__(256) void argreduce_tile_kernel(const T *__restrict
   }
 }
 
-constexpr int AR_TILE = 64, AR_PBK = 16, AR_PT = 4;
-
 template <typename T, int MAP, int RED, bool AT, bool BT>
 __global__ __launch_bounds__(256) void argreduce_kernel(const T *__restrict__ A, const T *__restrict__ B, T *__restrict__ C,
                                                         int *__restrict__ I, unsigned N, unsigned K, unsigned M,
                                                         size_t stride_a, size_t stride_b, size_t stride_c, int index_base,
                                                         int seeded) {
-  __shared__ T As[AR_PBK][AR_TILE + 1];  // [k][row], +1: column reads of a row-major source
-  __shared__ T Bs[AR_PBK][AR_TILE + (BT ? 1 : 0)];   // [k][col]; BT: +1, staged as a row-major A is
-  const unsigned tid = threadIdx.x;
-  const unsigned tx = tid % 16, ty = tid / 16;
-  // element e of the batch: XCD-remapped ids e * tiles .. (e + 1) * tiles - 1, row-major over its tile grid; uniform
-  const unsigned tiles_m = (M + AR_TILE - 1) / AR_TILE, tiles = tiles_m * ((N + AR_TILE - 1) / AR_TILE);
-  const unsigned lin = xcd_remap(blockIdx.x, gridDim.x), e = lin / tiles, t = lin - e * tiles;
-  A += e * stride_a;
-  B += e * stride_b;
-  C += e * stride_c;
-  I += e * stride_c;
-  const unsigned row0 = (t / tiles_m) * AR_TILE, col0 = (t % tiles_m) * AR_TILE;
+  __shared__ T As[kBK][kTile + 1];  // [k][row], +1: column reads of a row-major source
+  __shared__ T Bs[kBK][kTile + (BT ? 1 : 0)];   // [k][col]; BT: +1, staged as a row-major A is
+  const unsigned tx = threadIdx.x % 16, ty = threadIdx.x / 16;
+  unsigned row0, col0;
+  I += tile64_origin<Form::Batched>(A, B, C, N, M, stride_a, stride_b, stride_c, row0, col0) * stride_c;   // I moves with C
 
-  T acc[AR_PT][AR_PT];
-  int idx[AR_PT][AR_PT];
+  T acc[kPerThread][kPerThread];
+  int idx[kPerThread][kPerThread];
 #pragma unroll
-  for (int i = 0; i < AR_PT; ++i) {
-    const unsigned gr = row0 + ty * AR_PT + i;
+  for (int i = 0; i < kPerThread; ++i) {
+    const unsigned gr = row0 + ty * kPerThread + i;
 #pragma unroll
-    for (int j = 0; j < AR_PT; ++j) {
+    for (int j = 0; j < kPerThread; ++j) {
       const unsigned gc = col0 + tx + 16 * j;
       acc[i][j] = Op<RED, T>::identity();
       idx[i][j] = -1;
@@ -229,38 +222,22 @@ __global__ __launch_bounds__(256) void argreduce_kernel(const T *__restrict__ A,
     }
   }
 
-  for (unsigned k0 = 0; k0 < K; k0 += AR_PBK) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      unsigned r, kk;
-      if (AT) { r = tid % 64; kk = tid / 64 + 4 * i; }   // A is K x N: consecutive lanes along N
-      else    { kk = tid % 16; r = tid / 16 + 16 * i; }  // A is N x K: consecutive lanes along K
-      const unsigned gr = row0 + r, gk = k0 + kk;
-      T v = (T)0;
-      if (gr < N && gk < K) v = AT ? A[(size_t)gk * N + gr] : A[(size_t)gr * K + gk];
-      As[kk][r] = v;
-    }
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      unsigned c, kk;
-      if (BT) { kk = tid % 16; c = tid / 16 + 16 * i; }   // B is M x K: consecutive lanes along K
-      else    { c = tid % 64; kk = tid / 64 + 4 * i; }    // B is K x M: consecutive lanes along M
-      const unsigned gc = col0 + c, gk = k0 + kk;
-      Bs[kk][c] = (gc < M && gk < K) ? B[BT ? (size_t)gc * K + gk : (size_t)gk * M + gc] : (T)0;
-    }
+  for (unsigned k0 = 0; k0 < K; k0 += kBK) {
+    tile64_stage<!AT>(As, A, row0, N, k0, K);   // A is N x K, or (AT) K x N
+    tile64_stage<BT>(Bs, B, col0, M, k0, K);    // B is K x M, or (BT) M x K
     __syncthreads();
-    const unsigned kmax = (K - k0) < (unsigned)AR_PBK ? (K - k0) : (unsigned)AR_PBK;
+    const unsigned kmax = (K - k0) < (unsigned)kBK ? (K - k0) : (unsigned)kBK;
     for (unsigned kk = 0; kk < kmax; ++kk) {  // strictly ascending k
-      T av[AR_PT], bv[AR_PT];
+      T av[kPerThread], bv[kPerThread];
 #pragma unroll
-      for (int i = 0; i < AR_PT; ++i) av[i] = As[kk][ty * AR_PT + i];
+      for (int i = 0; i < kPerThread; ++i) av[i] = As[kk][ty * kPerThread + i];
 #pragma unroll
-      for (int j = 0; j < AR_PT; ++j) bv[j] = Bs[kk][tx + 16 * j];
+      for (int j = 0; j < kPerThread; ++j) bv[j] = Bs[kk][tx + 16 * j];
       const int kg = index_base + (int)(k0 + kk);
 #pragma unroll
-      for (int i = 0; i < AR_PT; ++i)
+      for (int i = 0; i < kPerThread; ++i)
 #pragma unroll
-        for (int j = 0; j < AR_PT; ++j) {
+        for (int j = 0; j < kPerThread; ++j) {
           const T s = Op<MAP, T>::apply(av[i], bv[j]);
           const bool tk = ar_takes<RED>(s, acc[i][j]);
           acc[i][j] = tk ? s : acc[i][j];
@@ -270,11 +247,11 @@ __global__ __launch_bounds__(256) void argreduce_kernel(const T *__restrict__ A,
     __syncthreads();
   }
 #pragma unroll
-  for (int i = 0; i < AR_PT; ++i) {
-    const unsigned gr = row0 + ty * AR_PT + i;
+  for (int i = 0; i < kPerThread; ++i) {
+    const unsigned gr = row0 + ty * kPerThread + i;
     if (gr >= N) continue;
 #pragma unroll
-    for (int j = 0; j < AR_PT; ++j) {
+    for (int j = 0; j < kPerThread; ++j) {
       const unsigned gc = col0 + tx + 16 * j;
       if (gc < M) {
         C[(size_t)gr * M + gc] = acc[i][j];
@@ -308,7 +285,7 @@ int ar_launch(hipStream_t s, const Problem &p, int *index, int index_base, bool 
       return (int)hipGetLastError();
     }
   }
-  const unsigned tiles = ((p.m + AR_TILE - 1) / AR_TILE) * ((p.n + AR_TILE - 1) / AR_TILE);
+  const unsigned tiles = ((p.m + kTile - 1) / kTile) * ((p.n + kTile - 1) / kTile);
   MM_AR_LAUNCH(argreduce_kernel, dim3(tiles * p.batch), (const T *)p.a, (const T *)p.b, (T *)p.c, index, p.n, p.k, p.m,
                p.stride_a, p.stride_b, p.stride_c, index_base, seeded);
   return (int)hipGetLastError();

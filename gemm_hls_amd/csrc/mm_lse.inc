@@ -11,13 +11,14 @@
 //     fallback (flags != null: a workgroup whose tile flag is clear exits at once) and what MM_PATH_ORDERED runs.
 //     BT ("lse_exact_nt", mm_gemm_logsumexp_nt_*): B is stored M x K row-major and staged as an N x K A is, into the same
 //     k-major Bs; the slabs, their order and every output's sequence are the row-major kernel's, so are the bits.
+//     The tile split and the staging are mm_tile64.h's, the staging with this kernel's load (sg * x in F) and A's -inf fill.
 //   * lse_rowmax_kernel / lse_colmax_kernel / lse_expand_kernel: the hybrid's prepass -- per-row (per-column) maxima of an
 //     operand, NaN-propagating, and E = exp(X - max) into a zero-padded row-major workspace matrix.
 //   * lse_epilogue_kernel: C = ra_i + rb_j + log S (S = EA @ EB from the matrix cores), combined with C's input by a stable
 //     log-add-exp when seeded; one flag per 64 x 64 tile, set when any output of the tile has S < tau (or NaN), a
 //     non-finite result, or `force`: such a tile leaves C untouched for the fallback.
 // No kernel here uses atomics, scratch or AGPRs; every store is a plain vector store.
-#include "mm_common.h"
+#include "mm_tile64.h"
 
 namespace mm {
 namespace {
@@ -83,7 +84,7 @@ template <typename T> __device__ __forceinline__ typename LseType<T>::F lse_load
   return (typename LseType<T>::F)*p;
 }
 
-constexpr int LSE_T = 64, LSE_BK = 16, LSE_SK = 4, LSE_PT = 4, LSE_APAD = 4;
+constexpr int LSE_SK = 4, LSE_APAD = 4;
 
 template <typename T, int RED, bool AT, bool BT>
 __global__ __launch_bounds__(256) void lse_exact_kernel(const T *__restrict__ A, const T *__restrict__ B, T *__restrict__ C,
@@ -94,27 +95,25 @@ __global__ __launch_bounds__(256) void lse_exact_kernel(const T *__restrict__ A,
   constexpr F sg = RED == MM_OP_MIN ? (F)-1 : (F)1;
   // terms per slab: 4 for f32; f64 takes 1 (its ocml exp2 is long, and 4 x 4 outputs of f64 slabs spilled to AGPRs)
   constexpr int SK = sizeof(F) == 4 ? LSE_SK : 1;
-  __shared__ __attribute__((aligned(16))) F As[LSE_BK][LSE_T + LSE_APAD];   // [k][row]; the pad spreads the transposing writes
-  __shared__ __attribute__((aligned(16))) F Bs[LSE_BK][LSE_T + (BT ? LSE_APAD : 0)];   // [k][col]; BT: padded as As is
-  const unsigned tid = threadIdx.x, tx = tid % 16, ty = tid / 16;
-  // element e of the batch: ids e * tiles .. (e + 1) * tiles - 1, row-major over its tile grid; uniform
-  const unsigned tiles_m = (M + LSE_T - 1) / LSE_T, tiles = tiles_m * ((N + LSE_T - 1) / LSE_T);
-  const unsigned lin = xcd_remap(blockIdx.x, gridDim.x), e = lin / tiles, t = lin - e * tiles;
-  if (flags && flags[lin] == 0) return;   // the hybrid's fallback: this tile's outputs are already in C
-  A += e * stride_a;
-  B += e * stride_b;
-  C += e * stride_c;
-  const unsigned row0 = (t / tiles_m) * LSE_T, col0 = (t % tiles_m) * LSE_T;
+  __shared__ __attribute__((aligned(16))) F As[kBK][kTile + LSE_APAD];   // [k][row]; the pad spreads the transposing writes
+  __shared__ __attribute__((aligned(16))) F Bs[kBK][kTile + (BT ? LSE_APAD : 0)];   // [k][col]; BT: padded as As is
+  const unsigned tx = threadIdx.x % 16, ty = threadIdx.x / 16;
+  const Tile64 w = tile64_split(N, M);
+  if (flags && flags[w.lin] == 0) return;   // the hybrid's fallback: this tile's outputs are already in C
+  A += w.e * stride_a;   // what tile64_origin does, after the flag
+  B += w.e * stride_b;
+  C += w.e * stride_c;
+  const unsigned row0 = w.row0(), col0 = w.col0();
 
-  F m[LSE_PT][LSE_PT], nm[LSE_PT][LSE_PT], s[LSE_PT][LSE_PT];
+  F m[kPerThread][kPerThread], nm[kPerThread][kPerThread], s[kPerThread][kPerThread];
 #pragma unroll
-  for (int i = 0; i < LSE_PT; ++i)
+  for (int i = 0; i < kPerThread; ++i)
 #pragma unroll
-    for (int j = 0; j < LSE_PT; ++j) {
+    for (int j = 0; j < kPerThread; ++j) {
       m[i][j] = lse_ninf<F>();
       nm[i][j] = X::kBig;
       s[i][j] = (F)0;
-      const unsigned gr = row0 + ty * LSE_PT + i, gc = col0 + tx + 16 * j;
+      const unsigned gr = row0 + ty * kPerThread + i, gc = col0 + tx + 16 * j;
       if (seeded && gr < N && gc < M) {   // C's input value is one more term
         const F c = sg * lse_load(C + (size_t)gr * M + gc);
         lse_raise(c, m[i][j], nm[i][j], s[i][j]);
@@ -122,41 +121,26 @@ __global__ __launch_bounds__(256) void lse_exact_kernel(const T *__restrict__ A,
       }
     }
 
-  for (unsigned k0 = 0; k0 < K; k0 += LSE_BK) {
-    // k beyond K: A = -inf, B = 0, so the padded terms are -inf and add exactly nothing
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      unsigned r, kk;
-      if (AT) { r = tid % 64; kk = tid / 64 + 4 * i; }   // A is K x N: consecutive lanes along N
-      else    { kk = tid % 16; r = tid / 16 + 16 * i; }  // A is N x K: consecutive lanes along K
-      const unsigned gr = row0 + r, gk = k0 + kk;
-      F v = lse_ninf<F>();
-      if (gk < K) v = gr < N ? sg * lse_load(AT ? A + (size_t)gk * N + gr : A + (size_t)gr * K + gk) : (F)0;
-      As[kk][r] = v;
-    }
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      unsigned c, kk;
-      if (BT) { kk = tid % 16; c = tid / 16 + 16 * i; }   // B is M x K: consecutive lanes along K
-      else    { c = tid % 64; kk = tid / 64 + 4 * i; }    // B is K x M: consecutive lanes along M
-      const unsigned gc = col0 + c, gk = k0 + kk;
-      Bs[kk][c] = (gc < M && gk < K) ? sg * lse_load(B + (BT ? (size_t)gc * K + gk : (size_t)gk * M + gc)) : (F)0;
-    }
+  for (unsigned k0 = 0; k0 < K; k0 += kBK) {
+    // sg * x in F; k beyond K: A = -inf, B = 0, so the padded terms are -inf and add exactly nothing
+    const auto load = [](const T *p) { return sg * lse_load(p); };
+    tile64_stage<!AT>(As, A, row0, N, k0, K, load, lse_ninf<F>());   // A is N x K, or (AT) K x N
+    tile64_stage<BT>(Bs, B, col0, M, k0, K, load);                   // B is K x M, or (BT) M x K
     __syncthreads();
 #pragma unroll 1
-    for (int kk = 0; kk < LSE_BK; kk += SK) {
-      F av[SK][LSE_PT], bv[SK][LSE_PT];
+    for (int kk = 0; kk < kBK; kk += SK) {
+      F av[SK][kPerThread], bv[SK][kPerThread];
 #pragma unroll
       for (int q = 0; q < SK; ++q) {
 #pragma unroll
-        for (int i = 0; i < LSE_PT; ++i) av[q][i] = As[kk + q][ty * LSE_PT + i];
+        for (int i = 0; i < kPerThread; ++i) av[q][i] = As[kk + q][ty * kPerThread + i];
 #pragma unroll
-        for (int j = 0; j < LSE_PT; ++j) bv[q][j] = Bs[kk + q][tx + 16 * j];
+        for (int j = 0; j < kPerThread; ++j) bv[q][j] = Bs[kk + q][tx + 16 * j];
       }
 #pragma unroll
-      for (int i = 0; i < LSE_PT; ++i)
+      for (int i = 0; i < kPerThread; ++i)
 #pragma unroll
-        for (int j = 0; j < LSE_PT; ++j) {
+        for (int j = 0; j < kPerThread; ++j) {
           F tv[SK];
 #pragma unroll
           for (int q = 0; q < SK; ++q) tv[q] = av[q][i] + bv[q][j];
@@ -173,11 +157,11 @@ __global__ __launch_bounds__(256) void lse_exact_kernel(const T *__restrict__ A,
     __syncthreads();
   }
 #pragma unroll
-  for (int i = 0; i < LSE_PT; ++i) {
-    const unsigned gr = row0 + ty * LSE_PT + i;
+  for (int i = 0; i < kPerThread; ++i) {
+    const unsigned gr = row0 + ty * kPerThread + i;
     if (gr >= N) continue;
 #pragma unroll
-    for (int j = 0; j < LSE_PT; ++j) {
+    for (int j = 0; j < kPerThread; ++j) {
       const unsigned gc = col0 + tx + 16 * j;
       if (gc < M) C[(size_t)gr * M + gc] = (T)(sg * lse_finish(m[i][j], s[i][j]));
     }
@@ -275,20 +259,20 @@ __global__ __launch_bounds__(256) void lse_epilogue_kernel(const typename LseTyp
   using X = LseMath<F>;
   constexpr F sg = RED == MM_OP_MIN ? (F)-1 : (F)1;
   const unsigned tid = threadIdx.x, tx = tid % 16, ty = tid / 16;
-  const unsigned tiles_m = (M + LSE_T - 1) / LSE_T, tiles = tiles_m * ((N + LSE_T - 1) / LSE_T);
+  const unsigned tiles_m = (M + kTile - 1) / kTile, tiles = tiles_m * ((N + kTile - 1) / kTile);
   const unsigned lin = blockIdx.x, e = lin / tiles, t = lin - e * tiles;
-  const unsigned row0 = (t / tiles_m) * LSE_T, col0 = (t % tiles_m) * LSE_T;
+  const unsigned row0 = (t / tiles_m) * kTile, col0 = (t % tiles_m) * kTile;
   S += e * stride_s;
   RA += e * stride_ra;
   RB += e * stride_rb;
   C += e * stride_c;
-  F out[LSE_PT][LSE_PT];
+  F out[kPerThread][kPerThread];
   int bad = 0;
 #pragma unroll
-  for (int i = 0; i < LSE_PT; ++i) {
-    const unsigned gr = row0 + ty * LSE_PT + i;
+  for (int i = 0; i < kPerThread; ++i) {
+    const unsigned gr = row0 + ty * kPerThread + i;
 #pragma unroll
-    for (int j = 0; j < LSE_PT; ++j) {
+    for (int j = 0; j < kPerThread; ++j) {
       const unsigned gc = col0 + tx + 16 * j;
       out[i][j] = (F)0;
       if (gr < N && gc < M) {
@@ -309,11 +293,11 @@ __global__ __launch_bounds__(256) void lse_epilogue_kernel(const typename LseTyp
   if (tid == 0) flags[lin] = flag ? 1 : 0;
   if (flag) return;
 #pragma unroll
-  for (int i = 0; i < LSE_PT; ++i) {
-    const unsigned gr = row0 + ty * LSE_PT + i;
+  for (int i = 0; i < kPerThread; ++i) {
+    const unsigned gr = row0 + ty * kPerThread + i;
     if (gr >= N) continue;
 #pragma unroll
-    for (int j = 0; j < LSE_PT; ++j) {
+    for (int j = 0; j < kPerThread; ++j) {
       const unsigned gc = col0 + tx + 16 * j;
       if (gc < M) C[(size_t)gr * M + gc] = (T)out[i][j];
     }
@@ -323,7 +307,7 @@ __global__ __launch_bounds__(256) void lse_epilogue_kernel(const typename LseTyp
 // ---- host side, shared by the units that hold these kernels (mm_lse_fp.hip; mm_lse_nt_fp.hip for an M x K B) -----------
 template <typename T, int RED, bool AT, bool BT>
 int lse_exact_launch(hipStream_t s, const Problem &p, const int *flags) {
-  const unsigned tiles = ((p.m + LSE_T - 1) / LSE_T) * ((p.n + LSE_T - 1) / LSE_T);
+  const unsigned tiles = ((p.m + kTile - 1) / kTile) * ((p.n + kTile - 1) / kTile);
   hipLaunchKernelGGL((lse_exact_kernel<T, RED, AT, BT>), dim3(tiles * p.batch), dim3(256), 0, s, (const T *)p.a,
                      (const T *)p.b, (T *)p.c, p.n, p.k, p.m, p.stride_a, p.stride_b, p.stride_c, p.seed ? 1 : 0, flags);
   return (int)hipGetLastError();

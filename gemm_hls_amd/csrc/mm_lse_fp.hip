@@ -24,7 +24,7 @@ int lse_epilogue_launch(hipStream_t s, const LseEpilogue &ep) {
   using F = typename LseType<T>::F;
   // S below tau: the terms that underflowed in the prepass (each below 2^-126 resp. 2^-1022 absolute) may matter
   const F tau = sizeof(F) == 4 ? (F)0x1p-64 : (F)0x1p-512;
-  const unsigned tiles = ((ep.m + LSE_T - 1) / LSE_T) * ((ep.n + LSE_T - 1) / LSE_T);
+  const unsigned tiles = ((ep.m + kTile - 1) / kTile) * ((ep.n + kTile - 1) / kTile);
   hipLaunchKernelGGL((lse_epilogue_kernel<T, RED>), dim3(tiles * ep.batch), dim3(256), 0, s, (const F *)ep.s,
                      (const F *)ep.ra, (const F *)ep.rb, (T *)ep.c, ep.flags, ep.n, ep.m, ep.m_p, ep.stride_s, ep.stride_ra,
                      ep.stride_rb, ep.stride_c, tau, ep.seed ? 1 : 0, ep.force ? 1 : 0);

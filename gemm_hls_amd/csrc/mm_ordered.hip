@@ -5,15 +5,12 @@
 // is compiled with -ffp-contract=off), binary16 accumulating in binary16.  Bit-identical to the
 // reference for every dtype and every (map, reduce); fully predicated, any N, K, M.
 // LDS-tiled (64 x 64 outputs per 256-thread workgroup, 4 x 4 per thread) so that it is usable
-// for verification at real sizes, but it is the parity anchor, not the fast path.
-#include "mm_common.h"
+// for verification at real sizes, but it is the parity anchor, not the fast path.  The geometry constants and where the
+// tile lies are mm_tile64.h's, shared with the other four kernels of this organisation.
+#include "mm_tile64.h"
 
 namespace mm {
 namespace {
-
-constexpr int kTile = 64;   // outputs per workgroup edge
-constexpr int kBK = 16;     // k-slab staged through LDS
-constexpr int kPerThread = 4;
 
 // ACC is the accumulator type: T itself for the Naive contract; float for the one exception,
 // half (Multiply, Add) under MM_PATH_AUTO on shapes the matrix-core kernel does not take
@@ -31,18 +28,7 @@ __global__ __launch_bounds__(256) void ordered_kernel(const T *__restrict__ A, c
   const unsigned tid = threadIdx.x;
   const unsigned tx = tid % 16, ty = tid / 16;
   unsigned row0, col0;
-  if constexpr (F == Form::Single) {   // a 2-D grid of tiles
-    row0 = blockIdx.y * kTile, col0 = blockIdx.x * kTile;
-  } else {
-    // element e of the batch: XCD-remapped ids e * tiles .. (e + 1) * tiles - 1 (one element's tiles stay on one XCD),
-    // row-major over its tile grid; uniform, SGPRs
-    const unsigned tiles_m = (M + kTile - 1) / kTile, tiles = tiles_m * ((N + kTile - 1) / kTile);
-    const unsigned lin = xcd_remap(blockIdx.x, gridDim.x), e = lin / tiles, t = lin - e * tiles;
-    A += e * stride_a;
-    B += e * stride_b;
-    C += e * stride_c;
-    row0 = (t / tiles_m) * kTile, col0 = (t % tiles_m) * kTile;
-  }
+  tile64_origin<F>(A, B, C, N, M, stride_a, stride_b, stride_c, row0, col0);
 
   ACC acc[kPerThread][kPerThread];
 #pragma unroll
@@ -64,7 +50,7 @@ __global__ __launch_bounds__(256) void ordered_kernel(const T *__restrict__ A, c
   }
 
   for (unsigned k0 = 0; k0 < K; k0 += kBK) {
-    // stage A: 64 rows x 16 k
+    // stage A: 64 rows x 16 k (this kernel's own loops, not tile64_stage: DESIGN.md 3.13)
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       unsigned r, kk;

@@ -4,16 +4,12 @@
 // one accumulator, k ascending, multiply and add two separately rounded operations (this file is compiled with
 // -ffp-contract=off): Naive (include/Utility.h:18-42) on the transposed operand, bit for bit, for every dtype and every
 // (map, reduce); any N, K, M, any element-aligned pointer or stride.
-// Written beside mm_ordered.hip, not shared with it: that kernel's B staging is [k][col] from rows of B, this one's is A's
-// N x K branch twice, and a flag threaded through the shared body would change what mm_ordered.hip compiles to.
-#include "mm_common.h"
+// A kernel of its own beside mm_ordered.hip's (a flag threaded through that body would change what mm_ordered.hip compiles
+// to); the geometry constants and the tile origin are mm_tile64.h's, the staging -- the k-contiguous mapping for A and Bt -- is here.
+#include "mm_tile64.h"
 
 namespace mm {
 namespace {
-
-constexpr int kTile = 64;   // outputs per workgroup edge
-constexpr int kBK = 16;     // k-slab staged through LDS
-constexpr int kPerThread = 4;
 
 // ACC: T for the Naive contract; float for half (Multiply, Add) under MM_PATH_AUTO where no matrix-core kernel serves (exact
 // products, f32 accumulation, ONE rounding to binary16 on store: mfma_f16's contract, as "ordered_wide_f16" keeps it in the
@@ -27,13 +23,8 @@ __global__ __launch_bounds__(256) void ordered_nt_kernel(const T *__restrict__ A
   __shared__ T Bs[kBK][kTile + 1];  // [k][col], +1: Bt is row-major in (col, k), staged as A is
   const unsigned tid = threadIdx.x;
   const unsigned tx = tid % 16, ty = tid / 16;
-  // element e of the batch: XCD-remapped ids e * tiles .. (e + 1) * tiles - 1, row-major over its tile grid; uniform
-  const unsigned tiles_m = (M + kTile - 1) / kTile, tiles = tiles_m * ((N + kTile - 1) / kTile);
-  const unsigned lin = xcd_remap(blockIdx.x, gridDim.x), e = lin / tiles, t = lin - e * tiles;
-  A += e * stride_a;
-  Bt += e * stride_b;
-  C += e * stride_c;
-  const unsigned row0 = (t / tiles_m) * kTile, col0 = (t % tiles_m) * kTile;
+  unsigned row0, col0;
+  tile64_origin<F>(A, Bt, C, N, M, stride_a, stride_b, stride_c, row0, col0);
 
   ACC acc[kPerThread][kPerThread];
 #pragma unroll
@@ -54,7 +45,7 @@ __global__ __launch_bounds__(256) void ordered_nt_kernel(const T *__restrict__ A
   }
 
   for (unsigned k0 = 0; k0 < K; k0 += kBK) {
-    // stage A (64 rows x 16 k) and Bt (64 cols x 16 k): consecutive lanes along k
+    // stage A (64 rows x 16 k) and Bt (64 cols x 16 k), lanes along k (this kernel's own loop, not tile64_stage: DESIGN.md 3.13)
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       const unsigned kk = tid % 16, r = tid / 16 + 16 * i;

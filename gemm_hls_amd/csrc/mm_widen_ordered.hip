@@ -9,15 +9,14 @@
 // in blocks -- 16 k into a partial sum, 64 partial sums into a middle one, the middle ones into the accumulator -- so that the
 // longest chain of additions is 16 + 64 + K / 1024 instead of K and the result keeps the matrix-core kernels' bound of
 // 1e-6 (|C_in| + |A||B|), which one accumulator over K terms does not (1.02e-6 measured at K = 512, growing with K).
-// Organisation of mm_ordered.hip's kernel: 64 x 64 outputs per 256-thread workgroup through LDS, 4 x 4 per thread.
-#include "mm_common.h"
+// Organisation of mm_ordered.hip's kernel: 64 x 64 outputs per 256-thread workgroup through LDS, 4 x 4 per thread; the
+// geometry constants and the tile origin are mm_tile64.h's.
+#include "mm_tile64.h"
 
 #pragma clang fp contract(off)
 
 namespace mm {
 namespace {
-
-constexpr int kTile = 64, kBK = 16, kPerThread = 4;
 
 __device__ __forceinline__ int widen_mac(int acc, signed char a, signed char b) { return (int)((unsigned)acc + (unsigned)((int)a * (int)b)); }
 __device__ __forceinline__ float widen_mac(float acc, _Float16 a, _Float16 b) { return acc + (float)a * (float)b; }
@@ -33,16 +32,7 @@ __global__ __launch_bounds__(256) void widen_ordered_kernel(const T *__restrict_
   const unsigned tid = threadIdx.x;
   const unsigned tx = tid % 16, ty = tid / 16;
   unsigned row0, col0;
-  if constexpr (F == Form::Single) {
-    row0 = blockIdx.y * kTile, col0 = blockIdx.x * kTile;
-  } else {
-    const unsigned tiles_m = (M + kTile - 1) / kTile, tiles = tiles_m * ((N + kTile - 1) / kTile);
-    const unsigned lin = xcd_remap(blockIdx.x, gridDim.x), e = lin / tiles, t = lin - e * tiles;
-    A += e * stride_a;
-    B += e * stride_b;
-    C += e * stride_c;
-    row0 = (t / tiles_m) * kTile, col0 = (t % tiles_m) * kTile;
-  }
+  tile64_origin<F>(A, B, C, N, M, stride_a, stride_b, stride_c, row0, col0);
 
   W acc[kPerThread][kPerThread];
 #pragma unroll
@@ -64,8 +54,9 @@ __global__ __launch_bounds__(256) void widen_ordered_kernel(const T *__restrict_
       for (int j = 0; j < kPerThread; ++j) mid[i][j] = (W)0;
   }
   for (unsigned k0 = 0; k0 < K; k0 += kBK) {
+    // stage A: 64 rows x 16 k (this kernel's own loops, not tile64_stage: DESIGN.md 3.13)
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {   // stage A: 64 rows x 16 k
+    for (int i = 0; i < 4; ++i) {
       unsigned r, kk;
       if (AT) { r = tid % 64; kk = tid / 64 + 4 * i; }   // A is K x N: consecutive lanes along N
       else    { kk = tid % 16; r = tid / 16 + 16 * i; }  // A is N x K: consecutive lanes along K
@@ -74,8 +65,9 @@ __global__ __launch_bounds__(256) void widen_ordered_kernel(const T *__restrict_
       if (gr < N && gk < K) v = AT ? A[(size_t)gk * N + gr] : A[(size_t)gr * K + gk];
       As[kk][r] = v;
     }
+    // stage B: 16 k x 64 cols
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {   // stage B: 16 k x 64 cols
+    for (int i = 0; i < 4; ++i) {
       const unsigned c = tid % 64, kk = tid / 64 + 4 * i;
       const unsigned gc = col0 + c, gk = k0 + kk;
       Bs[kk][c] = (gc < M && gk < K) ? B[(size_t)gk * M + gc] : (T)0;

@@ -165,6 +165,9 @@ def test_auto_every_config(dtype, mp, rd):
 # ---- 3. every batched family by name, ragged N (and M where the family allows it), guarded C ---------------------------
 FAMILIES = [  # (dtype, map, reduce, path, (n, k, m), transposed_a, knob, value, expected name prefix)
     ("float", "Add", "Min", g.PATH_ORDERED, (33, 17, 29), False, None, None, "ordered"),
+    # two tiles each way, a one-line last tile, a one-k last slab: both stagings of the 64 x 64 kernel's seeded form
+    ("float", "Add", "Min", g.PATH_ORDERED, (65, 17, 67), False, None, None, "ordered"),
+    ("int", "Multiply", "Add", g.PATH_ORDERED, (65, 17, 67), True, None, None, "ordered"),
     ("float", "Add", "Min", g.PATH_ORDERED, (130, 128, 136), False, None, None, "ordered_tile"),
     ("half", "Multiply", "Add", g.PATH_AUTO, (130, 128, 132), False, None, None, "ordered_wide_f16"),
     ("int", "Add", "Min", g.PATH_AUTO, (130, 128, 136), False, None, None, "valu_tile"),              # DMA-staged

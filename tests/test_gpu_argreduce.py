@@ -109,7 +109,9 @@ def check(got_c, got_i, want_c, want_i, what):
     assert np.array_equal(got_i, want_i), (what, "indices", sr.first_difference(got_i, want_i))
 
 
-SHAPES = [(200, 68, 132, False), (67, 37, 61, False), (132, 36, 72, True)]   # tiled ragged, unserved, K x N A
+# tiled ragged, unserved, K x N A, and the 64 x 64 kernel's edge in both A layouts: two tiles each way, a one-line last tile, a
+# one-k last slab
+SHAPES = [(200, 68, 132, False), (67, 37, 61, False), (132, 36, 72, True), (65, 17, 67, False), (65, 17, 67, True)]
 
 
 @pytest.mark.parametrize("dtype,mp,rd", ARG_CONFIGS, ids=["-".join(c) for c in ARG_CONFIGS])

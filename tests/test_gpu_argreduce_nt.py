@@ -17,6 +17,7 @@ pytestmark = pytest.mark.gpu
 
 GUARD = ar.GUARD
 TILED, PLAIN = (200, 68, 132), (67, 37, 61)   # 68 = 4 slabs of 16 + a last slab of 4; 200 and 132 leave ragged tile edges
+EDGE = (65, 17, 67)   # the 64 x 64 kernel: two tiles each way, a one-line last tile, a one-k last slab
 
 
 def launch(cfg, a, b, n, k, m, batch=1, sa=0, sb=0, sc=None, c0=None, i0=None, index_base=0, a_offset=0, nt=True):
@@ -51,7 +52,7 @@ def operands_nt(dtype, mp, rd, n, k, m, rng):
 @pytest.mark.parametrize("dtype,mp,rd", ar.ARG_CONFIGS, ids=["-".join(c) for c in ar.ARG_CONFIGS])
 def test_argreduce_nt_every_config_both_paths(dtype, mp, rd):
     rng = np.random.default_rng(zlib.crc32(f"nt/{dtype}/{mp}/{rd}".encode()))
-    for n, k, m in (TILED, PLAIN):
+    for n, k, m in (TILED, PLAIN, EDGE):
         a, bt, b = operands_nt(dtype, mp, rd, n, k, m, rng)
         want_c, want_i = ar.oracle(dtype, mp, rd, a, b)
         if (n, k, m) == TILED and (mp, rd) != ("And", "Max"):
@@ -75,6 +76,7 @@ def test_argreduce_nt_serving_rule_on_the_tested_shapes():
         tile = np.dtype(sr.NP_DTYPES[dtype]).itemsize <= 4 and mp != "And"
         assert g.kernel_name_argreduce_nt(g.make_config(dtype, mp, rd), *TILED) == ("argreduce_tile_nt" if tile else "argreduce_nt")
         assert g.kernel_name_argreduce_nt(g.make_config(dtype, mp, rd), *PLAIN) == "argreduce_nt"
+        assert g.kernel_name_argreduce_nt(g.make_config(dtype, mp, rd), *EDGE) == "argreduce_nt"
         assert g.kernel_name_argreduce_nt(g.make_config(dtype, mp, rd, g.PATH_ORDERED), *TILED) == "argreduce_nt"
 
 

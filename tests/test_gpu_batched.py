@@ -59,15 +59,17 @@ def element(flat, e, stride, rows, cols):
 @pytest.mark.parametrize("mp", ALL_OPS)
 @pytest.mark.parametrize("rd", ALL_OPS)
 def test_batched_ordered_every_config_matches_naive(dtype, mp, rd):
-    n, k, m, batch = 33, 17, 29, 3
     rng = np.random.default_rng(zlib.crc32(f"{dtype}/{mp}/{rd}".encode()))
-    a, b = stack(dtype, batch, n, k, rng), stack(dtype, batch, k, m, rng)
-    cfg = g.make_config(dtype, mp, rd, g.PATH_ORDERED)
-    c = batched_launch(cfg, a.ravel(), b.ravel(), n, k, m, batch, n * k, k * m, n * m)
-    for e in range(batch):
-        want = _oracle.naive(dtype, mp, rd, a[e], b[e])
-        got = element(c, e, n * m, n, m)
-        assert sr.same_bits(got, want), (e, sr.first_difference(got, want))
+    # a row-major A on one ragged tile; a K x N A on two tiles each way with a one-line last tile and a one-k last slab
+    for n, k, m, batch, ta in [(33, 17, 29, 3, False), (65, 17, 67, 2, True)]:
+        a, b = stack(dtype, batch, k if ta else n, n if ta else k, rng), stack(dtype, batch, k, m, rng)
+        cfg = g.make_config(dtype, mp, rd, g.PATH_ORDERED, ta)
+        assert g.kernel_name_batched(cfg, n, k, m, batch) == "ordered"
+        c = batched_launch(cfg, a.ravel(), b.ravel(), n, k, m, batch, n * k, k * m, n * m)
+        for e in range(batch):
+            want = _oracle.naive(dtype, mp, rd, a[e], b[e], transposed_a=ta)
+            got = element(c, e, n * m, n, m)
+            assert sr.same_bits(got, want), (e, ta, sr.first_difference(got, want))
 
 
 # ---- MM_PATH_AUTO, exact configurations: every element the single launch's bits ---------------------------------------

@@ -66,11 +66,15 @@ def test_lse_configs_against_reference(dtype, red, path):
         c = _run(a, b, dtype, red, path)
         _lse_ref.check(c, _lse_ref.logsumexp_ref(a, b, dtype, red), a, b, dtype, red, what=f"{(n, k, m)}")
     # the K x N A, and special values
-    n, k, m = 300, 64, 272
-    a = rng.uniform(-8, 8, size=(k, n)).astype(NP[dtype])
-    b = rng.uniform(-8, 8, size=(k, m)).astype(NP[dtype])
-    c = _run(a, b, dtype, red, path, transposed=True)
-    _lse_ref.check(c, _lse_ref.logsumexp_ref(a, b, dtype, red, transposed_a=True), a, b, dtype, red, True, "K x N A")
+    # (the first shape: two tiles each way, a one-line last tile, a one-k last slab whose other 15 k are the staging's fill)
+    for n, k, m in [(65, 17, 67), (300, 64, 272)]:
+        a = rng.uniform(-8, 8, size=(k, n)).astype(NP[dtype])
+        b = rng.uniform(-8, 8, size=(k, m)).astype(NP[dtype])
+        c = _run(a, b, dtype, red, path, transposed=True)
+        _lse_ref.check(c, _lse_ref.logsumexp_ref(a, b, dtype, red, transposed_a=True), a, b, dtype, red, True, f"K x N A {(n, k, m)}")
+        seed = rng.uniform(-8, 8, size=(n, m)).astype(NP[dtype])
+        c = _run(a, b, dtype, red, path, transposed=True, seed=seed)
+        _lse_ref.check(c, _lse_ref.logsumexp_ref(a, b, dtype, red, seed, True), a, b, dtype, red, True, f"K x N A seeded {(n, k, m)}")
     a = rng.uniform(-8, 8, size=(n, k)).astype(NP[dtype])
     a[3, 5] = np.nan
     a[7, :] = -np.inf

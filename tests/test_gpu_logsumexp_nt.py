@@ -57,7 +57,7 @@ def _same_numbers(x, y):
     return np.array_equal(np.isnan(x), np.isnan(y)) and np.array_equal(x[~np.isnan(x)], y[~np.isnan(y)])
 
 
-SHAPES = [(1, 1, 1), (300, 64, 272), (65, 129, 63), (37, 4099, 5)]
+SHAPES = [(1, 1, 1), (300, 64, 272), (65, 129, 63), (37, 4099, 5), (65, 17, 67)]
 
 
 @pytest.mark.parametrize("path", [g.PATH_AUTO, g.PATH_ORDERED], ids=["auto", "ordered"])

@@ -56,23 +56,24 @@ def _rng(*key):
 # ---- 1. ordered_nt: all 275 configurations, Naive's bits on the transposed operand, plain and seeded -----------------------
 @pytest.mark.parametrize("dtype,mp,rd", sr.CONFIGS, ids=lambda x: str(x))
 def test_nt_ordered_every_config_is_naive_on_the_transposed_operand(dtype, mp, rd):
-    n, k, m = 37, 19, 41
     rng = _rng(dtype, mp, rd)
-    a, bt = operands(dtype, mp, rd, n, k, m, rng)
-    cfg = g.make_config(dtype, mp, rd, g.PATH_ORDERED)
-    assert g.kernel_name_nt(cfg, n, k, m) == "ordered_nt"
-    want = sr.reference(dtype, mp, rd, a, bt.T)
-    sr.assert_not_degenerate(want, mp, rd, f"{dtype} ({mp}, {rd})")
-    got = run_nt(cfg, a, bt, n, k, m).reshape(n, m)
-    assert sr.same_bits(got, want), sr.first_difference(got, want)
-    c0 = seeds(dtype, (n, m), rng)
-    want = seeded_reference(dtype, mp, rd, a, bt.T, c0)
-    # (a seeded chain starts at an arbitrary value, so assert_not_degenerate's {0, 1} does not apply: the reference must take
-    # several values -- two where an And leaves only 0 and 1 to an unsigned Min -- and must not be the seed itself)
-    values = np.unique(want[~np.isnan(want)] if sr.is_float(dtype) else want).size
-    assert values >= (2 if sr.binary_result(mp, rd) else 3) and not sr.same_bits(want, c0), f"degenerate seeded reference for {dtype} ({mp}, {rd})"
-    got = run_nt(cfg, a, bt, n, k, m, c0=c0).reshape(n, m)
-    assert sr.same_bits(got, want), sr.first_difference(got, want)
+    # one ragged tile; then two tiles each way with a one-line last tile and a one-k last slab
+    for n, k, m in [(37, 19, 41), (65, 17, 67)]:
+        a, bt = operands(dtype, mp, rd, n, k, m, rng)
+        cfg = g.make_config(dtype, mp, rd, g.PATH_ORDERED)
+        assert g.kernel_name_nt(cfg, n, k, m) == "ordered_nt"
+        want = sr.reference(dtype, mp, rd, a, bt.T)
+        sr.assert_not_degenerate(want, mp, rd, f"{dtype} ({mp}, {rd})")
+        got = run_nt(cfg, a, bt, n, k, m).reshape(n, m)
+        assert sr.same_bits(got, want), sr.first_difference(got, want)
+        c0 = seeds(dtype, (n, m), rng)
+        want = seeded_reference(dtype, mp, rd, a, bt.T, c0)
+        # (a seeded chain starts at an arbitrary value, so assert_not_degenerate's {0, 1} does not apply: the reference must take
+        # several values -- two where an And leaves only 0 and 1 to an unsigned Min -- and must not be the seed itself)
+        values = np.unique(want[~np.isnan(want)] if sr.is_float(dtype) else want).size
+        assert values >= (2 if sr.binary_result(mp, rd) else 3) and not sr.same_bits(want, c0), f"degenerate seeded reference for {dtype} ({mp}, {rd})"
+        got = run_nt(cfg, a, bt, n, k, m, c0=c0).reshape(n, m)
+        assert sr.same_bits(got, want), sr.first_difference(got, want)
 
 
 # ---- 2. valu_tile_nt: one type per element size and two more, ragged tiles, the shifted last slab -----------------------------

@@ -766,10 +766,12 @@ def test_ordered_path_reference_ctest_shape_float():
 
 
 def test_ordered_transposed_a_layout():
-    n, k, m = 70, 48, 96
-    a, b = _oracle.fill("int", n, k, m)
-    c, _ = g.matmul_capi(np.ascontiguousarray(a.T), b, "int", path=g.PATH_ORDERED, transposed_a=True)
-    assert np.array_equal(c, _oracle.naive("int", "Multiply", "Add", a, b))
+    # the second shape: two tiles each way, a one-line last tile and a one-k last slab, on the 64 x 64 kernel's K x N staging
+    for n, k, m in [(70, 48, 96), (65, 17, 67)]:
+        assert g.kernel_name(g.make_config("int", path=g.PATH_ORDERED, transposed_a=True), n, k, m) == "ordered"
+        a, b = _oracle.fill("int", n, k, m)
+        c, _ = g.matmul_capi(np.ascontiguousarray(a.T), b, "int", path=g.PATH_ORDERED, transposed_a=True)
+        assert np.array_equal(c, _oracle.naive("int", "Multiply", "Add", a, b))
 
 
 AUTO_EXACT_CASES = [("float", "Add", "Min"), ("float", "Add", "Max"), ("int", "Multiply", "Add"),

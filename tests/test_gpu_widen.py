@@ -160,6 +160,22 @@ def test_widen_every_kernel_plain_and_seeded(dtype, pin, transposed, shape, kern
                     ).astype(np.float32)
             assert _bits_equal(_run(dtype, a, b, g.PATH_ORDERED, transposed, seed), _f32_loop(a, b, seed)), what + " ordered seeded"
             _check_bound(what + " seeded", _run(dtype, a, b, g.PATH_AUTO, transposed, seed), a, b, seed)
+    if kernel == "widen_ordered":
+        # the fallback's batched form in this A layout, plain and seeded: two elements of two tiles each way with a one-line
+        # last tile and a one-k last slab
+        n, k, m = 65, 17, 67
+        kind = "full" if dtype == "int8_t" else "wide"
+        a, b = _operands(dtype, (2, n, k), kind, rng), _operands(dtype, (2, k, m), kind, rng)
+        seed = rng.integers(-2 ** 31, 2 ** 31, (2, n, m), dtype=np.int64).astype(np.int32) if dtype == "int8_t" else (
+            rng.standard_normal((2, n, m)) * 1e4).astype(np.float32)
+        at = torch.from_numpy(np.ascontiguousarray(a.transpose(0, 2, 1) if transposed else a)).to(dev)
+        bt = torch.from_numpy(b).to(dev)
+        plain = g.matmul_wide(at, bt, dtype, g.PATH_ORDERED, transposed).cpu().numpy()
+        seeded = g.addmm_wide_(torch.from_numpy(seed.copy()).to(dev), at, bt, dtype, g.PATH_ORDERED, transposed).cpu().numpy()
+        for e in range(2):
+            ref = _int_ref if dtype == "int8_t" else _f32_loop
+            assert _bits_equal(plain[e], ref(a[e], b[e])), f"batched {e}"
+            assert _bits_equal(seeded[e], ref(a[e], b[e], seed[e])), f"batched seeded {e}"
 
 
 @pytest.mark.parametrize("dtype,shape", [("half", (130, 256, 264)), ("half", (70, 48, 72)), ("half", (33, 40, 20)),
@@ -297,6 +313,16 @@ def test_widen_misaligned_operands_run_on_the_fallback_silently(dtype, k):
         _check_bound(f"misaligned K = {k}", c.cpu().numpy(), a, b)
         seed = c.cpu().numpy()
         _check_bound(f"misaligned K = {k} seeded", g.addmm_wide_(c, at, bt, dtype).cpu().numpy(), a, b, seed)
+        # the same demotion with a K x N A, the blocked fallback's other staging of A (N = 136 names a matrix-core kernel).
+        # No partial last k-slab here: a matrix-core kernel is only named for K % 16 == 0, so the blocked form never sees one; the
+        # k tail of this staging is checked bit for bit on the unblocked K x N cases (K = 37, 33 in CASES, K = 17 batched)
+        n = 136
+        assert g.kernel_name_widen(g.make_config(dtype, transposed_a=True), n, k, m).startswith("mfma_")
+        a = _operands(dtype, (n, k), kind, rng)
+        abuf = torch.zeros(n * k + 1, dtype=at.dtype, device=dev)
+        a1 = abuf[1:].view(k, n)
+        a1.copy_(torch.from_numpy(np.ascontiguousarray(a.T)).to(dev))
+        _check_bound(f"misaligned K x N A, K = {k}", g.matmul_wide(a1, bt, dtype, transposed_a=True).cpu().numpy(), a, b)
     assert buf[0].item() == 0                            # the element in front of C is untouched
 
 

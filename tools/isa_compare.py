@@ -10,7 +10,9 @@ Without --same-naming, OLD_TREE names a kernel's form in its symbol (`*_batched`
 (`(mm::Form)N`; mfma_f32_batched_kernel: a trailing `bool SEED`).  Kernels are paired by (base name, form, the remaining
 template arguments).  A pair is identical when the instruction streams are equal line for line -- comments, assembler
 directives and blank lines dropped, local labels (.LBB<n>_<m>) renumbered in order of appearance -- and the .amdhsa_
-resource lines are equal (registers, LDS, private segment, user SGPRs).  Only .amdhsa_kernarg_size of a Form::Single
+resource lines are equal (registers, LDS, private segment, user SGPRs).  A differing pair's line also says whether the
+instruction count, the opcode multiset (first token of each line) and the .amdhsa_ lines are equal; a pair with all three
+equal is counted as "reordered" in its unit's line.  Only .amdhsa_kernarg_size of a Form::Single
 kernel may differ: it gained the batch arguments it never loads.  Prints one line per unit; exit status 1 on any
 difference, unpaired kernel or changed kernel count.
 
@@ -102,7 +104,7 @@ def compare(old_tree, new_tree, unit, same_naming=False, flag_added=False):
     old, new = kernels(assembly(old_tree, unit)), kernels(assembly(new_tree, unit))
     ko = keyed(old, False, same_naming)
     kn = keyed(new, True, same_naming, {k[0] for k in ko} if flag_added else None)
-    notes, same = [], 0
+    notes, same, reordered = [], 0, 0
     for key in sorted(ko.keys() & kn.keys()):
         (bo, ro), (bn, rn) = old[ko[key]], new[kn[key]]
         skip = ".amdhsa_kernarg_size" if key[1] == "Single" else "\0"
@@ -111,13 +113,19 @@ def compare(old_tree, new_tree, unit, same_naming=False, flag_added=False):
                     None if (len(bo), len(ro)) == (len(bn), len(rn)) else f"{len(bo)} != {len(bn)} instructions")
         same += diff is None
         if diff:
-            notes.append(f"  differs: {key}: {diff}")
+            # a pair that differs only in scheduling and register naming: the same opcodes, as many of each, the same resources
+            eq = (len(bo) == len(bn), sorted(t.split()[0] for t in bo) == sorted(t.split()[0] for t in bn), ro == rn)
+            reordered += all(eq)
+            notes.append(f"  differs: {key}: {diff} [instruction count {'=' if eq[0] else '!'}= opcode multiset "
+                         f"{'=' if eq[1] else '!'}= .amdhsa_ {'=' if eq[2] else '!'}=]")
     notes += [f"  only in OLD: {k}" for k in sorted(ko.keys() - kn.keys())]
     added = sorted(kn.keys() - ko.keys())
     if not flag_added:
         notes += [f"  only in NEW: {k}" for k in added]
     paired = len(ko.keys() & kn.keys())
     line = f"{unit}: kernels {len(old)} -> {len(new)}, paired {paired}, identical {same}, differing {paired - same}"
+    if paired - same:
+        line += f" ({reordered} reordered: equal instruction count, opcode multiset and .amdhsa_ lines)"
     if flag_added:
         line += f", new {len(added)}"
     return "\n".join([line] + notes), not notes and (flag_added or len(old) == len(new))
