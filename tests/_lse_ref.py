@@ -74,3 +74,86 @@ def check(c, ref, a, b, dtype="float", reduce_op="Max", transposed_a=False, what
     assert not bad.any(), (f"{what}: {int(bad.sum())} outputs beyond the bound, worst err {err[bad].max()} "
                            f"vs bound {bnd[bad].min()}")
     return float(err[fin].max()) if fin.any() else 0.0
+
+
+# ---- operands that need the hybrid's fallback, and the batch that puts them inside a batched call ----------------------------
+NP = {"half": np.float16, "float": np.float32, "double": np.float64}
+DEPTH = {"half": 120, "float": 120, "double": 800}   # exp(-depth) is 0 in the computation type, and S below tau (2^-64, f64: 2^-512)
+
+
+def adversarial(dtype, red, n, k, m, rows, cols, depth, seed=3, spread=1.0):
+    """(a (n, k), b (k, m)) of uniform(-spread, spread) data in which rows `rows` of A are about 0 over the first half of K and
+    about -depth over the second, and columns `cols` of B the mirror image: every term of that block sits about `depth` below
+    ra + rb.  Min: the pair negated.  Asserted here, per call: the reference on the block is finite with |ref| > depth - 10,
+    and the shifted pipeline log(exp(a - ra) @ exp(b - rb)) + ra + rb in the computation type returns an infinity on all of
+    it -- without the exact kernel's tiles the answer would be wrong."""
+    rng = np.random.default_rng(seed)
+    h = k // 2
+    nr, nc = len(range(*rows.indices(n))), len(range(*cols.indices(m)))
+    a = rng.uniform(-spread, spread, size=(n, k))
+    b = rng.uniform(-spread, spread, size=(k, m))
+    a[rows, :h] = rng.uniform(-0.5, 0.5, size=(nr, h))
+    a[rows, h:] = -depth + rng.uniform(-0.5, 0.5, size=(nr, k - h))
+    b[:h, cols] = -depth + rng.uniform(-0.5, 0.5, size=(h, nc))
+    b[h:, cols] = rng.uniform(-0.5, 0.5, size=(k - h, nc))
+    sg = -1 if red == "Min" else 1
+    a, b = (sg * a).astype(NP[dtype]), (sg * b).astype(NP[dtype])
+    ref = logsumexp_ref(a[rows], b[:, cols], dtype, red)
+    assert np.isfinite(ref).all() and (np.abs(ref.astype(np.float64)) > depth - 10).all(), "the block's reference"
+    ct = COMPUTE[dtype]
+    sa, sb = sg * a.astype(ct), sg * b.astype(ct)
+    ra, rb = sa.max(axis=1, keepdims=True), sb.max(axis=0, keepdims=True)
+    with np.errstate(divide="ignore", under="ignore"):
+        shifted = np.log(np.exp(sa - ra) @ np.exp(sb - rb)) + ra + rb
+    assert shifted.dtype == ct and np.isinf(shifted[rows, cols]).all(), "the shifted pipeline was expected to lose the block"
+    return a, b
+
+
+# 3 x 4 tiles of 64 x 64, a two-row last tile row and an eight-column last tile column, K padded from 72 to 128
+FB_SHAPE = (130, 72, 200)
+FB_BATCH = 5
+# element -> (rows, cols) of its adversarial block: element 1 flags tiles 5 and 9 (the ragged tile row), element 4 tiles 2 and 3
+FB_BLOCKS = {1: (slice(100, 130), slice(64, 128)), 4: (slice(0, 64), slice(128, 200))}
+# the 64 x 64 tiles those blocks touch, as (rows, cols): what the exact kernel recomputes
+FB_TILES = {1: (slice(64, 130), slice(64, 128)), 4: (slice(0, 64), slice(128, 200))}
+FB_NAN = (2, 70, 30)      # A[e, i, k]: row 70 of element 2 is NaN
+FB_INF_ROW = (3, 5)       # A[e, i, :]: row 5 of element 3 is -inf (Min: +inf), every term of it
+_FB = {}
+
+
+def _frozen(x):
+    x.setflags(write=False)
+    return x
+
+
+def fallback_batch(dtype, red):
+    """The batch of 5 the fallback and chunking tests share (built once per (dtype, red), read-only): elements 0, 2 and 3
+    uniform(-5, 5), elements 1 and 4 adversarial() on FB_BLOCKS -- two elements that flag DIFFERENT tiles, in chunks 0 and 2
+    of a 2 + 2 + 1 split.  Returns a dict of
+      a (5, N, K), b (5, K, M);
+      seed (5, N, M): uniform(-8, 8) with one row of -inf (Min: +inf), a term that adds nothing, and for Min a row of -inf
+        as well, which is then the output;
+      a_special: a with one NaN in element 2 (FB_NAN) and a row of -inf (Min: +inf) in element 3 (FB_INF_ROW);
+      ref, ref_seeded, ref_special: the references of all five elements."""
+    if (dtype, red) not in _FB:
+        n, k, m = FB_SHAPE
+        rng = np.random.default_rng(41)
+        a = rng.uniform(-5, 5, size=(FB_BATCH, n, k)).astype(NP[dtype])
+        b = rng.uniform(-5, 5, size=(FB_BATCH, k, m)).astype(NP[dtype])
+        for e, (rows, cols) in FB_BLOCKS.items():
+            a[e], b[e] = adversarial(dtype, red, n, k, m, rows, cols, DEPTH[dtype], seed=50 + e, spread=5.0)
+        seed = rng.uniform(-8, 8, size=(FB_BATCH, n, m)).astype(NP[dtype])
+        seed[:, 101, :] = np.inf if red == "Min" else -np.inf     # the reduction's identity, inside element 1's block
+        if red == "Min":
+            seed[:, 70, :] = -np.inf                              # a row of -inf absorbs a soft-min: -inf out (in no block)
+        ref = np.stack([logsumexp_ref(a[e], b[e], dtype, red) for e in range(FB_BATCH)])
+        ref_seeded = np.stack([logsumexp_ref(a[e], b[e], dtype, red, seed[e]) for e in range(FB_BATCH)])
+        a_special = a.copy()
+        a_special[FB_NAN] = np.nan
+        a_special[FB_INF_ROW] = np.inf if red == "Min" else -np.inf
+        ref_special = ref.copy()
+        for e in (FB_NAN[0], FB_INF_ROW[0]):
+            ref_special[e] = logsumexp_ref(a_special[e], b[e], dtype, red)
+        parts = dict(a=a, b=b, seed=seed, a_special=a_special, ref=ref, ref_seeded=ref_seeded, ref_special=ref_special)
+        _FB[dtype, red] = {key: _frozen(v) for key, v in parts.items()}
+    return _FB[dtype, red]

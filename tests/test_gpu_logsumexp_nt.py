@@ -1,7 +1,7 @@
 """The log-semiring product over an M x K B on the MI355X (mm_gemm_logsumexp_nt_*, matmul_logsumexp_nt /
 addmm_logsumexp_nt_): every configuration on both kernels against the numpy reference on bt.T (the header's bound for finite
-outputs, special values exactly), equality with the row-major call on a materialised transpose, the hybrid's fallback,
-accumulation, batches, determinism, and a Viterbi decoder and a forward pass over a "to-state major" transition matrix."""
+outputs, special values exactly), equality with the row-major call on a materialised transpose, the hybrid's fallback --
+alone and inside a batch --, accumulation, batches, batches chunked by the knob, determinism, and a Viterbi decoder and a forward pass over a "to-state major" transition matrix."""
 import math
 
 import numpy as np
@@ -16,6 +16,7 @@ torch = pytest.importorskip("torch")
 DEV = rm.DEV
 NP = rm.NP
 GUARD = rm.GUARD
+knobs = rm.knobs    # the fixture: set(name, value), every knob put back
 
 
 @pytest.fixture
@@ -130,6 +131,19 @@ def test_lse_nt_hybrid_fallback(lse_variant):
         lse_variant(0)
         c0 = g.matmul_logsumexp_nt(ta, tb, reduce_op=red).cpu().numpy()
         assert np.array_equal(c1[block].view(np.uint8), c0[block].view(np.uint8)), "the flagged tile is the exact kernel's"
+
+
+@pytest.mark.parametrize("dtype,red,form", rm.fallback_cases(nt=True))
+def test_lse_nt_fallback_inside_a_batch(dtype, red, form, knobs):
+    """test_gpu_logsumexp.py's batch of five with two adversarial elements, B handed over as materialised b.mT: "lse_hybrid_nt",
+    whose exact kernel reads an M x K B with a batch stride."""
+    rm.check_fallback_inside_a_batch(dtype, red, form, knobs, nt=True)
+
+
+@pytest.mark.parametrize("red", ["Max", "Min"])
+@pytest.mark.parametrize("dtype", ["half", "float", "double"])
+def test_lse_nt_batch_chunks_by_the_knob_keep_every_bit(dtype, red, knobs):
+    rm.check_chunks_by_the_knob(dtype, red, knobs, nt=True)
 
 
 @pytest.mark.parametrize("path", [g.PATH_AUTO, g.PATH_ORDERED], ids=["auto", "ordered"])

@@ -2,6 +2,7 @@
 Bt stored M x K.  The reference is _semiring_ref.reference() on bt.T -- Naive on the transposed operand -- and, for the
 matrix-core route, the row-major batched call on a materialised transpose."""
 import ctypes
+import time
 import zlib
 
 import numpy as np
@@ -223,6 +224,58 @@ def test_nt_batches_broadcast_padded_and_chunked(kernel, dtype, mp, rd, path, sh
         assert sr.same_bits(full, g.bmm(ta, tb, dtype).cpu().numpy())
         assert sr.same_bits(b_shared, g.bmm(ta, tb[0], dtype).cpu().numpy())
         assert sr.same_bits(a_shared, g.bmm(ta[0], tb, dtype).cpu().numpy())
+
+
+# (the pre-pass's OWN loop over the batch -- a second transposition into the reused workspace, batch_slice at e0 > 0, the
+# stride_b of the second chunk's product -- is bounded by the workspace alone: batch_chunk does not reach it)
+@pytest.mark.parametrize("dtype,k", [("uint8_t", 1024), ("float", 512)])
+def test_nt_prepass_second_workspace_chunk(dtype, k):
+    """K = M = 1024 of uint8_t, or 512 of float: a transposed copy is K * M * es = 2^20 bytes, the 256 MiB of workspace hold
+    2^28 / 2^20 = 256 of them, and a batch of 261 runs as 256 + 5.  The batch is base[e % 7] -- no chunk boundary falls on
+    a period -- gathered on the device, Bt with a padded batch stride (M * K + 16; the pads hold 255 / NaN).  uint8_t, plain
+    and seeded: every element is numpy's sums mod 2^8 of its base.  float: the whole batch is, bit for bit, bmm / baddbmm_ on
+    the materialised transposes of the same 261 elements, and the first 7 are within the north_star bar and the chain guard
+    of the float64 products."""
+    import torch
+    n, m, batch, period, pad = 64, k, 261, 7, 16
+    t = sr.NP_DTYPES[dtype]
+    assert ((256 << 20) // (k * m * t().itemsize)) == 256 < batch
+    assert g.kernel_name_nt(g.make_config(dtype), n, k, m, batch) == "nt_prepass"
+    rng = _rng("second-chunk", dtype)
+    if dtype == "float":
+        a, bt, c0 = (rng.uniform(-2, 2, size=shape).astype(t) for shape in ((period, n, k), (period, m * k), (period, n, m)))
+    else:
+        a, bt, c0 = (rng.integers(0, 255, size=shape, endpoint=True).astype(t) for shape in ((period, n, k), (period, m * k), (period, n, m)))
+    index = torch.arange(batch, device="cuda:0") % period
+    ta, tc0 = torch.from_numpy(a).cuda()[index], torch.from_numpy(c0).cuda()[index]
+    buf = torch.full((batch, m * k + pad), float("nan") if dtype == "float" else 255, dtype=ta.dtype, device="cuda:0")
+    buf[:, :m * k] = torch.from_numpy(bt).cuda()[index]
+    tbt = torch.as_strided(buf, (batch, m, k), (m * k + pad, k, 1))
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    got = g.matmul_nt(ta, tbt, dtype)
+    got_seeded = g.addmm_nt_(tc0.clone(), ta, tbt, dtype)
+    torch.cuda.synchronize()
+    print(f"nt_prepass {dtype}, {batch} x {n}x{k}x{m} in two workspace chunks, plain + seeded: {time.perf_counter() - t0:.3f} s")
+    if dtype == "uint8_t":   # exact, and independent of any kernel
+        prod = np.stack([a[e].astype(np.int64) @ bt[e].reshape(m, k).T.astype(np.int64) for e in range(period)])
+        want, want_seeded = (prod % 256).astype(t), ((prod + c0) % 256).astype(t)
+        assert np.unique(want).size >= 3 and not np.array_equal(want, want_seeded)
+        assert torch.equal(got, torch.from_numpy(want).cuda()[index])
+        assert torch.equal(got_seeded, torch.from_numpy(want_seeded).cuda()[index])
+        return
+    tb = tbt.mT.contiguous()
+    want, want_seeded = g.bmm(ta, tb, dtype), g.baddbmm_(tc0.clone(), ta, tb, dtype)
+    assert torch.equal(got.view(torch.int32), want.view(torch.int32))
+    assert torch.equal(got_seeded.view(torch.int32), want_seeded.view(torch.int32)) and not torch.equal(got_seeded, got)
+    first = got[:period].cpu().numpy()
+    tiny = np.finfo(t).smallest_subnormal
+    for e in range(period):
+        exact, scale = sr.exact_and_scale(dtype, a[e], bt[e].reshape(m, k).T)
+        sr.assert_not_degenerate(exact, "Multiply", "Add", f"base {e}")
+        err = _bounds.normwise(first[e].astype(exact.dtype), exact, scale + k * tiny.astype(exact.dtype))
+        _bounds.north_star(err, f"nt_prepass float, base {e}")
+        _bounds.guard(err, _bounds.f32_chain_guard(k), f"nt_prepass float, base {e}")
 
 
 # ---- 5. composition and symmetry ---------------------------------------------------------------------------------------------------
