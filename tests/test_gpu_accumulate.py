@@ -9,23 +9,11 @@ import pytest
 
 import _semiring_ref as sr
 import gemm_hls_amd as g
+from _product_ref import MUL_ADD_TOL, seeded_reference, within_bound
 
 pytestmark = pytest.mark.gpu
 
 GUARD = 64   # elements of guard pattern on each side of C
-
-
-def seeded_reference(dtype, mp, rd, a, b, c0, transposed_a=False, auto_minmax=False):
-    """Naive (include/Utility.h:18-42) with acc = C[i][j] in place of identity()."""
-    t = sr.NP_DTYPES[dtype]
-    a = np.asarray(a, dtype=t)
-    if transposed_a:
-        a = a.T
-    acc = np.array(c0, dtype=t, copy=True)
-    with np.errstate(all="ignore"):
-        for kk in range(a.shape[1]):
-            acc = sr._apply(rd, acc, sr._apply(mp, a[:, kk:kk + 1], b[kk:kk + 1, :], t, auto_minmax), t, auto_minmax)
-    return acc
 
 
 def _dev(x):
@@ -83,19 +71,6 @@ def seeds(dtype, shape, rng, nan=True):
     idx = rng.choice(flat.size, size=min(flat.size, 4 * len(special)), replace=False)
     flat[idx] = np.resize(np.array(special, dtype=t), idx.size)
     return c
-
-
-MUL_ADD_TOL = {"float": 1e-5, "double": 1e-12, "half": 2e-3}
-
-
-def within_bound(dtype, got, a, b, c0, ta=False):
-    """|C - (C_in + A B)| <= tol (|C_in| + |A||B|) elementwise."""
-    exact, scale = sr.exact_and_scale(dtype, a, b, ta) if dtype != "double" else (
-        (a.T if ta else a) @ b, np.abs(a.T if ta else a) @ np.abs(b))
-    exact = exact + c0.astype(exact.dtype)
-    scale = scale + np.abs(c0.astype(exact.dtype)) + np.finfo(sr.NP_DTYPES[dtype]).tiny
-    err = float(np.max(np.abs(got.astype(exact.dtype) - exact) / scale))
-    return err < MUL_ADD_TOL[dtype], err
 
 
 # ---- 1. MM_PATH_ORDERED: all 275 configurations, seeded Naive's bits, single and batched -------------------------------

@@ -11,30 +11,13 @@ import pytest
 
 import _semiring_ref as sr
 import gemm_hls_amd as g
+from _product_ref import oracle
 
 pytestmark = pytest.mark.gpu
 
 GUARD = 64   # elements of guard pattern on each side of C and of I
 REDUCTIONS = ("Min", "Max")
 ARG_CONFIGS = [(d, mp, rd) for d in sr.DTYPES for mp in sr.OPS for rd in REDUCTIONS]   # 11 x 5 x 2 = 110
-
-
-def oracle(dtype, mp, rd, a, b, c0=None, i0=None, transposed_a=False, index_base=0):
-    t = sr.NP_DTYPES[dtype]
-    a = np.asarray(a, dtype=t)
-    if transposed_a:
-        a = a.T
-    n, k = a.shape
-    m = b.shape[1]
-    acc = np.full((n, m), sr.identity(dtype, rd), dtype=t) if c0 is None else np.array(c0, dtype=t, copy=True)
-    idx = np.full((n, m), -1, dtype=np.int32) if i0 is None else np.array(i0, dtype=np.int32, copy=True)
-    with np.errstate(all="ignore"):
-        for kk in range(k):
-            s = sr._apply(mp, a[:, kk:kk + 1], b[kk:kk + 1, :], t, False)
-            take = (s < acc) if rd == "Min" else (acc < s)
-            acc = np.where(take, s, acc)
-            idx = np.where(take, np.int32(index_base + kk), idx)
-    return acc, idx
 
 
 def _dev(x):

@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 
 import gemm_hls_amd as g
+from _product_ref import _check_bound, _f32_loop, _int_ref
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -72,32 +73,6 @@ def _operands(dtype, shape, kind, rng):
         return rng.uniform(1.0, 10.0, shape).astype(np.float16)
     mag = np.minimum(2.0 ** rng.uniform(-14.0, 16.0, shape), 65504.0)
     return (mag * rng.choice([-1.0, 1.0], shape)).astype(np.float16)
-
-
-def _int_ref(a, b, seed=None):
-    s = a.astype(np.int64) @ b.astype(np.int64)
-    return (s if seed is None else s + seed.astype(np.int64)).astype(np.int32)      # the cast wraps mod 2^32
-
-
-def _f32_loop(a, b, seed=None):
-    """acc = seed or 0; for k ascending: acc = acc + (float)a * (float)b, each operation rounded to float32 (numpy does not fuse)."""
-    a32, b32 = a.astype(np.float32), b.astype(np.float32)
-    acc = np.zeros((a.shape[0], b.shape[1]), np.float32) if seed is None else seed.astype(np.float32).copy()
-    with np.errstate(all="ignore"):
-        for kk in range(a.shape[1]):
-            acc = acc + a32[:, kk, None] * b32[None, kk, :]
-    return acc
-
-
-def _check_bound(what, c, a, b, seed=None, rel=1e-6):
-    exact = a.astype(np.float64) @ b.astype(np.float64)
-    scale = np.abs(a.astype(np.float64)) @ np.abs(b.astype(np.float64))
-    if seed is not None:
-        exact, scale = exact + seed.astype(np.float64), scale + np.abs(seed.astype(np.float64))
-    err, bound = np.abs(c.astype(np.float64) - exact), rel * scale
-    bad = np.argwhere(~(err <= bound))
-    print(f"{what}: max err / bound = {np.max(err / np.maximum(bound, 1e-300)):.3f}")
-    assert bad.size == 0, f"{what}: |c - exact| {err[tuple(bad[0])]!r} above the bound {bound[tuple(bad[0])]!r} at {tuple(bad[0])} ({len(bad)} elements)"
 
 
 def _half(x):
