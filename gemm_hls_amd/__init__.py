@@ -32,7 +32,9 @@ EXPORTS = ["mm_init", "mm_alloc", "mm_free", "mm_copy_to_device", "mm_copy_to_ho
            "mm_gemm_widen_enqueue", "mm_gemm_widen_launch", "mm_kernel_name_widen", "mm_widen_dtype",
            "mm_gemm_nt_enqueue", "mm_gemm_nt_launch", "mm_kernel_name_nt", "mm_gemm_argreduce_nt_enqueue",
            "mm_gemm_argreduce_nt_launch", "mm_kernel_name_argreduce_nt", "mm_gemm_logsumexp_nt_enqueue",
-           "mm_gemm_logsumexp_nt_launch", "mm_kernel_name_logsumexp_nt"]
+           "mm_gemm_logsumexp_nt_launch", "mm_kernel_name_logsumexp_nt", "mm_bits_gemm_enqueue", "mm_bits_gemm_launch",
+           "mm_kernel_name_bits_gemm", "mm_bits_closure_enqueue", "mm_bits_closure_launch", "mm_kernel_name_bits_closure",
+           "mm_bits_pack_enqueue", "mm_bits_pack_launch", "mm_bits_unpack_enqueue", "mm_bits_unpack_launch"]
 
 
 class MMError(RuntimeError):
@@ -140,6 +142,18 @@ def lib():
         L.mm_gemm_logsumexp_nt_launch.argtypes = L.mm_gemm_logsumexp_launch.argtypes
         L.mm_kernel_name_logsumexp_nt.argtypes = [cfgp, u, u, u, u]
         L.mm_kernel_name_logsumexp_nt.restype = ctypes.c_char_p
+        L.mm_bits_gemm_enqueue.argtypes = [vp, vp, vp, vp, u, u, u, sz, sz, sz, u, sz, sz, sz, i]
+        L.mm_bits_gemm_launch.argtypes = [i, vp, vp, vp, u, u, u, sz, sz, sz, u, sz, sz, sz, i, ctypes.POINTER(ctypes.c_double)]
+        L.mm_kernel_name_bits_gemm.argtypes = [u, u, u, sz, sz, sz, u]
+        L.mm_kernel_name_bits_gemm.restype = ctypes.c_char_p
+        L.mm_bits_closure_enqueue.argtypes = [vp, vp, u, sz, u, sz]
+        L.mm_bits_closure_launch.argtypes = [i, vp, u, sz, u, sz, ctypes.POINTER(ctypes.c_double)]
+        L.mm_kernel_name_bits_closure.argtypes = [u, u]
+        L.mm_kernel_name_bits_closure.restype = ctypes.c_char_p
+        L.mm_bits_pack_enqueue.argtypes = [vp, vp, vp, u, u, sz, sz, u, sz, sz]
+        L.mm_bits_pack_launch.argtypes = [i, vp, vp, u, u, sz, sz, u, sz, sz, ctypes.POINTER(ctypes.c_double)]
+        L.mm_bits_unpack_enqueue.argtypes = L.mm_bits_pack_enqueue.argtypes
+        L.mm_bits_unpack_launch.argtypes = L.mm_bits_pack_launch.argtypes
         _lib = L
     return _lib
 
@@ -686,6 +700,173 @@ def closure_(d, d_witness=None, dtype="float", map_op="Add", reduce_op="Min", pa
         w = d_witness.data_ptr()
     cfg = make_config(dtype, map_op, reduce_op, path)
     _enqueue(d.device, lib().mm_closure_enqueue, ctypes.byref(cfg), d.data_ptr(), w, n, batch, n * n)
+    return d
+
+
+# ---- bit-packed Boolean semiring (mm_bits_*): one bit per element, 32 columns per torch.int32 word, LSB first ---------------
+def bits_words(cols):
+    """Words of a packed row of `cols` columns."""
+    return (cols + 31) // 32
+
+
+def kernel_name_bits_gemm(n, k, m, lda=None, ldb=None, ldc=None, batch=1):
+    """Name of the kernel bits_matmul / bits_addmm_ run; the row strides (words) default to the rows' own word counts."""
+    lda, ldb, ldc = (bits_words(c) if ld is None else ld for ld, c in ((lda, k), (ldb, m), (ldc, m)))
+    return lib().mm_kernel_name_bits_gemm(n, k, m, lda, ldb, ldc, batch).decode()
+
+
+def kernel_name_bits_closure(n, batch=1):
+    return lib().mm_kernel_name_bits_closure(n, batch).decode()
+
+
+def _byte_rows(x, what):
+    """(x or a dense copy, batch, batch stride, row stride) of a (..., rows, cols) tensor of one-byte elements."""
+    if x.dim() < 2:
+        raise MMError(f"{what} takes a (..., rows, cols) tensor; got shape {tuple(x.shape)}")
+    rows, cols = x.shape[-2], x.shape[-1]
+    dense = x.dim() <= 3 and (cols == 1 or x.stride(-1) == 1) and (rows == 1 or x.stride(-2) >= cols) and (
+        x.dim() == 2 or x.shape[0] == 1 or x.stride(0) >= (rows - 1) * x.stride(-2) + cols)
+    if not dense:
+        x = x.contiguous()
+    if x.dim() > 3:
+        x = x.reshape(-1, rows, cols)
+    batch = x.shape[0] if x.dim() == 3 else 1
+    return x, batch, (x.stride(0) if batch > 1 else 0), (x.stride(-2) if rows > 1 else cols)
+
+
+def pack_bits(x):
+    """torch.bool or torch.uint8 (..., rows, cols) -> torch.int32 (..., rows, ceil(cols / 32)) on torch's current stream
+    (mm_bits_pack_enqueue): column j is bit j & 31 of word j >> 5, a nonzero byte is 1, the padding bits are 0.  A 2-D or
+    3-D x with unit column stride is read as it lies (row and batch strides), anything else through a dense copy."""
+    import torch
+    if not x.is_cuda:
+        raise MMError("pack_bits needs a device tensor: there is no CPU path")
+    if x.dtype not in (torch.bool, torch.uint8):
+        raise MMError(f"pack_bits takes torch.bool or torch.uint8 (got {x.dtype})")
+    shape = tuple(x.shape)
+    x, batch, stride, ld = _byte_rows(x, "pack_bits")
+    rows, cols = shape[-2], shape[-1]
+    words = bits_words(cols)
+    out = torch.empty(shape[:-1] + (words,), dtype=torch.int32, device=x.device)
+    _enqueue(x.device, lib().mm_bits_pack_enqueue, x.data_ptr(), out.data_ptr(), rows, cols, ld, words, batch, stride,
+             rows * words)
+    return out
+
+
+def _packed_operand(x, name, rows, cols):
+    """(batch or None, batch stride, row stride), in words, of a packed operand: torch.int32, (rows, W) or (B, rows, W) with
+    W >= ceil(cols / 32) and unit stride along the words; the row stride is the tensor's own, so a slice of whole words of
+    a wider packed matrix is an operand as it lies."""
+    import torch
+    words = bits_words(cols)
+    if x.dtype != torch.int32:
+        raise MMError(f"{name} must be a packed torch.int32 tensor (got {x.dtype})")
+    if x.dim() not in (2, 3) or x.shape[-2] != rows or x.shape[-1] < words:
+        raise MMError(f"{name} has shape {tuple(x.shape)}, expected ({rows}, W) or (B, {rows}, W) with W >= {words}")
+    if x.shape[-1] > 1 and x.stride(-1) != 1:
+        raise MMError(f"the words of a row of {name} must be contiguous (strides {x.stride()})")
+    ld = x.stride(-2) if rows > 1 else max(x.stride(-2), words)
+    if ld < words:
+        raise MMError(f"{name} has row stride {ld}, below its {words} words")
+    if x.dim() == 2:
+        return None, 0, ld
+    if x.stride(0) < 0:
+        raise MMError(f"{name} has a negative batch stride")
+    return x.shape[0], (0 if x.shape[0] == 1 else x.stride(0)), ld
+
+
+def unpack_bits(p, cols, dtype=None):
+    """The inverse of pack_bits (mm_bits_unpack_enqueue): packed torch.int32 (..., rows, W), W >= ceil(cols / 32), to
+    (..., rows, cols) of `dtype` -- torch.bool (the default) or torch.uint8 -- holding 0 / 1."""
+    import torch
+    dtype = torch.bool if dtype is None else dtype
+    if dtype not in (torch.bool, torch.uint8):
+        raise MMError(f"unpack_bits writes torch.bool or torch.uint8 (got {dtype})")
+    if not p.is_cuda:
+        raise MMError("unpack_bits needs a device tensor: there is no CPU path")
+    if p.dim() < 2:
+        raise MMError(f"unpack_bits takes a (..., rows, W) tensor; got shape {tuple(p.shape)}")
+    shape = tuple(p.shape[:-1]) + (cols,)
+    if p.dim() > 3:
+        p = p.contiguous().reshape(-1, *p.shape[-2:])
+    rows = p.shape[-2]
+    batch, stride, ld = _packed_operand(p, "p", rows, cols)
+    out = torch.empty(shape, dtype=dtype, device=p.device)
+    _enqueue(p.device, lib().mm_bits_unpack_enqueue, p.data_ptr(), out.data_ptr(), rows, cols, ld, cols, batch or 1, stride,
+             rows * cols)
+    return out
+
+
+def _bits_shapes(what, a, b, k, m):
+    if not (a.is_cuda and b.is_cuda):
+        raise MMError(f"{what} needs device tensors: there is no CPU path")
+    if a.device != b.device:
+        raise MMError(f"operands live on different devices: {a.device} and {b.device}")
+    if a.dim() not in (2, 3) or b.dim() not in (2, 3):
+        raise MMError(f"{what} takes 2-D or 3-D operands")
+    n = a.shape[-2]
+    ba, sa, lda = _packed_operand(a, "a", n, k)
+    bb, sb, ldb = _packed_operand(b, "b", k, m)
+    batches = {x for x in (ba, bb) if x is not None and x != 1}
+    if len(batches) > 1:
+        raise MMError(f"batch sizes differ: {ba} and {bb}")
+    return n, (batches.pop() if batches else 1), sa, sb, lda, ldb
+
+
+def bits_matmul(a, b, k, m, out=None):
+    """Packed Boolean product on torch's current stream (mm_bits_gemm_enqueue): C[i][j] = OR_k (A[i][k] AND B[k][j]).
+    a: (N, Wk) packed along K, b: (K, Wm) packed along M, torch.int32; either may be 3-D, or expanded with batch stride 0.
+    k and m are the logical bit counts (the word counts alone do not determine them); Wk >= ceil(k / 32), Wm >=
+    ceil(m / 32), and row strides are taken from the tensors, so p[:, 1:3] of a wider packed matrix is a valid a without a
+    copy.  Returns (N, ceil(m / 32)) when both operands are 2-D, else (B, N, ceil(m / 32)); out: a packed tensor of that
+    shape (more words per row allowed; they are left alone).  Padding bits of the result are 0.  Asynchronous."""
+    import torch
+    n, batch, sa, sb, lda, ldb = _bits_shapes("bits_matmul", a, b, k, m)
+    two_d = a.dim() == 2 and b.dim() == 2
+    if out is None:
+        out = torch.empty((n, bits_words(m)) if two_d else (batch, n, bits_words(m)), dtype=torch.int32, device=a.device)
+    elif out.device != a.device or out.dim() != (2 if two_d else 3) or (not two_d and out.shape[0] != batch):
+        raise MMError(f"out has shape {tuple(out.shape)} on {out.device}; expected {'(N, W)' if two_d else f'({batch}, N, W)'} on {a.device}")
+    bc, sc, ldc = _packed_operand(out, "out", n, m)
+    if batch > 1 and sc == 0:
+        raise MMError(f"out has batch stride 0: the {batch} outputs would overlap")
+    _enqueue(a.device, lib().mm_bits_gemm_enqueue, a.data_ptr(), b.data_ptr(), out.data_ptr(), n, k, m, lda, ldb, ldc, batch,
+             sa, sb, sc, 0)
+    return out
+
+
+def bits_addmm_(c, a, b, k, m):
+    """In place C <- C | A B on torch's current stream (mm_bits_gemm_enqueue, accumulate); a and b as for bits_matmul, c:
+    (N, Wm) or (B, N, Wm) packed torch.int32 with its own row stride, not overlapping a or b.  Two calls on the halves of K
+    equal one call on all of it.  Returns c.  Asynchronous."""
+    n, batch, sa, sb, lda, ldb = _bits_shapes("bits_addmm_", a, b, k, m)
+    if not c.is_cuda or c.device != a.device:
+        raise MMError(f"c must live on {a.device} (got {c.device})")
+    bc, sc, ldc = _packed_operand(c, "c", n, m)
+    if batch not in (1, bc or 1):
+        raise MMError(f"c has shape {tuple(c.shape)}, expected ({batch}, {n}, W)")
+    batch = bc or 1
+    if batch > 1 and sc == 0:
+        raise MMError(f"c has batch stride 0: the {batch} outputs would overlap")
+    _enqueue(a.device, lib().mm_bits_gemm_enqueue, a.data_ptr(), b.data_ptr(), c.data_ptr(), n, k, m, lda, ldb, ldc, batch,
+             sa, sb, sc, 1)
+    return c
+
+
+def bits_closure_(d, n=None):
+    """In place D <- D+, the transitive closure of a packed adjacency matrix, on torch's current stream
+    (mm_bits_closure_enqueue): (i, j) is set when a path of one or more edges leads from i to j; no identity is added to
+    the diagonal.  d: packed torch.int32 (n, W) or (batch, n, W) with W >= ceil(n / 32) and its own row stride; n defaults
+    to the number of rows.  Returns d.  Asynchronous."""
+    if not d.is_cuda:
+        raise MMError("bits_closure_ needs a device tensor: there is no CPU path")
+    if d.dim() not in (2, 3):
+        raise MMError(f"bits_closure_ takes an (n, W) or (batch, n, W) tensor; got shape {tuple(d.shape)}")
+    n = d.shape[-2] if n is None else n
+    batch, stride, ldd = _packed_operand(d, "d", n, n)
+    if (batch or 1) > 1 and stride == 0:
+        raise MMError(f"d has batch stride 0: the {batch} graphs would overlap")
+    _enqueue(d.device, lib().mm_bits_closure_enqueue, d.data_ptr(), n, ldd, batch or 1, stride)
     return d
 
 

@@ -92,11 +92,11 @@ std::atomic<int> g_tuning[mm::TUNE_COUNT];
 const char *const kTuneName[mm::TUNE_COUNT] = {"f32_variant", "f64_variant", "f16_variant", "i8_variant", "band_rows",
                                                "valu_variant", "split_variant", "f32_splitk", "ablations", "debug_poison", "kxn_prepass_min_m",
                                                "md_virtual_devices", "ordered_variant", "half_contract", "batch_chunk",
-                                               "closure_block", "lse_variant"};
+                                               "closure_block", "lse_variant", "bits_variant"};
 const char *const kTuneEnv[mm::TUNE_COUNT] = {"MM_F32_VARIANT", "MM_F64_VARIANT", "MM_F16_VARIANT", "MM_I8_VARIANT",
                                               "MM_BAND_ROWS", "MM_VALU_VARIANT", "MM_SPLIT_VARIANT", "MM_F32_SPLITK", "MM_ABLATIONS", "MM_DEBUG_POISON", "MM_KXN_PREPASS_MIN_M",
                                               "MM_MD_VIRTUAL_DEVICES", "MM_ORDERED_VARIANT", "MM_HALF_CONTRACT", "MM_BATCH_CHUNK",
-                                              "MM_CLOSURE_BLOCK", "MM_LSE_VARIANT"};
+                                              "MM_CLOSURE_BLOCK", "MM_LSE_VARIANT", "MM_BITS_VARIANT"};
 void tuning_init() {
   for (int i = 0; i < mm::TUNE_COUNT; ++i) {
     const char *e = getenv(kTuneEnv[i]);
@@ -575,6 +575,166 @@ int dispatch_closure(hipStream_t s, const mm_config_t &cfg, void *d, int *w, uns
   return rc;
 }
 
+// ---- bit-packed Boolean semiring (mm_bits_*) ----------------------------------------------------------------------------
+enum BitsKernel { BITS_NONE, BITS_PLAIN, BITS_TILE, BITS_INVALID };
+
+size_t bits_words(unsigned cols) { return ((size_t)cols + 31) / 32; }
+// Units (words, or bytes for the unpacked side) an operand of the batch can touch: rows of `row` units, ld apart.
+size_t bits_span(unsigned rows, size_t row, size_t ld, unsigned batch, size_t stride) {
+  return rows && row && batch ? (size_t)(batch - 1) * stride + (size_t)(rows - 1) * ld + row : 0;
+}
+
+// The kernel by shape, ld and knob alone (mm_kernel_name_bits_gemm); alignment may still demote BITS_TILE at launch.
+BitsKernel bits_kernel_for(unsigned m, size_t ldb, size_t ldc) {
+  const int v = mm::tuning(mm::TUNE_BITS_VARIANT);
+  if (v < -1 || v > 1) return BITS_INVALID;
+  if (v == 0 || !mm::bits_tile_serves(ldb, ldc)) return BITS_PLAIN;
+  return v == 1 || m > 2048 ? BITS_TILE : BITS_PLAIN;   // below 65 words the tile's second word per lane would be idle
+}
+
+// The launch-time half of the rule: b in 16-byte and c in 8-byte accesses, for every element of the batch.
+BitsKernel bits_demote(const mm::BitsProblem &p, BitsKernel ker) {
+  if (ker != BITS_TILE) return ker;
+  const bool aligned = ((uintptr_t)p.b & 15u) == 0 && ((uintptr_t)p.c & 7u) == 0 &&
+                       (p.batch <= 1 || (p.stride_b % 4 == 0 && p.stride_c % 2 == 0));
+  return aligned ? BITS_TILE : BITS_PLAIN;
+}
+
+// All argument checks of a packed product, before any device is touched.  *ker = BITS_NONE: nothing to launch.
+int check_bits_gemm(const mm::BitsProblem &p, BitsKernel *ker) {
+  *ker = BITS_NONE;
+  const BitsKernel k = bits_kernel_for(p.m, p.ldb, p.ldc);
+  if (k == BITS_INVALID) return fail(MM_ERR_BAD_ARGUMENT, "bits_variant %d is not one of -1, 0, 1", mm::tuning(mm::TUNE_BITS_VARIANT));
+  if (p.batch == 0 || p.n == 0 || p.m == 0) return MM_OK;
+  if (!p.c || (p.k && (!p.a || !p.b))) return fail(MM_ERR_BAD_ARGUMENT, "null matrix pointer");   // (K = 0: A, B unread)
+  const size_t kw = bits_words(p.k), mw = bits_words(p.m);
+  if (p.lda < kw || p.ldc < mw || (p.k && p.ldb < mw))
+    return fail(MM_ERR_BAD_ARGUMENT, "a row stride is below its row's words: lda %zu (needs %zu), ldb %zu (%zu), ldc %zu (%zu)",
+                p.lda, kw, p.ldb, mw, p.ldc, mw);
+  const size_t c_words = bits_span(p.n, mw, p.ldc, 1, 0);
+  if (p.batch > 1 && p.stride_c < c_words)
+    return fail(MM_ERR_BAD_ARGUMENT, "stride_c %zu < (N - 1) ldc + ceil(M / 32) = %zu: the outputs of the batch would overlap",
+                p.stride_c, c_words);
+  const size_t a_bytes = 4 * bits_span(p.n, kw, p.lda, p.batch, p.stride_a), b_bytes = 4 * bits_span(p.k, mw, p.ldb, p.batch, p.stride_b);
+  const size_t c_bytes = 4 * bits_span(p.n, mw, p.ldc, p.batch, p.stride_c);
+  if (spans_overlap(p.c, c_bytes, p.a, a_bytes) || spans_overlap(p.c, c_bytes, p.b, b_bytes))
+    return fail(MM_ERR_BAD_ARGUMENT, "c overlaps a or b (bases %p, %p, %p)", (const void *)p.a, (const void *)p.b, (void *)p.c);
+  if (p.k == 0 && p.seed) return MM_OK;   // accumulating over no k: C keeps its value
+  *ker = bits_demote(p, k);
+  return MM_OK;
+}
+
+// The batch in launches of at most 2^22 workgroups (64 x 64-word tiles, the smaller of the two) and batch_chunk elements.
+int dispatch_bits_gemm(hipStream_t s, const mm::BitsProblem &p, BitsKernel ker) {
+  const unsigned long long tiles = (unsigned long long)((p.n + 63) / 64) * ((bits_words(p.m) + 63) / 64);
+  unsigned long long chunk = std::max(1ull, (1ull << 22) / tiles);
+  const int knob = mm::tuning(mm::TUNE_BATCH_CHUNK);
+  if (knob > 0) chunk = std::min<unsigned long long>(chunk, (unsigned)knob);
+  (void)hipGetLastError();   // a stale error of the application's own calls must not be reported as this launch's
+  for (unsigned e0 = 0; e0 < p.batch; e0 += (unsigned)std::min<unsigned long long>(chunk, p.batch)) {
+    mm::BitsProblem q = p;
+    q.batch = (unsigned)std::min<unsigned long long>(chunk, p.batch - e0);
+    q.a += (size_t)e0 * p.stride_a;
+    q.b += (size_t)e0 * p.stride_b;
+    q.c += (size_t)e0 * p.stride_c;
+    if (int e = mm::launch_bits_gemm(s, q, ker == BITS_TILE)) return hip_fail((hipError_t)e, "packed product kernel launch");
+  }
+  return MM_OK;
+}
+
+// pack (to_bits) / unpack: *nothing: an empty call
+int check_bits_convert(const mm::BitsConvert &c, bool to_bits, bool *nothing) {
+  *nothing = c.rows == 0 || c.cols == 0 || c.batch == 0;
+  if (*nothing) return MM_OK;
+  if (!c.src || !c.dst) return fail(MM_ERR_BAD_ARGUMENT, "null matrix pointer");
+  const size_t words = bits_words(c.cols), src_row = to_bits ? c.cols : words, dst_row = to_bits ? words : c.cols;
+  if (c.ld_src < src_row || c.ld_dst < dst_row)
+    return fail(MM_ERR_BAD_ARGUMENT, "a row stride is below its row: source %zu (needs %zu), destination %zu (%zu)", c.ld_src,
+                src_row, c.ld_dst, dst_row);
+  if (c.batch > 1 && c.stride_dst < bits_span(c.rows, dst_row, c.ld_dst, 1, 0))
+    return fail(MM_ERR_BAD_ARGUMENT, "destination batch stride %zu: the outputs of the batch would overlap", c.stride_dst);
+  const size_t src_unit = to_bits ? 1 : 4, dst_unit = to_bits ? 4 : 1;
+  if (spans_overlap(c.dst, dst_unit * bits_span(c.rows, dst_row, c.ld_dst, c.batch, c.stride_dst), c.src,
+                    src_unit * bits_span(c.rows, src_row, c.ld_src, c.batch, c.stride_src)))
+    return fail(MM_ERR_BAD_ARGUMENT, "the destination overlaps the source (bases %p, %p)", c.src, c.dst);
+  return MM_OK;
+}
+
+int dispatch_bits_convert(hipStream_t s, const mm::BitsConvert &c, bool to_bits) {
+  (void)hipGetLastError();
+  const int e = to_bits ? mm::launch_bits_pack(s, c) : mm::launch_bits_unpack(s, c);
+  return e ? hip_fail((hipError_t)e, to_bits ? "pack kernel launch" : "unpack kernel launch") : MM_OK;
+}
+
+constexpr unsigned kBitsClosureBlock = 64;   // one wavefront closes a diagonal block: one row of 64 bits per lane
+
+int check_bits_closure(const void *d, unsigned n, size_t ldd, unsigned batch, size_t stride_d, bool *nothing) {
+  *nothing = n == 0 || batch == 0;
+  if (*nothing) return MM_OK;
+  if (!d) return fail(MM_ERR_BAD_ARGUMENT, "null matrix pointer");
+  const size_t nw = bits_words(n);
+  if (ldd < nw) return fail(MM_ERR_BAD_ARGUMENT, "ldd %zu is below the row's %zu words", ldd, nw);
+  if (batch > 1 && stride_d < bits_span(n, nw, ldd, 1, 0))
+    return fail(MM_ERR_BAD_ARGUMENT, "stride_d %zu < (n - 1) ldd + ceil(n / 32) = %zu: the graphs of the batch would overlap",
+                stride_d, bits_span(n, nw, ldd, 1, 0));
+  return MM_OK;
+}
+
+// One product of a closure round on the graphs of a chunk: the library's own operands, no argument checks.
+int bits_closure_product(hipStream_t s, const mm::BitsProblem &p) {
+  const BitsKernel k = bits_kernel_for(p.m, p.ldb, p.ldc);
+  return dispatch_bits_gemm(s, p, bits_demote(p, k == BITS_INVALID ? BITS_PLAIN : k));
+}
+
+// The packed closure on stream `s`, never synchronising the host.  n <= 64: the wavefront kernel in place, 2^20 graphs per
+// launch.  Otherwise, per chunk of graphs and per block K of 64 vertices: P | I of the closed diagonal block, the panels
+// R = (P | I) D[K,:] and Cc = D[:,K] (P | I) into workspace -- nothing reads a word of D that the same launch writes -- and
+// D <- D | Cc R.  (P | I)(P | I) = P | I, so Cc R = D[:,K] (P | I) D[K,:]: every path whose inner vertices lie in K.
+int dispatch_bits_closure(hipStream_t s, uint32_t *d, unsigned n, size_t ldd, unsigned batch, size_t stride_d) {
+  (void)hipGetLastError();
+  if (batch == 1) stride_d = 0;
+  if (n <= kBitsClosureBlock) {
+    const unsigned chunk = 1u << 20;
+    for (unsigned e0 = 0; e0 < batch; e0 += chunk)
+      if (int e = mm::launch_bits_closure_diag(s, d + (size_t)e0 * stride_d, n, ldd, std::min(chunk, batch - e0), stride_d, 0, nullptr, 0))
+        return hip_fail((hipError_t)e, "packed closure kernel launch");
+    return MM_OK;
+  }
+  const size_t nw = bits_words(n), ldr = (nw + 3) & ~(size_t)3;   // R's rows 16-byte aligned: the tile kernel's B
+  const size_t p_words = 2 * kBitsClosureBlock, r_words = kBitsClosureBlock * ldr, c_words = ((size_t)2 * n + 3) & ~(size_t)3;
+  const size_t per_graph = p_words + r_words + c_words;
+  size_t chunk = std::min<size_t>(batch, std::max<size_t>(1, kClosureWorkspaceCap / (per_graph * 4)));
+  const int knob = mm::tuning(mm::TUNE_BATCH_CHUNK);
+  if (knob > 0) chunk = std::min<size_t>(chunk, (unsigned)knob);
+  int dev = 0;
+  MM_HIP(hipGetDevice(&dev));
+  hipMemPool_t pool = nullptr;
+  if (int e = mm::workspace_pool(dev, &pool)) return hip_fail((hipError_t)e, "workspace pool");
+  void *ws = nullptr;
+  MM_HIP(hipMallocFromPoolAsync(&ws, per_graph * chunk * 4, pool, s));
+  uint32_t *pstar = (uint32_t *)ws, *rp = pstar + p_words, *cp = rp + r_words;   // per graph: [P | I, R, Cc], per_graph words apart
+  int rc = MM_OK;
+  for (unsigned e0 = 0; e0 < batch && rc == MM_OK; e0 += (unsigned)chunk) {
+    const unsigned graphs = (unsigned)std::min<size_t>(chunk, batch - e0);
+    uint32_t *dg = d + (size_t)e0 * stride_d;
+    for (unsigned k0 = 0; k0 < n && rc == MM_OK; k0 += kBitsClosureBlock) {
+      const unsigned bt = std::min(kBitsClosureBlock, n - k0);
+      if (int e = mm::launch_bits_closure_diag(s, dg, n, ldd, graphs, stride_d, k0, pstar, per_graph)) {
+        rc = hip_fail((hipError_t)e, "packed closure kernel launch");
+        break;
+      }
+      const mm::BitsProblem row{pstar, dg + (size_t)k0 * ldd, rp, bt, bt, n, 2, ldd, ldr, graphs, per_graph, stride_d, per_graph, false};
+      const mm::BitsProblem col{dg + k0 / 32, pstar, cp, n, bt, bt, ldd, 2, 2, graphs, stride_d, per_graph, per_graph, false};
+      const mm::BitsProblem all{cp, rp, dg, n, bt, n, 2, ldr, ldd, graphs, per_graph, per_graph, stride_d, true};
+      if ((rc = bits_closure_product(s, row)) || (rc = bits_closure_product(s, col))) break;
+      rc = bits_closure_product(s, all);
+    }
+  }
+  const hipError_t f = hipFreeAsync(ws, s);
+  if (rc == MM_OK && f != hipSuccess) rc = hip_fail(f, "hipFreeAsync (packed closure workspace)");
+  return rc;
+}
+
 // ---- log semiring (mm_gemm_logsumexp_*, mm_gemm_logsumexp_nt_*): log sum exp (A + B) --------------------------------------
 enum LseKernel { LSE_NONE, LSE_EXACT, LSE_HYBRID };
 
@@ -1027,6 +1187,24 @@ int run_closure(const Target &t, const mm_config_t *cfg, void *d, int *witness, 
   return run(t, block == 0, [&](hipStream_t s) { return dispatch_closure(s, *cfg, d, witness, n, batch, stride_d, block); });
 }
 
+int run_bits_gemm(const Target &t, const mm::BitsProblem &p) {
+  BitsKernel ker;
+  if (int rc = check_bits_gemm(p, &ker)) return rc;
+  return run(t, ker == BITS_NONE, [&](hipStream_t s) { return dispatch_bits_gemm(s, p, ker); });
+}
+
+int run_bits_convert(const Target &t, const mm::BitsConvert &c, bool to_bits) {
+  bool nothing;
+  if (int rc = check_bits_convert(c, to_bits, &nothing)) return rc;
+  return run(t, nothing, [&](hipStream_t s) { return dispatch_bits_convert(s, c, to_bits); });
+}
+
+int run_bits_closure(const Target &t, void *d, unsigned n, size_t ldd, unsigned batch, size_t stride_d) {
+  bool nothing;
+  if (int rc = check_bits_closure(d, n, ldd, batch, stride_d, &nothing)) return rc;
+  return run(t, nothing, [&](hipStream_t s) { return dispatch_bits_closure(s, (uint32_t *)d, n, ldd, batch, stride_d); });
+}
+
 }  // namespace
 
 // One library-owned memory pool per device for stream-ordered workspace (the packed planes of MM_PATH_SPLIT, the
@@ -1346,6 +1524,50 @@ int mm_closure_enqueue(void *hip_stream, const mm_config_t *cfg, void *d, int *w
 int mm_closure_launch(int device, const mm_config_t *cfg, void *d, int *witness, unsigned n, unsigned batch, size_t stride_d,
                       double *elapsed_seconds) {
   return run_closure(timed_on(device, elapsed_seconds), cfg, d, witness, n, batch, stride_d);
+}
+
+int mm_bits_gemm_enqueue(void *hip_stream, const void *a, const void *b, void *c, unsigned n, unsigned k, unsigned m, size_t lda,
+                         size_t ldb, size_t ldc, unsigned batch, size_t stride_a, size_t stride_b, size_t stride_c,
+                         int accumulate) {
+  return run_bits_gemm(on_stream(hip_stream), {(const uint32_t *)a, (const uint32_t *)b, (uint32_t *)c, n, k, m, lda, ldb, ldc, batch,
+                                               stride_a, stride_b, stride_c, accumulate != 0});
+}
+
+int mm_bits_gemm_launch(int device, const void *a, const void *b, void *c, unsigned n, unsigned k, unsigned m, size_t lda, size_t ldb,
+                        size_t ldc, unsigned batch, size_t stride_a, size_t stride_b, size_t stride_c, int accumulate,
+                        double *elapsed_seconds) {
+  return run_bits_gemm(timed_on(device, elapsed_seconds), {(const uint32_t *)a, (const uint32_t *)b, (uint32_t *)c, n, k, m, lda, ldb,
+                                                           ldc, batch, stride_a, stride_b, stride_c, accumulate != 0});
+}
+
+int mm_bits_closure_enqueue(void *hip_stream, void *d, unsigned n, size_t ldd, unsigned batch, size_t stride_d) {
+  return run_bits_closure(on_stream(hip_stream), d, n, ldd, batch, stride_d);
+}
+
+int mm_bits_closure_launch(int device, void *d, unsigned n, size_t ldd, unsigned batch, size_t stride_d, double *elapsed_seconds) {
+  return run_bits_closure(timed_on(device, elapsed_seconds), d, n, ldd, batch, stride_d);
+}
+
+int mm_bits_pack_enqueue(void *hip_stream, const void *bytes, void *packed, unsigned rows, unsigned cols, size_t ld_bytes,
+                         size_t ld_packed, unsigned batch, size_t stride_bytes, size_t stride_packed) {
+  return run_bits_convert(on_stream(hip_stream), {bytes, packed, rows, cols, ld_bytes, ld_packed, batch, stride_bytes, stride_packed}, true);
+}
+
+int mm_bits_pack_launch(int device, const void *bytes, void *packed, unsigned rows, unsigned cols, size_t ld_bytes, size_t ld_packed,
+                        unsigned batch, size_t stride_bytes, size_t stride_packed, double *elapsed_seconds) {
+  return run_bits_convert(timed_on(device, elapsed_seconds),
+                          {bytes, packed, rows, cols, ld_bytes, ld_packed, batch, stride_bytes, stride_packed}, true);
+}
+
+int mm_bits_unpack_enqueue(void *hip_stream, const void *packed, void *bytes, unsigned rows, unsigned cols, size_t ld_packed,
+                           size_t ld_bytes, unsigned batch, size_t stride_packed, size_t stride_bytes) {
+  return run_bits_convert(on_stream(hip_stream), {packed, bytes, rows, cols, ld_packed, ld_bytes, batch, stride_packed, stride_bytes}, false);
+}
+
+int mm_bits_unpack_launch(int device, const void *packed, void *bytes, unsigned rows, unsigned cols, size_t ld_packed, size_t ld_bytes,
+                          unsigned batch, size_t stride_packed, size_t stride_bytes, double *elapsed_seconds) {
+  return run_bits_convert(timed_on(device, elapsed_seconds),
+                          {packed, bytes, rows, cols, ld_packed, ld_bytes, batch, stride_packed, stride_bytes}, false);
 }
 
 // Rows per device of the N split: ceil(N / G) rounded up to whole tile rows of the kernel that will run on a slab of that
@@ -1735,6 +1957,20 @@ const char *mm_kernel_name_closure(const mm_config_t *cfg, unsigned n, unsigned 
   const unsigned b = closure_block(*cfg, with_witness != 0);   // the choice check_closure makes
   if (cfg->layout_a == MM_A_TRANSPOSED || b == 0) return "invalid";
   return n <= b ? "closure_onchip" : "closure_blocked";
+}
+
+const char *mm_kernel_name_bits_gemm(unsigned n, unsigned k, unsigned m, size_t lda, size_t ldb, size_t ldc, unsigned batch) {
+  (void)n, (void)k, (void)lda, (void)batch;   // the batch is chunked, never a different kernel
+  switch (bits_kernel_for(m, ldb, ldc)) {     // the choice check_bits_gemm makes, before alignment
+    case BITS_TILE: return "bits_tile";
+    case BITS_INVALID: return "invalid";
+    default: return "bits_plain";
+  }
+}
+
+const char *mm_kernel_name_bits_closure(unsigned n, unsigned batch) {
+  (void)batch;
+  return n <= kBitsClosureBlock ? "bits_closure_onchip" : "bits_closure_blocked";
 }
 
 int mm_kernel_info(const mm_config_t *cfg, unsigned n, unsigned k, unsigned m, mm_kernel_info_t *info) {

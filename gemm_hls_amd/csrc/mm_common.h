@@ -179,6 +179,36 @@ struct ClosureStep {
   int w_fresh;
 };
 int launch_closure(hipStream_t s, const mm_config_t &cfg, const ClosureStep &st);
+// Bit-packed Boolean product (mm_bits_gemm_*, mm_bits.hip): the p.batch elements of p, every ld and batch stride in words;
+// seed: C <- C | A B.  tile: "bits_tile" (bits_tile_serves() on the ld's, b 16-byte and c 8-byte aligned per element), else
+// "bits_plain" (anything).
+struct BitsProblem {
+  const uint32_t *a, *b;
+  uint32_t *c;
+  unsigned n, k, m;
+  size_t lda, ldb, ldc;
+  unsigned batch;
+  size_t stride_a, stride_b, stride_c;
+  bool seed;
+};
+bool bits_tile_serves(size_t ldb, size_t ldc);   // the ld half of the serving rule; the M half is mm_capi.hip's (a knob lifts it)
+int launch_bits_gemm(hipStream_t s, const BitsProblem &p, bool tile);
+// pack: src bytes -> dst words; unpack: src words -> dst bytes (0 / 1).  ld and batch strides in each side's own unit.
+struct BitsConvert {
+  const void *src;
+  void *dst;
+  unsigned rows, cols;
+  size_t ld_src, ld_dst;
+  unsigned batch;
+  size_t stride_src, stride_dst;
+};
+int launch_bits_pack(hipStream_t s, const BitsConvert &c);
+int launch_bits_unpack(hipStream_t s, const BitsConvert &c);
+// The wavefront kernel of the packed closure (mm_bits_closure.hip): closes block [k0, k0 + min(64, n - k0)) of `graphs` graphs
+// at d + e * stride_d.  pstar null: writes the closed block back into D (the on-chip closure, k0 = 0, n <= 64); else leaves D
+// alone and writes P | I as 64 rows x 2 words at pstar + e * stride_p.
+int launch_bits_closure_diag(hipStream_t s, uint32_t *d, unsigned n, size_t ldd, unsigned graphs, size_t stride_d, unsigned k0,
+                             uint32_t *pstar, size_t stride_p);
 // Log-semiring product (mm_gemm_logsumexp_*, mm_lse_fp.hip).  launch_lse_exact: the exact kernel over the p.batch elements of
 // p (p.seed: C's input is one more term); flags != null: the hybrid's fallback, tile t of element e runs only where
 // flags[e * tiles + t] != 0 (64 x 64 tiles); p.b_transposed: launch_lse_exact_nt, "lse_exact_nt" (mm_lse_nt_fp.hip).  The hybrid's prepass transforms `count` elements of one operand: r = the
@@ -372,6 +402,8 @@ enum Tunable {
   TUNE_CLOSURE_BLOCK,      // MM_CLOSURE_BLOCK  block size B of mm_closure_* (64, 128, or 256 where the form allows it); -1: the default
   TUNE_LSE_VARIANT,        // MM_LSE_VARIANT  mm_gemm_logsumexp_*: 0 exact kernel only, 1 hybrid, 2 hybrid with every tile sent to
                            //                 the fallback (the cross-check); -1: the default (hybrid)
+  TUNE_BITS_VARIANT,       // MM_BITS_VARIANT  mm_bits_gemm_*: 0 bits_plain always, 1 bits_tile wherever its ld rule holds (any M);
+                           //                 -1: the default (bits_tile for M > 2048)
   TUNE_COUNT
 };
 int tuning(Tunable t);  // mm_capi.hip

@@ -495,6 +495,74 @@ int mm_closure_launch(int device, const mm_config_t *cfg, void *d_dev, int *witn
  * "invalid" for a bad configuration, MM_A_TRANSPOSED or a closure_block this form does not take.  Pure arithmetic. */
 const char *mm_kernel_name_closure(const mm_config_t *cfg, unsigned n, unsigned batch, int with_witness);
 
+/* ---- bit-packed Boolean semiring: (AND, OR) on one bit per element -------------------------------------------------------
+ * Storage format (the contract of every mm_bits_* call).  A Boolean rows x cols matrix is `rows` rows of 32-bit words:
+ * column j is bit (j & 31) of word (j >> 5), least significant bit first -- on the host
+ * np.packbits(x, axis=-1, bitorder="little"), padded to a multiple of 4 bytes and viewed as uint32.  Each operand has a row
+ * stride ld in WORDS, ld >= ceil(cols / 32), so a column slice of a packed matrix (whole words) and a panel of a larger
+ * matrix are operands as they lie.  Padding bits -- positions >= cols in a row's last word -- are ignored in every input,
+ * whatever they hold, and written as 0 in every output.  The words of a row beyond ceil(cols / 32), up to ld, are never
+ * read and never written.  Pointers are 4-byte aligned; batch strides count words.
+ *
+ * Product: C[e,i,j] = OR_k (A[e,i,k] AND B[e,k,j]); a: N x K packed along K, b: K x M packed along M, c: N x M packed along
+ * M.  accumulate != 0: C <- C | A B (the valid bits of C's input are kept, its padding bits are dropped).  stride_a or
+ * stride_b 0 = one operand shared by the batch; with batch > 1, stride_c >= (N - 1) ldc + ceil(M / 32).  batch, N or M 0:
+ * MM_OK, nothing done (_launch reports 0 s); so is K = 0 when accumulating; K = 0 in the plain form writes C = 0, the
+ * empty OR (a and b are then not read and may be null).  Refused with MM_ERR_BAD_ARGUMENT before any device is touched: a
+ * null pointer, an ld below its row's word count, outputs of the batch that would overlap, and a span of C -- [base, base +
+ * (batch - 1) stride + (rows - 1) ld + words) -- that overlaps A's or B's.
+ * Kernels (mm_kernel_name_bits_gemm; pure arithmetic, the launcher's own resolver):
+ *   "bits_tile"   64 rows x 128 words of C per workgroup, K streamed through LDS in slabs of 32; a thread holds 16 rows x 2
+ *                 words, forms each row's mask from A's bit with one scalar instruction and does acc |= mask & b.  Serves
+ *                 M > 2048 with ldb % 4 == 0 and ldc % 2 == 0 (16-byte loads of B, 8-byte loads and stores of C).
+ *   "bits_plain"  the same loop on 64 rows x 64 words with one-word accesses: every shape, every ld, any 4-byte aligned
+ *                 pointer.
+ * Knob "bits_variant" (MM_BITS_VARIANT): -1 the rule above, 0 bits_plain always, 1 bits_tile wherever its ld rule holds,
+ * whatever M; any other value: MM_ERR_BAD_ARGUMENT ("invalid" as a name).  The name is decided by shape and ld alone: a
+ * bits_tile launch whose b is not 16-byte aligned or whose c is not 8-byte aligned -- base, or batch stride -- runs
+ * bits_plain instead, the same bits, no error.  All-zero words of A are skipped: the time depends on the data, the result
+ * does not.  The batch is launched in chunks (knob "batch_chunk").
+ * _enqueue: asynchronous on a hipStream_t of the CURRENT device, never synchronises the host; _launch: blocking,
+ * *elapsed_seconds (may be NULL) timed with HIP events. */
+int mm_bits_gemm_enqueue(void *hip_stream, const void *a_dev, const void *b_dev, void *c_dev, unsigned size_n, unsigned size_k,
+                         unsigned size_m, size_t lda, size_t ldb, size_t ldc, unsigned batch, size_t stride_a,
+                         size_t stride_b, size_t stride_c, int accumulate);
+int mm_bits_gemm_launch(int device, const void *a_dev, const void *b_dev, void *c_dev, unsigned size_n, unsigned size_k,
+                        unsigned size_m, size_t lda, size_t ldb, size_t ldc, unsigned batch, size_t stride_a,
+                        size_t stride_b, size_t stride_c, int accumulate, double *elapsed_seconds);
+const char *mm_kernel_name_bits_gemm(unsigned size_n, unsigned size_k, unsigned size_m, size_t lda, size_t ldb, size_t ldc,
+                                     unsigned batch);
+
+/* Transitive closure, in place: D <- D+, (i, j) set when a path of one or more edges leads from i to j.  No identity is
+ * added to the diagonal, as in mm_closure_*.  OR is idempotent, so the result does not depend on the algorithm.  d: n x n
+ * packed, row stride ldd >= ceil(n / 32) words; graph e at d_dev + e * stride_d (stride_d >= (n - 1) ldd + ceil(n / 32)
+ * when batch > 1).  Kernels (mm_kernel_name_bits_closure): "bits_closure_onchip" for n <= 64 -- one wavefront per graph,
+ * one row per lane, the pivot row by broadcast; four graphs per workgroup, 2^20 graphs per launch -- else
+ * "bits_closure_blocked": blocked Warshall over blocks K of 64 vertices; per block the wavefront kernel closes D[K,K] into P
+ * and writes P | I to workspace, the product kernels take R = (P | I) D[K,:] and Cc = D[:,K] (P | I) into workspace (the
+ * panels as the round leaves them), and D <- D | Cc R runs as the accumulating product with ld = ldd.  The workspace (about
+ * 66 ceil(n / 32) + 2 n words per graph) comes from the library's stream-ordered pool; the batch is chunked to keep it near
+ * 256 MiB and by "batch_chunk".  Refused before any device is touched: a null d_dev, ldd < ceil(n / 32), overlapping graphs
+ * (MM_ERR_BAD_ARGUMENT).  n or batch 0: MM_OK, nothing done.  _enqueue / _launch as above. */
+int mm_bits_closure_enqueue(void *hip_stream, void *d_dev, unsigned n, size_t ldd, unsigned batch, size_t stride_d);
+int mm_bits_closure_launch(int device, void *d_dev, unsigned n, size_t ldd, unsigned batch, size_t stride_d,
+                           double *elapsed_seconds);
+const char *mm_kernel_name_bits_closure(unsigned n, unsigned batch);
+
+/* Conversions between a row-major matrix of one-byte elements (bool, uint8_t; row stride ld in BYTES, batch stride in bytes)
+ * and the packed form (row stride and batch stride in words).  pack: a nonzero byte is 1, padding bits are written 0;
+ * unpack writes 0 or 1.  Only ceil(cols / 32) words and cols bytes of a row are touched.  Refused before any device is
+ * touched: a null pointer, an ld below its row, a destination whose rows or batch elements would overlap, and a
+ * destination span overlapping the source's (MM_ERR_BAD_ARGUMENT).  rows, cols or batch 0: MM_OK, nothing done. */
+int mm_bits_pack_enqueue(void *hip_stream, const void *bytes_dev, void *packed_dev, unsigned rows, unsigned cols,
+                         size_t ld_bytes, size_t ld_packed, unsigned batch, size_t stride_bytes, size_t stride_packed);
+int mm_bits_pack_launch(int device, const void *bytes_dev, void *packed_dev, unsigned rows, unsigned cols, size_t ld_bytes,
+                        size_t ld_packed, unsigned batch, size_t stride_bytes, size_t stride_packed, double *elapsed_seconds);
+int mm_bits_unpack_enqueue(void *hip_stream, const void *packed_dev, void *bytes_dev, unsigned rows, unsigned cols,
+                           size_t ld_packed, size_t ld_bytes, unsigned batch, size_t stride_packed, size_t stride_bytes);
+int mm_bits_unpack_launch(int device, const void *packed_dev, void *bytes_dev, unsigned rows, unsigned cols, size_t ld_packed,
+                          size_t ld_bytes, unsigned batch, size_t stride_packed, size_t stride_bytes, double *elapsed_seconds);
+
 /* One node, `device_count` GPUs, rows of C split into contiguous slabs (device g gets the rows mm_row_slab() names), B
  * replicated, no collective: every outer tile of C is independent (kernel/Compute.cpp:53-60, kernel/Memory.cpp:114-127,
  * 272-286, 367-391).  Host pointers in, host pointer out; copies are outside the timed region exactly as in
@@ -590,6 +658,7 @@ int mm_kernel_info(const mm_config_t *cfg, unsigned size_n, unsigned size_k, uns
  * 0.2-30 % slower (its release fence writes the L2 back; profiles/r06d_*), kept as the cross-check of the shipped flag protocol; 9 stream-K in
  * single ranges with its own fix-up kernel (cross-check, its own bits).
  * "closure_block": the block size of mm_closure_* (see there).  "lse_variant": the kernels of mm_gemm_logsumexp_* (see there).
+ * "bits_variant": the kernels of mm_bits_gemm_* (see there).
  * "debug_poison" = 1 fills the scratch that kernels hand partial tiles through, and C itself (pure output), with NaN before
  * every stream-K launch: a read of anything the launch did not write, or a tile nobody finished, then shows in C (tests only).  "md_virtual_devices": see mm_gemm_multi_device.  Any
  * other id is refused: the retired schedules and the work-skipping ablations of the measurement history exist only in the
