@@ -75,85 +75,53 @@ def lib():
             pass
         L = ctypes.CDLL(LIB_PATH)
         vp, u, i, sz = ctypes.c_void_p, ctypes.c_uint, ctypes.c_int, ctypes.c_size_t
-        cfgp = ctypes.POINTER(Config)
+        cfgp, dp = ctypes.POINTER(Config), ctypes.POINTER(ctypes.c_double)
         L.mm_init.argtypes = [ctypes.POINTER(i)]
         L.mm_alloc.argtypes = [i, sz, ctypes.POINTER(vp)]
         L.mm_free.argtypes = [i, vp]
         L.mm_copy_to_device.argtypes = [i, vp, vp, sz]
         L.mm_copy_to_host.argtypes = [i, vp, vp, sz]
         L.mm_fill_device.argtypes = [i, i, vp, sz, ctypes.c_ulonglong]
-        L.mm_gemm_launch.argtypes = [i, cfgp, vp, vp, vp, u, u, u, ctypes.POINTER(ctypes.c_double)]
-        L.mm_gemm_enqueue.argtypes = [vp, cfgp, vp, vp, vp, u, u, u]
-        L.mm_gemm_multi_device.argtypes = [i, cfgp, vp, vp, vp, u, u, u, ctypes.POINTER(ctypes.c_double)]
-        L.mm_gemm_multi_device_timed.argtypes = [i, cfgp, vp, vp, vp, u, u, u, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double),
-                                                 ctypes.POINTER(ctypes.c_double)]
+        # Every <stem>_enqueue(stream, ...) has a blocking <stem>_launch(device, ..., double *elapsed_seconds): the arguments
+        # between, once per pair
+        gemm = [cfgp, vp, vp, vp, u, u, u]                  # a, b, c, n, k, m
+        batched = gemm + [u, sz, sz, sz]                    # ..., batch, stride_a, stride_b, stride_c
+        seeded = batched + [i]                              # ..., accumulate
+        argreduce = [cfgp, vp, vp, vp, vp] + batched[4:] + [i, i]   # a, b, c, c_index, ..., index_base, accumulate
+        convert = [vp, vp, u, u, sz, sz, u, sz, sz]
+        pairs = {"mm_gemm": gemm, "mm_gemm_accumulate": gemm, "mm_gemm_batched": batched, "mm_gemm_batched_accumulate": batched,
+                 "mm_gemm_argreduce": argreduce, "mm_gemm_argreduce_nt": argreduce, "mm_gemm_logsumexp": seeded,
+                 "mm_gemm_logsumexp_nt": seeded, "mm_gemm_widen": seeded, "mm_gemm_nt": seeded,
+                 "mm_closure": [cfgp, vp, vp, u, u, sz], "mm_bits_gemm": [vp, vp, vp, u, u, u, sz, sz, sz, u, sz, sz, sz, i],
+                 "mm_bits_closure": [vp, u, sz, u, sz], "mm_bits_pack": convert, "mm_bits_unpack": convert}
+        for stem, between in pairs.items():
+            getattr(L, stem + "_enqueue").argtypes = [vp] + between
+            getattr(L, stem + "_launch").argtypes = [i] + between + [dp]
+        # mm_kernel_name<suffix>(...): a string
+        shape = [cfgp, u, u, u]
+        names = {"": shape, "_closure": [cfgp, u, u, i], "_bits_gemm": [u, u, u, sz, sz, sz, u], "_bits_closure": [u, u]}
+        names.update((suffix, shape + [u]) for suffix in ("_batched", "_argreduce", "_logsumexp", "_widen", "_nt", "_argreduce_nt",
+                                                          "_logsumexp_nt"))
+        for suffix, args in names.items():
+            fn = getattr(L, "mm_kernel_name" + suffix)
+            fn.argtypes, fn.restype = args, ctypes.c_char_p
+        L.mm_gemm_multi_device.argtypes = [i] + gemm + [dp]
+        L.mm_gemm_multi_device_timed.argtypes = [i] + gemm + [dp, dp, dp]
         L.MatrixMultiplicationKernel.argtypes = [vp, vp, vp, u, u, u]
         L.MatrixMultiplicationKernel.restype = None
         L.mm_set_default_config.argtypes = [cfgp]
         L.mm_dtype_size.argtypes = [i]
         L.mm_dtype_size.restype = sz
         L.mm_config_supported.argtypes = [cfgp]
-        L.mm_kernel_name.argtypes = [cfgp, u, u, u]
-        L.mm_kernel_name.restype = ctypes.c_char_p
-        L.mm_kernel_info.argtypes = [cfgp, u, u, u, ctypes.POINTER(KernelInfo)]
+        L.mm_kernel_info.argtypes = shape + [ctypes.POINTER(KernelInfo)]
         L.mm_last_error.restype = ctypes.c_char_p
-        L.mm_gemm_host.argtypes = [cfgp, vp, vp, vp, u, u, u]
+        L.mm_gemm_host.argtypes = gemm
         L.mm_tuning_set.argtypes = [ctypes.c_char_p, i]
         L.mm_tuning_get.argtypes = [ctypes.c_char_p, ctypes.POINTER(i)]
         L.mm_release_workspace.argtypes = [i]
         L.mm_device_pci_bus_id.argtypes = [i, ctypes.c_char_p, i]
-        L.mm_row_slab.argtypes = [cfgp, u, u, u, i, i, ctypes.POINTER(u), ctypes.POINTER(u)]
-        L.mm_gemm_batched_enqueue.argtypes = [vp, cfgp, vp, vp, vp, u, u, u, u, sz, sz, sz]
-        L.mm_gemm_batched_launch.argtypes = [i, cfgp, vp, vp, vp, u, u, u, u, sz, sz, sz, ctypes.POINTER(ctypes.c_double)]
-        L.mm_kernel_name_batched.argtypes = [cfgp, u, u, u, u]
-        L.mm_kernel_name_batched.restype = ctypes.c_char_p
-        L.mm_gemm_accumulate_enqueue.argtypes = [vp, cfgp, vp, vp, vp, u, u, u]
-        L.mm_gemm_accumulate_launch.argtypes = [i, cfgp, vp, vp, vp, u, u, u, ctypes.POINTER(ctypes.c_double)]
-        L.mm_gemm_batched_accumulate_enqueue.argtypes = [vp, cfgp, vp, vp, vp, u, u, u, u, sz, sz, sz]
-        L.mm_gemm_batched_accumulate_launch.argtypes = [i, cfgp, vp, vp, vp, u, u, u, u, sz, sz, sz,
-                                                        ctypes.POINTER(ctypes.c_double)]
-        L.mm_gemm_argreduce_enqueue.argtypes = [vp, cfgp, vp, vp, vp, vp, u, u, u, u, sz, sz, sz, i, i]
-        L.mm_gemm_argreduce_launch.argtypes = [i, cfgp, vp, vp, vp, vp, u, u, u, u, sz, sz, sz, i, i,
-                                               ctypes.POINTER(ctypes.c_double)]
-        L.mm_kernel_name_argreduce.argtypes = [cfgp, u, u, u, u]
-        L.mm_kernel_name_argreduce.restype = ctypes.c_char_p
-        L.mm_closure_enqueue.argtypes = [vp, cfgp, vp, vp, u, u, sz]
-        L.mm_closure_launch.argtypes = [i, cfgp, vp, vp, u, u, sz, ctypes.POINTER(ctypes.c_double)]
-        L.mm_kernel_name_closure.argtypes = [cfgp, u, u, i]
-        L.mm_kernel_name_closure.restype = ctypes.c_char_p
-        L.mm_gemm_logsumexp_enqueue.argtypes = [vp, cfgp, vp, vp, vp, u, u, u, u, sz, sz, sz, i]
-        L.mm_gemm_logsumexp_launch.argtypes = [i, cfgp, vp, vp, vp, u, u, u, u, sz, sz, sz, i, ctypes.POINTER(ctypes.c_double)]
-        L.mm_kernel_name_logsumexp.argtypes = [cfgp, u, u, u, u]
-        L.mm_kernel_name_logsumexp.restype = ctypes.c_char_p
-        L.mm_gemm_widen_enqueue.argtypes = [vp, cfgp, vp, vp, vp, u, u, u, u, sz, sz, sz, i]
-        L.mm_gemm_widen_launch.argtypes = [i, cfgp, vp, vp, vp, u, u, u, u, sz, sz, sz, i, ctypes.POINTER(ctypes.c_double)]
-        L.mm_kernel_name_widen.argtypes = [cfgp, u, u, u, u]
-        L.mm_kernel_name_widen.restype = ctypes.c_char_p
+        L.mm_row_slab.argtypes = shape + [i, i, ctypes.POINTER(u), ctypes.POINTER(u)]
         L.mm_widen_dtype.argtypes = [i]
-        L.mm_gemm_nt_enqueue.argtypes = [vp, cfgp, vp, vp, vp, u, u, u, u, sz, sz, sz, i]
-        L.mm_gemm_nt_launch.argtypes = [i, cfgp, vp, vp, vp, u, u, u, u, sz, sz, sz, i, ctypes.POINTER(ctypes.c_double)]
-        L.mm_kernel_name_nt.argtypes = [cfgp, u, u, u, u]
-        L.mm_kernel_name_nt.restype = ctypes.c_char_p
-        L.mm_gemm_argreduce_nt_enqueue.argtypes = L.mm_gemm_argreduce_enqueue.argtypes
-        L.mm_gemm_argreduce_nt_launch.argtypes = L.mm_gemm_argreduce_launch.argtypes
-        L.mm_kernel_name_argreduce_nt.argtypes = [cfgp, u, u, u, u]
-        L.mm_kernel_name_argreduce_nt.restype = ctypes.c_char_p
-        L.mm_gemm_logsumexp_nt_enqueue.argtypes = L.mm_gemm_logsumexp_enqueue.argtypes
-        L.mm_gemm_logsumexp_nt_launch.argtypes = L.mm_gemm_logsumexp_launch.argtypes
-        L.mm_kernel_name_logsumexp_nt.argtypes = [cfgp, u, u, u, u]
-        L.mm_kernel_name_logsumexp_nt.restype = ctypes.c_char_p
-        L.mm_bits_gemm_enqueue.argtypes = [vp, vp, vp, vp, u, u, u, sz, sz, sz, u, sz, sz, sz, i]
-        L.mm_bits_gemm_launch.argtypes = [i, vp, vp, vp, u, u, u, sz, sz, sz, u, sz, sz, sz, i, ctypes.POINTER(ctypes.c_double)]
-        L.mm_kernel_name_bits_gemm.argtypes = [u, u, u, sz, sz, sz, u]
-        L.mm_kernel_name_bits_gemm.restype = ctypes.c_char_p
-        L.mm_bits_closure_enqueue.argtypes = [vp, vp, u, sz, u, sz]
-        L.mm_bits_closure_launch.argtypes = [i, vp, u, sz, u, sz, ctypes.POINTER(ctypes.c_double)]
-        L.mm_kernel_name_bits_closure.argtypes = [u, u]
-        L.mm_kernel_name_bits_closure.restype = ctypes.c_char_p
-        L.mm_bits_pack_enqueue.argtypes = [vp, vp, vp, u, u, sz, sz, u, sz, sz]
-        L.mm_bits_pack_launch.argtypes = [i, vp, vp, u, u, sz, sz, u, sz, sz, ctypes.POINTER(ctypes.c_double)]
-        L.mm_bits_unpack_enqueue.argtypes = L.mm_bits_pack_enqueue.argtypes
-        L.mm_bits_unpack_launch.argtypes = L.mm_bits_pack_launch.argtypes
         _lib = L
     return _lib
 
@@ -171,10 +139,15 @@ def _enqueue(device, fn, *args):
         _check(fn(ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream), *args))
 
 
-def _check_out(x, name, shape, dtype, device):
+def _output(x, name, shape, dtype, device):
+    """The caller's output `x`, checked, or a new one: a contiguous `dtype` tensor of `shape` on `device`."""
+    if x is None:
+        import torch
+        return torch.empty(shape, dtype=dtype, device=device)
     if tuple(x.shape) != shape or x.dtype != dtype or x.device != device or not x.is_contiguous():
         raise MMError(f"{name} must be a contiguous {dtype} tensor of shape {shape} on {device}; got "
                       f"{tuple(x.shape)}, {x.dtype}, {x.device}, contiguous={x.is_contiguous()}")
+    return x
 
 
 def make_config(dtype="float", map_op="Multiply", reduce_op="Add", path=PATH_AUTO, transposed_a=False):
@@ -187,40 +160,36 @@ def device_count():
     return n.value
 
 
+def _kernel_name(suffix, cfg, *args):
+    return getattr(lib(), "mm_kernel_name" + suffix)(ctypes.byref(cfg), *args).decode()
+
+
+def _batched_kernel_name(suffix):
+    """kernel_name<suffix>(cfg, n, k, m, batch=1): the kernel the calls of that family run."""
+    def name(cfg, n, k, m, batch=1):
+        return _kernel_name(suffix, cfg, n, k, m, batch)
+    name.__name__ = name.__qualname__ = "kernel_name" + suffix
+    return name
+
+
 def kernel_name(cfg, n, k, m):
-    return lib().mm_kernel_name(ctypes.byref(cfg), n, k, m).decode()
+    return _kernel_name("", cfg, n, k, m)
 
 
 def kernel_name_batched(cfg, n, k, m, batch):
-    return lib().mm_kernel_name_batched(ctypes.byref(cfg), n, k, m, batch).decode()
-
-
-def kernel_name_argreduce(cfg, n, k, m, batch=1):
-    return lib().mm_kernel_name_argreduce(ctypes.byref(cfg), n, k, m, batch).decode()
+    return _kernel_name("_batched", cfg, n, k, m, batch)
 
 
 def kernel_name_closure(cfg, n, batch=1, with_witness=False):
-    return lib().mm_kernel_name_closure(ctypes.byref(cfg), n, batch, int(bool(with_witness))).decode()
+    return _kernel_name("_closure", cfg, n, batch, int(bool(with_witness)))
 
 
-def kernel_name_logsumexp(cfg, n, k, m, batch=1):
-    return lib().mm_kernel_name_logsumexp(ctypes.byref(cfg), n, k, m, batch).decode()
-
-
-def kernel_name_widen(cfg, n, k, m, batch=1):
-    return lib().mm_kernel_name_widen(ctypes.byref(cfg), n, k, m, batch).decode()
-
-
-def kernel_name_nt(cfg, n, k, m, batch=1):
-    return lib().mm_kernel_name_nt(ctypes.byref(cfg), n, k, m, batch).decode()
-
-
-def kernel_name_argreduce_nt(cfg, n, k, m, batch=1):
-    return lib().mm_kernel_name_argreduce_nt(ctypes.byref(cfg), n, k, m, batch).decode()
-
-
-def kernel_name_logsumexp_nt(cfg, n, k, m, batch=1):
-    return lib().mm_kernel_name_logsumexp_nt(ctypes.byref(cfg), n, k, m, batch).decode()
+kernel_name_argreduce = _batched_kernel_name("_argreduce")
+kernel_name_logsumexp = _batched_kernel_name("_logsumexp")
+kernel_name_widen = _batched_kernel_name("_widen")
+kernel_name_nt = _batched_kernel_name("_nt")
+kernel_name_argreduce_nt = _batched_kernel_name("_argreduce_nt")
+kernel_name_logsumexp_nt = _batched_kernel_name("_logsumexp_nt")
 
 
 def widen_dtype(dtype):
@@ -261,31 +230,43 @@ def torch_dtype(dtype):
     return _TORCH_DTYPES[dtype]
 
 
+def _device_operands(what, tdt, *xs):
+    """The checks every torch entry point makes: device tensors of one device and of the configuration's dtype."""
+    if not all(x.is_cuda for x in xs):
+        raise MMError(f"{what} needs device tensors: there is no CPU path")
+    if any(x.device != xs[0].device for x in xs):
+        raise MMError(f"operands live on different devices: {', '.join(str(x.device) for x in xs)}")
+    if any(x.dtype != tdt for x in xs):
+        raise MMError(f"operand dtypes {', '.join(str(x.dtype) for x in xs)} do not match {tdt}")
+
+
+def _inner_mismatch(a, b, transposed_a=False, nt=False):
+    return MMError(f"inner dimensions differ: A {tuple(a.shape)}{' (K x N)' if transposed_a else ''}, B {tuple(b.shape)}"
+                   f"{' (M, K)' if nt else ''}")
+
+
+def _matrix_shapes(what, transposed_a, a, b, *c):
+    """(n, k, m) of matmul's and addmm_'s operands, which the single-launch calls take 2-D and contiguous only."""
+    if any(x.dim() != 2 for x in (a, b) + c):
+        raise MMError(f"{what} takes 2-D operands")
+    if not all(x.is_contiguous() for x in (a, b) + c):
+        raise MMError(f"{what} needs contiguous (row-major) operands")
+    k, m = b.shape
+    n, ka = reversed(a.shape) if transposed_a else a.shape
+    if ka != k:
+        raise _inner_mismatch(a, b, transposed_a)
+    return n, k, m
+
+
 def matmul(a, b, dtype="float", map_op="Multiply", reduce_op="Add", path=PATH_AUTO, transposed_a=False,
            out=None):
     """C = A (map, reduce) B on the current CUDA(HIP) device and torch's current stream.
     a: (N, K) -- or (K, N) with transposed_a -- b: (K, M); contiguous device tensors whose torch
     dtype matches `dtype`.  Asynchronous, like any torch op."""
-    import torch
-    if not (a.is_cuda and b.is_cuda):
-        raise MMError("matmul needs device tensors: there is no CPU path")
-    if a.device != b.device:
-        raise MMError(f"operands live on different devices: {a.device} and {b.device}")
     tdt = torch_dtype(dtype)
-    if not (a.is_contiguous() and b.is_contiguous()):
-        raise MMError("matmul needs contiguous (row-major) operands")
-    if a.dtype != tdt or b.dtype != tdt:
-        raise MMError(f"operand dtypes {a.dtype}, {b.dtype} do not match Data_t={dtype} ({tdt})")
-    if a.dim() != 2 or b.dim() != 2:
-        raise MMError("matmul takes 2-D operands")
-    k, m = b.shape
-    n = a.shape[1] if transposed_a else a.shape[0]
-    if (a.shape[0] if transposed_a else a.shape[1]) != k:
-        raise MMError(f"inner dimensions differ: A {tuple(a.shape)}{' (K x N)' if transposed_a else ''}, B {tuple(b.shape)}")
-    if out is None:
-        out = torch.empty((n, m), dtype=tdt, device=a.device)
-    else:
-        _check_out(out, "out", (n, m), tdt, a.device)
+    _device_operands("matmul", tdt, a, b)
+    n, k, m = _matrix_shapes("matmul", transposed_a, a, b)
+    out = _output(out, "out", (n, m), tdt, a.device)
     cfg = make_config(dtype, map_op, reduce_op, path, transposed_a)
     _enqueue(a.device, lib().mm_gemm_enqueue, ctypes.byref(cfg), a.data_ptr(), b.data_ptr(), out.data_ptr(), n, k, m)
     return out
@@ -308,16 +289,17 @@ def _batched_operand(x, name, rows, cols):
     return x.shape[0], (0 if x.shape[0] == 1 else x.stride(0))
 
 
-def _bmm_shapes(what, a, b, transposed_a):
-    """(n, k, m, batch, stride_a, stride_b) of bmm-style operands: 2-D, 3-D, or expanded with batch stride 0."""
+def _shapes(what, a, b, transposed_a=False, nt=False):
+    """(n, k, m, batch, stride_a, stride_b) of bmm-style operands: 2-D, 3-D, or expanded with batch stride 0.  a: (N, K), or
+    (K, N) with transposed_a; b: (K, M), or (M, K) with nt (the A x B^T forms)."""
     if a.dim() not in (2, 3) or b.dim() not in (2, 3):
         raise MMError(f"{what} takes 2-D or 3-D operands")
-    k, m = b.shape[-2], b.shape[-1]
-    n = a.shape[-1] if transposed_a else a.shape[-2]
-    if (a.shape[-2] if transposed_a else a.shape[-1]) != k:
-        raise MMError(f"inner dimensions differ: A {tuple(a.shape)}{' (K x N)' if transposed_a else ''}, B {tuple(b.shape)}")
-    ba, sa = _batched_operand(a, "a", *((k, n) if transposed_a else (n, k)))
-    bb, sb = _batched_operand(b, "b", k, m)
+    n, ka = reversed(a.shape[-2:]) if transposed_a else a.shape[-2:]
+    m, k = reversed(b.shape[-2:]) if not nt else b.shape[-2:]
+    if ka != k:
+        raise _inner_mismatch(a, b, transposed_a, nt)
+    ba, sa = _batched_operand(a, "a", *a.shape[-2:])
+    bb, sb = _batched_operand(b, "b (M, K)" if nt else "b", *b.shape[-2:])
     batches = {x for x in (ba, bb) if x is not None and x != 1}
     if len(batches) > 1:
         raise MMError(f"batch sizes differ: {ba} and {bb}")
@@ -336,38 +318,63 @@ def _inplace_batch(c, n, m, batch):
     return batch, sc
 
 
+def _widen_types(what, dtype):
+    wide = widen_dtype(dtype)
+    if wide is None:
+        raise MMError(f"{what} takes half or int8_t operands (got {dtype})")
+    return torch_dtype(dtype), torch_dtype(wide)
+
+
+def _product(what, symbol, a, b, dtype, map_op, reduce_op, path, transposed_a=False, *, nt=False, wide=False, indexed=False,
+             index_base=0, c=None, c_index=None, out=None, out_index=None, flag=True, batched_out=False):
+    """The skeleton of every batched product wrapper: check the operands, derive the shapes, check or allocate the outputs,
+    enqueue lib().<symbol>.  A new wrapper is a call of this.
+
+    dtype ... transposed_a: make_config's arguments.  nt: b is (M, K).  wide: C has the widened type of `dtype`.  indexed:
+    an int32 index lies beside C, and index_base is passed on.  c (and c_index): the in-place form, which accumulates;
+    otherwise the result is out (and out_index) or new, (N, M) when both operands are 2-D, else (B, N, M).  bmm and
+    baddbmm_ alone set batched_out (a 3-D result always) or clear flag (their C calls do not end in the accumulate flag).
+    Returns C, or (C, index)."""
+    import torch
+    tdt, cdt = _widen_types(what, dtype) if wide else (torch_dtype(dtype),) * 2
+    in_place = c is not None
+    if in_place and wide:
+        _device_operands(what, tdt, a, b)
+        _device_operands(what, cdt, c)
+        if c.device != a.device:
+            raise MMError(f"operands live on different devices: {c.device}, {a.device}")
+    else:
+        _device_operands(what, tdt, *((c, a, b) if in_place else (a, b)))
+    if in_place:
+        if indexed and (not c_index.is_cuda or c_index.device != c.device or c_index.dtype != torch.int32):
+            raise MMError(f"c_index must be a torch.int32 tensor on {c.device}; got {c_index.dtype} on {c_index.device}")
+        if c.dim() not in (2, 3):
+            raise MMError(f"{what} takes 2-D or 3-D operands")
+        if indexed and (tuple(c_index.shape) != tuple(c.shape) or c_index.stride() != c.stride()):
+            raise MMError(f"c_index must have c's shape and strides: {tuple(c.shape)} {c.stride()}, got "
+                          f"{tuple(c_index.shape)} {c_index.stride()}")
+    n, k, m, batch, sa, sb = _shapes(what, a, b, transposed_a, nt)
+    if in_place:
+        batch, sc = _inplace_batch(c, n, m, batch)
+        index = c_index
+    else:
+        shape = (n, m) if a.dim() == 2 and b.dim() == 2 and not batched_out else (batch, n, m)
+        c, sc = _output(out, "out", shape, cdt, a.device), n * m
+        index = _output(out_index, "out_index", shape, torch.int32, a.device) if indexed else None
+    config = make_config(dtype, map_op, reduce_op, path, transposed_a)
+    _enqueue(a.device, getattr(lib(), symbol), ctypes.byref(config), a.data_ptr(), b.data_ptr(), c.data_ptr(),
+             *((index.data_ptr(),) if indexed else ()), n, k, m, batch, sa, sb, sc, *((int(index_base),) if indexed else ()),
+             *((int(in_place),) if flag else ()))
+    return (c, index) if indexed else c
+
+
 def bmm(a, b, dtype="float", map_op="Multiply", reduce_op="Add", path=PATH_AUTO, transposed_a=False, out=None):
     """Strided-batched C[e] = A[e] (map, reduce) B[e] on torch's current stream (mm_gemm_batched_enqueue).
     a: (B, N, K) -- or (B, K, N) with transposed_a -- b: (B, K, M); either may be 2-D or expanded with batch stride 0
     (one operand shared by the batch).  Each matrix must be dense row-major; the batch stride may be anything the C ABI
     accepts.  out: (B, N, M) contiguous.  Asynchronous, like any torch op."""
-    import torch
-    if not (a.is_cuda and b.is_cuda):
-        raise MMError("bmm needs device tensors: there is no CPU path")
-    if a.device != b.device:
-        raise MMError(f"operands live on different devices: {a.device} and {b.device}")
-    tdt = torch_dtype(dtype)
-    if a.dtype != tdt or b.dtype != tdt:
-        raise MMError(f"operand dtypes {a.dtype}, {b.dtype} do not match Data_t={dtype} ({tdt})")
-    n, k, m, batch, sa, sb = _bmm_shapes("bmm", a, b, transposed_a)
-    if out is None:
-        out = torch.empty((batch, n, m), dtype=tdt, device=a.device)
-    else:
-        _check_out(out, "out", (batch, n, m), tdt, a.device)
-    cfg = make_config(dtype, map_op, reduce_op, path, transposed_a)
-    _enqueue(a.device, lib().mm_gemm_batched_enqueue, ctypes.byref(cfg), a.data_ptr(), b.data_ptr(), out.data_ptr(),
-             n, k, m, batch, sa, sb, n * m)
-    return out
-
-
-def _device_operands(what, tdt, *xs):
-    """The checks every torch entry point makes: device tensors of one device and of the configuration's dtype."""
-    if not all(x.is_cuda for x in xs):
-        raise MMError(f"{what} needs device tensors: there is no CPU path")
-    if any(x.device != xs[0].device for x in xs):
-        raise MMError(f"operands live on different devices: {', '.join(str(x.device) for x in xs)}")
-    if any(x.dtype != tdt for x in xs):
-        raise MMError(f"operand dtypes {', '.join(str(x.dtype) for x in xs)} do not match {tdt}")
+    return _product("bmm", "mm_gemm_batched_enqueue", a, b, dtype, map_op, reduce_op, path, transposed_a, out=out, flag=False,
+                    batched_out=True)
 
 
 def addmm_(c, a, b, dtype="float", map_op="Multiply", reduce_op="Add", path=PATH_AUTO, transposed_a=False):
@@ -375,16 +382,8 @@ def addmm_(c, a, b, dtype="float", map_op="Multiply", reduce_op="Add", path=PATH
     at the value C holds instead of identity() -- torch.addmm_ for (Multiply, Add), D <- min(D, A + B) for (Add, Min).
     a: (N, K) -- or (K, N) with transposed_a -- b: (K, M), c: (N, M); contiguous device tensors of `dtype`, C not
     overlapping A or B.  Returns c.  Asynchronous, like any torch op."""
-    tdt = torch_dtype(dtype)
-    _device_operands("addmm_", tdt, c, a, b)
-    if a.dim() != 2 or b.dim() != 2 or c.dim() != 2:
-        raise MMError("addmm_ takes 2-D operands")
-    if not (a.is_contiguous() and b.is_contiguous() and c.is_contiguous()):
-        raise MMError("addmm_ needs contiguous (row-major) operands")
-    k, m = b.shape
-    n = a.shape[1] if transposed_a else a.shape[0]
-    if (a.shape[0] if transposed_a else a.shape[1]) != k:
-        raise MMError(f"inner dimensions differ: A {tuple(a.shape)}{' (K x N)' if transposed_a else ''}, B {tuple(b.shape)}")
+    _device_operands("addmm_", torch_dtype(dtype), c, a, b)
+    n, k, m = _matrix_shapes("addmm_", transposed_a, a, b, c)
     if tuple(c.shape) != (n, m):
         raise MMError(f"c has shape {tuple(c.shape)}, expected {(n, m)}")
     cfg = make_config(dtype, map_op, reduce_op, path, transposed_a)
@@ -397,16 +396,8 @@ def baddbmm_(c, a, b, dtype="float", map_op="Multiply", reduce_op="Add", path=PA
     (mm_gemm_batched_accumulate_enqueue) -- torch.baddbmm_ for (Multiply, Add).  a and b as for bmm (2-D, 3-D, or expanded
     with batch stride 0); c: (B, N, M) with dense row-major matrices and a batch stride of at least N * M (2-D when B is 1),
     not overlapping A or B.  Returns c.  Asynchronous, like any torch op."""
-    tdt = torch_dtype(dtype)
-    _device_operands("baddbmm_", tdt, c, a, b)
-    if c.dim() not in (2, 3):
-        raise MMError("baddbmm_ takes 2-D or 3-D operands")
-    n, k, m, batch, sa, sb = _bmm_shapes("baddbmm_", a, b, transposed_a)
-    batch, sc = _inplace_batch(c, n, m, batch)
-    cfg = make_config(dtype, map_op, reduce_op, path, transposed_a)
-    _enqueue(a.device, lib().mm_gemm_batched_accumulate_enqueue, ctypes.byref(cfg), a.data_ptr(), b.data_ptr(), c.data_ptr(),
-             n, k, m, batch, sa, sb, sc)
-    return c
+    return _product("baddbmm_", "mm_gemm_batched_accumulate_enqueue", a, b, dtype, map_op, reduce_op, path, transposed_a, c=c,
+                    flag=False)
 
 
 def matmul_argreduce(a, b, dtype="float", map_op="Add", reduce_op="Min", path=PATH_AUTO, transposed_a=False, index_base=0,
@@ -416,21 +407,8 @@ def matmul_argreduce(a, b, dtype="float", map_op="Add", reduce_op="Min", path=PA
     first k whose mapped value is the result, or -1 where no k improved on identity() -- torch.min(x, dim)'s pair.
     a and b as for bmm (2-D, 3-D, or expanded with batch stride 0); the outputs are (N, M) when both operands are 2-D,
     else (B, N, M).  out / out_index: contiguous tensors of that shape (values' dtype, torch.int32).  Asynchronous."""
-    import torch
-    tdt = torch_dtype(dtype)
-    _device_operands("matmul_argreduce", tdt, a, b)
-    n, k, m, batch, sa, sb = _bmm_shapes("matmul_argreduce", a, b, transposed_a)
-    shape = (n, m) if a.dim() == 2 and b.dim() == 2 else (batch, n, m)
-    if out is None:
-        out = torch.empty(shape, dtype=tdt, device=a.device)
-    if out_index is None:
-        out_index = torch.empty(shape, dtype=torch.int32, device=a.device)
-    _check_out(out, "out", shape, tdt, a.device)
-    _check_out(out_index, "out_index", shape, torch.int32, a.device)
-    cfg = make_config(dtype, map_op, reduce_op, path, transposed_a)
-    _enqueue(a.device, lib().mm_gemm_argreduce_enqueue, ctypes.byref(cfg), a.data_ptr(), b.data_ptr(), out.data_ptr(),
-             out_index.data_ptr(), n, k, m, batch, sa, sb, n * m, int(index_base), 0)
-    return out, out_index
+    return _product("matmul_argreduce", "mm_gemm_argreduce_enqueue", a, b, dtype, map_op, reduce_op, path, transposed_a,
+                    out=out, out_index=out_index, indexed=True, index_base=index_base)
 
 
 def addmm_argreduce_(c, c_index, a, b, dtype="float", map_op="Add", reduce_op="Min", path=PATH_AUTO, transposed_a=False,
@@ -440,22 +418,8 @@ def addmm_argreduce_(c, c_index, a, b, dtype="float", map_op="Add", reduce_op="M
     an output whose seed survives keeps its index exactly.  D <- min(D, A + B) of min-plus relaxation with the predecessor
     alongside.  2-D operands as for addmm_, 3-D (and broadcast) as for baddbmm_; c_index: torch.int32 with c's shape and
     strides.  Returns (c, c_index).  Asynchronous, like any torch op."""
-    import torch
-    tdt = torch_dtype(dtype)
-    _device_operands("addmm_argreduce_", tdt, c, a, b)
-    if not c_index.is_cuda or c_index.device != c.device or c_index.dtype != torch.int32:
-        raise MMError(f"c_index must be a torch.int32 tensor on {c.device}; got {c_index.dtype} on {c_index.device}")
-    if c.dim() not in (2, 3):
-        raise MMError("addmm_argreduce_ takes 2-D or 3-D operands")
-    if tuple(c_index.shape) != tuple(c.shape) or c_index.stride() != c.stride():
-        raise MMError(f"c_index must have c's shape and strides: {tuple(c.shape)} {c.stride()}, got "
-                      f"{tuple(c_index.shape)} {c_index.stride()}")
-    n, k, m, batch, sa, sb = _bmm_shapes("addmm_argreduce_", a, b, transposed_a)
-    batch, sc = _inplace_batch(c, n, m, batch)
-    cfg = make_config(dtype, map_op, reduce_op, path, transposed_a)
-    _enqueue(a.device, lib().mm_gemm_argreduce_enqueue, ctypes.byref(cfg), a.data_ptr(), b.data_ptr(), c.data_ptr(),
-             c_index.data_ptr(), n, k, m, batch, sa, sb, sc, int(index_base), 1)
-    return c, c_index
+    return _product("addmm_argreduce_", "mm_gemm_argreduce_enqueue", a, b, dtype, map_op, reduce_op, path, transposed_a,
+                    c=c, c_index=c_index, indexed=True, index_base=index_base)
 
 
 def matmul_logsumexp(a, b, dtype="float", reduce_op="Max", path=PATH_AUTO, transposed_a=False, out=None):
@@ -463,42 +427,14 @@ def matmul_logsumexp(a, b, dtype="float", reduce_op="Max", path=PATH_AUTO, trans
     reduce_op="Max" (the HMM forward step, the smooth max-plus product), -log sum_k exp(-(A[i,k] + B[k,j])) for "Min" (the
     soft-min).  dtype: "half", "float" or "double".  a and b as for bmm (2-D, 3-D, or expanded with batch stride 0); the
     output is (N, M) when both operands are 2-D, else (B, N, M); out: a contiguous tensor of that shape.  Asynchronous."""
-    import torch
-    tdt = torch_dtype(dtype)
-    _device_operands("matmul_logsumexp", tdt, a, b)
-    n, k, m, batch, sa, sb = _bmm_shapes("matmul_logsumexp", a, b, transposed_a)
-    shape = (n, m) if a.dim() == 2 and b.dim() == 2 else (batch, n, m)
-    if out is None:
-        out = torch.empty(shape, dtype=tdt, device=a.device)
-    else:
-        _check_out(out, "out", shape, tdt, a.device)
-    cfg = make_config(dtype, "Add", reduce_op, path, transposed_a)
-    _enqueue(a.device, lib().mm_gemm_logsumexp_enqueue, ctypes.byref(cfg), a.data_ptr(), b.data_ptr(), out.data_ptr(),
-             n, k, m, batch, sa, sb, n * m, 0)
-    return out
+    return _product("matmul_logsumexp", "mm_gemm_logsumexp_enqueue", a, b, dtype, "Add", reduce_op, path, transposed_a, out=out)
 
 
 def addmm_logsumexp_(c, a, b, dtype="float", reduce_op="Max", path=PATH_AUTO, transposed_a=False):
     """In place C <- log(exp(C) + sum_k exp(A[i,k] + B[k,j])) (Min: the soft-min) on torch's current stream
     (mm_gemm_logsumexp_enqueue, accumulate): C's value is one more term, so two calls on the halves of K compose to one
     call on all of it.  2-D operands as for addmm_, 3-D (and broadcast) as for baddbmm_.  Returns c.  Asynchronous."""
-    tdt = torch_dtype(dtype)
-    _device_operands("addmm_logsumexp_", tdt, c, a, b)
-    if c.dim() not in (2, 3):
-        raise MMError("addmm_logsumexp_ takes 2-D or 3-D operands")
-    n, k, m, batch, sa, sb = _bmm_shapes("addmm_logsumexp_", a, b, transposed_a)
-    batch, sc = _inplace_batch(c, n, m, batch)
-    cfg = make_config(dtype, "Add", reduce_op, path, transposed_a)
-    _enqueue(a.device, lib().mm_gemm_logsumexp_enqueue, ctypes.byref(cfg), a.data_ptr(), b.data_ptr(), c.data_ptr(),
-             n, k, m, batch, sa, sb, sc, 1)
-    return c
-
-
-def _widen_types(what, dtype):
-    wide = widen_dtype(dtype)
-    if wide is None:
-        raise MMError(f"{what} takes half or int8_t operands (got {dtype})")
-    return torch_dtype(dtype), torch_dtype(wide)
+    return _product("addmm_logsumexp_", "mm_gemm_logsumexp_enqueue", a, b, dtype, "Add", reduce_op, path, transposed_a, c=c)
 
 
 def matmul_wide(a, b, dtype="half", path=PATH_AUTO, transposed_a=False, out=None):
@@ -506,54 +442,15 @@ def matmul_wide(a, b, dtype="half", path=PATH_AUTO, transposed_a=False, out=None
     the matrix cores accumulate, not rounded to binary16 -- or int8_t operands to a torch.int32 C, the exact sums mod 2^32.
     a and b as for bmm (2-D, 3-D, or expanded with batch stride 0); the output is (N, M) when both operands are 2-D, else
     (B, N, M); out: a contiguous tensor of that shape and of the wide type.  Asynchronous."""
-    import torch
-    tdt, wdt = _widen_types("matmul_wide", dtype)
-    _device_operands("matmul_wide", tdt, a, b)
-    n, k, m, batch, sa, sb = _bmm_shapes("matmul_wide", a, b, transposed_a)
-    shape = (n, m) if a.dim() == 2 and b.dim() == 2 else (batch, n, m)
-    if out is None:
-        out = torch.empty(shape, dtype=wdt, device=a.device)
-    else:
-        _check_out(out, "out", shape, wdt, a.device)
-    cfg = make_config(dtype, "Multiply", "Add", path, transposed_a)
-    _enqueue(a.device, lib().mm_gemm_widen_enqueue, ctypes.byref(cfg), a.data_ptr(), b.data_ptr(), out.data_ptr(),
-             n, k, m, batch, sa, sb, n * m, 0)
-    return out
+    return _product("matmul_wide", "mm_gemm_widen_enqueue", a, b, dtype, "Multiply", "Add", path, transposed_a, out=out,
+                    wide=True)
 
 
 def addmm_wide_(c, a, b, dtype="half", path=PATH_AUTO, transposed_a=False):
     """In place C <- C + A B in the wide type on torch's current stream (mm_gemm_widen_enqueue, accumulate): c is
     torch.float32 for half operands, torch.int32 for int8_t; a K-split accumulated through it never rounds to the operand
     type.  2-D operands as for addmm_, 3-D (and broadcast) as for baddbmm_.  Returns c.  Asynchronous."""
-    tdt, wdt = _widen_types("addmm_wide_", dtype)
-    _device_operands("addmm_wide_", tdt, a, b)
-    _device_operands("addmm_wide_", wdt, c)
-    if c.device != a.device:
-        raise MMError(f"operands live on different devices: {c.device}, {a.device}")
-    if c.dim() not in (2, 3):
-        raise MMError("addmm_wide_ takes 2-D or 3-D operands")
-    n, k, m, batch, sa, sb = _bmm_shapes("addmm_wide_", a, b, transposed_a)
-    batch, sc = _inplace_batch(c, n, m, batch)
-    cfg = make_config(dtype, "Multiply", "Add", path, transposed_a)
-    _enqueue(a.device, lib().mm_gemm_widen_enqueue, ctypes.byref(cfg), a.data_ptr(), b.data_ptr(), c.data_ptr(),
-             n, k, m, batch, sa, sb, sc, 1)
-    return c
-
-
-def _nt_shapes(what, a, b):
-    """(n, k, m, batch, stride_a, stride_b) of A x B^T operands: a (N, K), b (M, K), each 2-D, 3-D, or expanded with batch
-    stride 0."""
-    if a.dim() not in (2, 3) or b.dim() not in (2, 3):
-        raise MMError(f"{what} takes 2-D or 3-D operands")
-    n, k, m = a.shape[-2], a.shape[-1], b.shape[-2]
-    if b.shape[-1] != k:
-        raise MMError(f"inner dimensions differ: A {tuple(a.shape)}, B {tuple(b.shape)} (M, K)")
-    ba, sa = _batched_operand(a, "a", n, k)
-    bb, sb = _batched_operand(b, "b (M, K)", m, k)
-    batches = {x for x in (ba, bb) if x is not None and x != 1}
-    if len(batches) > 1:
-        raise MMError(f"batch sizes differ: {ba} and {bb}")
-    return n, k, m, (batches.pop() if batches else 1), sa, sb
+    return _product("addmm_wide_", "mm_gemm_widen_enqueue", a, b, dtype, "Multiply", "Add", path, transposed_a, c=c, wide=True)
 
 
 def matmul_nt(a, b, dtype="float", map_op="Multiply", reduce_op="Add", path=PATH_AUTO, out=None):
@@ -562,35 +459,14 @@ def matmul_nt(a, b, dtype="float", map_op="Multiply", reduce_op="Add", path=PATH
     a: (N, K) or (B, N, K); b: (M, K) or (B, M, K); either may be expanded with batch stride 0, and a and b may be one
     buffer.  The output is (N, M) when both operands are 2-D, else (B, N, M); out: a contiguous tensor of that shape.
     Asynchronous, like any torch op."""
-    import torch
-    tdt = torch_dtype(dtype)
-    _device_operands("matmul_nt", tdt, a, b)
-    n, k, m, batch, sa, sb = _nt_shapes("matmul_nt", a, b)
-    shape = (n, m) if a.dim() == 2 and b.dim() == 2 else (batch, n, m)
-    if out is None:
-        out = torch.empty(shape, dtype=tdt, device=a.device)
-    else:
-        _check_out(out, "out", shape, tdt, a.device)
-    cfg = make_config(dtype, map_op, reduce_op, path)
-    _enqueue(a.device, lib().mm_gemm_nt_enqueue, ctypes.byref(cfg), a.data_ptr(), b.data_ptr(), out.data_ptr(),
-             n, k, m, batch, sa, sb, n * m, 0)
-    return out
+    return _product("matmul_nt", "mm_gemm_nt_enqueue", a, b, dtype, map_op, reduce_op, path, out=out, nt=True)
 
 
 def addmm_nt_(c, a, b, dtype="float", map_op="Multiply", reduce_op="Add", path=PATH_AUTO):
     """In place C <- C (+) (A (x) B^T) on torch's current stream (mm_gemm_nt_enqueue, accumulate): each output's reduction
     starts at the value C holds, so two calls on the halves of K compose to one call on all of it.  a and b as for matmul_nt;
     c: (N, M), or (B, N, M) as for baddbmm_, not overlapping a or b.  Returns c.  Asynchronous."""
-    tdt = torch_dtype(dtype)
-    _device_operands("addmm_nt_", tdt, c, a, b)
-    if c.dim() not in (2, 3):
-        raise MMError("addmm_nt_ takes 2-D or 3-D operands")
-    n, k, m, batch, sa, sb = _nt_shapes("addmm_nt_", a, b)
-    batch, sc = _inplace_batch(c, n, m, batch)
-    cfg = make_config(dtype, map_op, reduce_op, path)
-    _enqueue(a.device, lib().mm_gemm_nt_enqueue, ctypes.byref(cfg), a.data_ptr(), b.data_ptr(), c.data_ptr(),
-             n, k, m, batch, sa, sb, sc, 1)
-    return c
+    return _product("addmm_nt_", "mm_gemm_nt_enqueue", a, b, dtype, map_op, reduce_op, path, c=c, nt=True)
 
 
 def matmul_argreduce_nt(a, b, dtype="float", map_op="Add", reduce_op="Min", path=PATH_AUTO, index_base=0, out=None,
@@ -600,43 +476,16 @@ def matmul_argreduce_nt(a, b, dtype="float", map_op="Add", reduce_op="Min", path
     major transition matrix.  a and b as for matmul_nt: (N, K) or (B, N, K) and (M, K) or (B, M, K), either expanded with
     batch stride 0, possibly one buffer.  The outputs are (N, M) when both operands are 2-D, else (B, N, M).  out /
     out_index: contiguous tensors of that shape (values' dtype, torch.int32).  Asynchronous."""
-    import torch
-    tdt = torch_dtype(dtype)
-    _device_operands("matmul_argreduce_nt", tdt, a, b)
-    n, k, m, batch, sa, sb = _nt_shapes("matmul_argreduce_nt", a, b)
-    shape = (n, m) if a.dim() == 2 and b.dim() == 2 else (batch, n, m)
-    if out is None:
-        out = torch.empty(shape, dtype=tdt, device=a.device)
-    if out_index is None:
-        out_index = torch.empty(shape, dtype=torch.int32, device=a.device)
-    _check_out(out, "out", shape, tdt, a.device)
-    _check_out(out_index, "out_index", shape, torch.int32, a.device)
-    cfg = make_config(dtype, map_op, reduce_op, path)
-    _enqueue(a.device, lib().mm_gemm_argreduce_nt_enqueue, ctypes.byref(cfg), a.data_ptr(), b.data_ptr(), out.data_ptr(),
-             out_index.data_ptr(), n, k, m, batch, sa, sb, n * m, int(index_base), 0)
-    return out, out_index
+    return _product("matmul_argreduce_nt", "mm_gemm_argreduce_nt_enqueue", a, b, dtype, map_op, reduce_op, path,
+                    out=out, out_index=out_index, indexed=True, index_base=index_base, nt=True)
 
 
 def addmm_argreduce_nt_(c, c_index, a, b, dtype="float", map_op="Add", reduce_op="Min", path=PATH_AUTO, index_base=0):
     """In place (C, I) <- the A x B^T argreduce seeded with (C, I) on torch's current stream (mm_gemm_argreduce_nt_enqueue,
     accumulate): addmm_argreduce_ on b.mT.  a and b as for matmul_nt; c: (N, M), or (B, N, M) as for baddbmm_; c_index:
     torch.int32 with c's shape and strides.  Returns (c, c_index).  Asynchronous, like any torch op."""
-    import torch
-    tdt = torch_dtype(dtype)
-    _device_operands("addmm_argreduce_nt_", tdt, c, a, b)
-    if not c_index.is_cuda or c_index.device != c.device or c_index.dtype != torch.int32:
-        raise MMError(f"c_index must be a torch.int32 tensor on {c.device}; got {c_index.dtype} on {c_index.device}")
-    if c.dim() not in (2, 3):
-        raise MMError("addmm_argreduce_nt_ takes 2-D or 3-D operands")
-    if tuple(c_index.shape) != tuple(c.shape) or c_index.stride() != c.stride():
-        raise MMError(f"c_index must have c's shape and strides: {tuple(c.shape)} {c.stride()}, got "
-                      f"{tuple(c_index.shape)} {c_index.stride()}")
-    n, k, m, batch, sa, sb = _nt_shapes("addmm_argreduce_nt_", a, b)
-    batch, sc = _inplace_batch(c, n, m, batch)
-    cfg = make_config(dtype, map_op, reduce_op, path)
-    _enqueue(a.device, lib().mm_gemm_argreduce_nt_enqueue, ctypes.byref(cfg), a.data_ptr(), b.data_ptr(), c.data_ptr(),
-             c_index.data_ptr(), n, k, m, batch, sa, sb, sc, int(index_base), 1)
-    return c, c_index
+    return _product("addmm_argreduce_nt_", "mm_gemm_argreduce_nt_enqueue", a, b, dtype, map_op, reduce_op, path,
+                    c=c, c_index=c_index, indexed=True, index_base=index_base, nt=True)
 
 
 def matmul_logsumexp_nt(a, b, dtype="float", reduce_op="Max", path=PATH_AUTO, out=None):
@@ -644,35 +493,16 @@ def matmul_logsumexp_nt(a, b, dtype="float", reduce_op="Max", path=PATH_AUTO, ou
     b[j,k]) for reduce_op="Max" (Min: the soft-min) -- matmul_logsumexp on b.mT, the forward step over a to-state major
     transition matrix.  a and b as for matmul_nt; the output is (N, M) when both operands are 2-D, else (B, N, M); out: a
     contiguous tensor of that shape.  Asynchronous."""
-    import torch
-    tdt = torch_dtype(dtype)
-    _device_operands("matmul_logsumexp_nt", tdt, a, b)
-    n, k, m, batch, sa, sb = _nt_shapes("matmul_logsumexp_nt", a, b)
-    shape = (n, m) if a.dim() == 2 and b.dim() == 2 else (batch, n, m)
-    if out is None:
-        out = torch.empty(shape, dtype=tdt, device=a.device)
-    else:
-        _check_out(out, "out", shape, tdt, a.device)
-    cfg = make_config(dtype, "Add", reduce_op, path)
-    _enqueue(a.device, lib().mm_gemm_logsumexp_nt_enqueue, ctypes.byref(cfg), a.data_ptr(), b.data_ptr(), out.data_ptr(),
-             n, k, m, batch, sa, sb, n * m, 0)
-    return out
+    return _product("matmul_logsumexp_nt", "mm_gemm_logsumexp_nt_enqueue", a, b, dtype, "Add", reduce_op, path, out=out,
+                    nt=True)
 
 
 def addmm_logsumexp_nt_(c, a, b, dtype="float", reduce_op="Max", path=PATH_AUTO):
     """In place C <- log(exp(C) + sum_k exp(a[i,k] + b[j,k])) (Min: the soft-min) on torch's current stream
     (mm_gemm_logsumexp_nt_enqueue, accumulate): addmm_logsumexp_ on b.mT.  a and b as for matmul_nt; c: (N, M), or
     (B, N, M) as for baddbmm_.  Returns c.  Asynchronous."""
-    tdt = torch_dtype(dtype)
-    _device_operands("addmm_logsumexp_nt_", tdt, c, a, b)
-    if c.dim() not in (2, 3):
-        raise MMError("addmm_logsumexp_nt_ takes 2-D or 3-D operands")
-    n, k, m, batch, sa, sb = _nt_shapes("addmm_logsumexp_nt_", a, b)
-    batch, sc = _inplace_batch(c, n, m, batch)
-    cfg = make_config(dtype, "Add", reduce_op, path)
-    _enqueue(a.device, lib().mm_gemm_logsumexp_nt_enqueue, ctypes.byref(cfg), a.data_ptr(), b.data_ptr(), c.data_ptr(),
-             n, k, m, batch, sa, sb, sc, 1)
-    return c
+    return _product("addmm_logsumexp_nt_", "mm_gemm_logsumexp_nt_enqueue", a, b, dtype, "Add", reduce_op, path, c=c,
+                    nt=True)
 
 
 def closure_(d, d_witness=None, dtype="float", map_op="Add", reduce_op="Min", path=PATH_AUTO):

@@ -223,6 +223,30 @@ int check_problem(const mm_config_t *cfg, const void *a, const void *b, void *c,
   return MM_OK;
 }
 
+// ---- one row per matrix-core family: its batched kernels' resolver (once per call, on the whole batch; -1: none serves), launcher
+// (a chunk of the batch on the resolved kernel) and name.  mm_gemm_batched_*, the A x B^T pre-pass, the logsumexp hybrid's product
+// and mm_kernel_name_batched all go through it: a new family is a new row.  The fp32 row binds the f32_variant knob.
+struct MatrixCore {
+  int (*resolve)(const mm::Problem &whole);
+  int (*launch)(hipStream_t s, const mm::Problem &chunk, int kernel);
+  const char *(*name)(const mm::Problem &whole);
+};
+int f32_batched_resolve(const mm::Problem &p) { return mm::mfma_f32_batched_resolve(p, f32_variant()); }
+const char *f32_batched_name(const mm::Problem &p) {
+  const int v = f32_batched_resolve(p);
+  return v < 0 ? "unsupported" : mm::mfma_f32_name(v);
+}
+const MatrixCore kMatrixCore[] = {   // by Family, from FAM_MFMA_F32 on
+    {f32_batched_resolve, mm::launch_mfma_f32_batched, f32_batched_name},
+    {mm::mfma_f64_batched_resolve, mm::launch_mfma_f64_batched, mm::mfma_f64_batched_name},
+    {mm::mfma_f16_batched_resolve, mm::launch_mfma_f16_batched, mm::mfma_f16_batched_name},
+    {mm::mfma_i8_batched_resolve, mm::launch_mfma_i8_batched, mm::mfma_i8_batched_name},
+};
+static_assert(FAM_MFMA_F64 == FAM_MFMA_F32 + 1 && FAM_MFMA_F16 == FAM_MFMA_F32 + 2 && FAM_MFMA_I8 == FAM_MFMA_F32 + 3, "kMatrixCore's order");
+const MatrixCore *matrix_core(Family f) {   // null: not a matrix-core family
+  return f >= FAM_MFMA_F32 && f <= FAM_MFMA_I8 ? &kMatrixCore[f - FAM_MFMA_F32] : nullptr;
+}
+
 // ---- strided batches (mm_gemm_batched_*) -----------------------------------------------------------------------------
 // The family a batched launch runs: the single launch's, each matrix-core family through its batched resolver (decided on
 // the whole batch), except where that family would need workspace (split-K planes, stream-K scratch, a K x N transposition
@@ -230,16 +254,12 @@ int check_problem(const mm_config_t *cfg, const void *a, const void *b, void *c,
 // (K x N A: the direct K x N kernel), half (Multiply, Add) to half_wide (f32 accumulation, one rounding: mfma_f16's
 // contract), the 8-bit products to the register-tiled VALU kernel (exact).  Pure arithmetic: no device is touched.
 Family choose_batched(const mm_config_t &cfg, const mm::Problem &p) {
-  const auto valu_or_ordered = [&] { return mm::valu_tile_serves(cfg, p) ? FAM_VALU_TILE : FAM_ORDERED; };
-  switch (Family f = choose(cfg, p)) {
-    case FAM_MFMA_F32:   // (a library built without the batched fp32 kernels -- tools/lab -- resolves none)
-      return mm::mfma_f32_batched_resolve(p, f32_variant()) >= 0 ? f : valu_or_ordered();
-    case FAM_MFMA_F64: return mm::mfma_f64_batched_resolve(p) >= 0 ? f : valu_or_ordered();
-    case FAM_MFMA_I8: return mm::mfma_i8_batched_resolve(p) >= 0 ? f : valu_or_ordered();
-    case FAM_MFMA_F16: return mm::mfma_f16_batched_resolve(p) >= 0 ? f : FAM_HALF_WIDE;
-    case FAM_F32_SPLIT: return FAM_NONE;   // MM_PATH_SPLIT needs workspace: not batched
-    default: return f;
-  }
+  const Family f = choose(cfg, p);
+  if (f == FAM_F32_SPLIT) return FAM_NONE;   // MM_PATH_SPLIT needs workspace: not batched
+  const MatrixCore *mc = matrix_core(f);
+  if (!mc || mc->resolve(p) >= 0) return f;   // (a library built without the batched fp32 kernels -- tools/lab -- resolves none)
+  if (f == FAM_MFMA_F16) return FAM_HALF_WIDE;
+  return mm::valu_tile_serves(cfg, p) ? FAM_VALU_TILE : FAM_ORDERED;
 }
 
 // Every element meets the single launch's alignment rule: the fast families need each element's a, b and c 16-byte aligned.
@@ -280,6 +300,22 @@ bool outputs_overlap(const mm::Problem &p, size_t es, const int *index = nullptr
                     spans_overlap(index, i_bytes, p.c, c_bytes)));
 }
 
+// What the checks of the products that may be seeded (p.seed: mm_gemm_logsumexp_*, mm_gemm_widen_*, mm_gemm_nt_*) end in, after
+// the call's own rules -- the configurations it serves, its knob.  A refusal's status; else *go: whether there is anything to
+// launch -- not for an empty batch, nor when accumulating over K = 0, where C keeps its value.  es, c_es: A and B's and C's
+// element sizes.  (mm_gemm_argreduce_* has this order too, but index checks in between and A, B and the index required at K = 0.)
+int check_seeded(const mm::Problem &p, size_t es, size_t c_es, bool *go) {
+  *go = false;
+  if (p.k == 0 && !p.seed) return fail(MM_ERR_BAD_ARGUMENT, "size_k must be positive");
+  if (empty_batch(p)) return MM_OK;
+  if (!p.c || (p.k && (!p.a || !p.b))) return fail(MM_ERR_BAD_ARGUMENT, "null matrix pointer");   // (K = 0: A, B unread)
+  if (int rc = check_stride_c(p)) return rc;
+  if (outputs_overlap(p, es, nullptr, c_es))   // (B's extent is K * M in either layout)
+    return fail(MM_ERR_BAD_ARGUMENT, "c overlaps a or b (bases %p, %p, %p)", p.a, p.b, p.c);
+  *go = p.k > 0;
+  return MM_OK;
+}
+
 // Elements [e0, e0 + count) of the batch.
 mm::Problem batch_slice(const mm::Problem &p, unsigned e0, unsigned count, size_t es) {
   mm::Problem q = p;
@@ -296,6 +332,48 @@ template <class F> int for_each_chunk(const mm::Problem &p, size_t es, unsigned 
     if (int rc = fn(batch_slice(p, e0, std::min(chunk, p.batch - e0), es), e0)) return rc;
   return MM_OK;
 }
+
+// Stream-ordered workspace of one call, from the current device's library pool: allocated on the call's stream and freed on it
+// with hipFreeAsync, so the host never waits.  A dispatcher allocates, enqueues its work keeping its status, and returns
+// release(status); an exit without release() frees in the destructor.
+struct Workspace {
+  hipStream_t s;
+  const char *free_failed;   // the caller's words for a failed release: "hipFreeAsync (closure workspace)"
+  void *p = nullptr;
+  ~Workspace() { if (p) (void)hipFreeAsync(p, s); }
+  char *bytes() const { return (char *)p; }
+
+  // `size` bytes; *e: the allocation's own status.  Non-zero: the device's pool could not be had.
+  int from_pool(size_t size, hipError_t *e) {
+    *e = hipSuccess;
+    int dev = 0;
+    MM_HIP(hipGetDevice(&dev));
+    hipMemPool_t pool = nullptr;
+    if (int rc = mm::workspace_pool(dev, &pool)) return hip_fail((hipError_t)rc, "workspace pool");
+    if ((*e = hipMallocFromPoolAsync(&p, size, pool, s)) != hipSuccess) p = nullptr;
+    return MM_OK;
+  }
+  // A failed allocation fails the call, under the caller's words for it
+  int allocate(size_t size, const char *failed) {
+    hipError_t e;
+    const int rc = from_pool(size, &e);
+    return rc == MM_OK && e != hipSuccess ? hip_fail(e, failed) : rc;
+  }
+  // A failed allocation is reported in *full, the sticky error cleared: for a caller with a kernel that needs no workspace
+  int try_allocate(size_t size, bool *full) {
+    hipError_t e;
+    const int rc = from_pool(size, &e);
+    if ((*full = e != hipSuccess)) (void)hipGetLastError();
+    return rc;
+  }
+
+  // `rc`, the status of the work enqueued since allocate(), or -- when that is MM_OK -- a failed free's
+  int release(int rc) {
+    const hipError_t f = hipFreeAsync(p, s);
+    p = nullptr;
+    return rc == MM_OK && f != hipSuccess ? hip_fail(f, free_failed) : rc;
+  }
+};
 
 // All argument checks of a batched call, before any device is touched.  *fam: the family that will run (FAM_NONE: an empty
 // batch, a no-op).
@@ -319,32 +397,31 @@ int check_batched(const mm_config_t *cfg, const mm::Problem &p, Family *fam) {
   return MM_OK;
 }
 
-// Elements per launch: the batch_chunk knob, and a grid of at most 2^22 workgroups (of at most 512 threads) -- counted in
-// 64 x 64 tiles, the smallest any family uses.  An element bigger than that runs alone, as a single launch would.
-unsigned batch_chunk(const mm::Problem &p) {
-  const unsigned long long tiles = (unsigned long long)((p.n + 63) / 64) * ((p.m + 63) / 64);
+// Elements per launch of a batch whose elements take `tiles` workgroups each: the batch_chunk knob, and a grid of at most
+// 2^22 workgroups (of at most 512 threads).  An element bigger than that runs alone, as a single launch would.
+unsigned chunk_of_tiles(unsigned long long tiles, unsigned batch) {
   unsigned long long chunk = std::max(1ull, (1ull << 22) / tiles);
   const int knob = mm::tuning(mm::TUNE_BATCH_CHUNK);
   if (knob > 0) chunk = std::min<unsigned long long>(chunk, (unsigned)knob);
-  return (unsigned)std::min<unsigned long long>(chunk, p.batch);
+  return (unsigned)std::min<unsigned long long>(chunk, batch);
+}
+
+// ... of a product, counted in 64 x 64 tiles of C, the smallest any family uses
+unsigned batch_chunk(const mm::Problem &p) {
+  return chunk_of_tiles((unsigned long long)((p.n + 63) / 64) * ((p.m + 63) / 64), p.batch);
 }
 
 // Launches the batch as consecutive launches of at most batch_chunk() elements on `s`.  The family and the fp32 geometry
 // are decided once, on the whole batch, so that an element's kernel does not depend on how the batch was chunked.
 int dispatch_batched(hipStream_t s, const mm_config_t &cfg, const mm::Problem &p, Family fam) {
   if (empty_batch(p)) return MM_OK;
-  const int kernel = fam == FAM_MFMA_F32 ? mm::mfma_f32_batched_resolve(p, f32_variant())
-                   : fam == FAM_MFMA_F64 ? mm::mfma_f64_batched_resolve(p)
-                   : fam == FAM_MFMA_F16 ? mm::mfma_f16_batched_resolve(p)
-                   : fam == FAM_MFMA_I8 ? mm::mfma_i8_batched_resolve(p) : -1;
+  const MatrixCore *mc = matrix_core(fam);
+  const int kernel = mc ? mc->resolve(p) : -1;
   (void)hipGetLastError();   // a stale error of the application's own calls must not be reported as this launch's
   return for_each_chunk(p, mm_dtype_size(cfg.dtype), batch_chunk(p), [&](const mm::Problem &q, unsigned) {
+    if (mc) return launch_status(mc->launch(s, q, kernel), cfg, "", "batched kernel launch");
     int e;
     switch (fam) {
-      case FAM_MFMA_F32: e = mm::launch_mfma_f32_batched(s, q, kernel); break;
-      case FAM_MFMA_F64: e = mm::launch_mfma_f64_batched(s, q, kernel); break;
-      case FAM_MFMA_F16: e = mm::launch_mfma_f16_batched(s, q, kernel); break;
-      case FAM_MFMA_I8: e = mm::launch_mfma_i8_batched(s, q, kernel); break;
       case FAM_HALF_WIDE: e = mm::launch_half_wide_batched(s, q); break;
       case FAM_VALU_TILE:
         e = mm::launch_valu_tile_batched(s, cfg, q);
@@ -540,16 +617,12 @@ int dispatch_closure(hipStream_t s, const mm_config_t &cfg, void *d, int *w, uns
   }
   const size_t sn = ((size_t)n * B + 63) & ~(size_t)63;   // elements of one snapshot: 16-byte aligned for every element size
   const unsigned chunk = (unsigned)std::min<size_t>(batch, std::max<size_t>(1, kClosureWorkspaceCap / (2 * sn * es)));
-  int dev = 0;
-  MM_HIP(hipGetDevice(&dev));
-  hipMemPool_t pool = nullptr;
-  if (int e = mm::workspace_pool(dev, &pool)) return hip_fail((hipError_t)e, "workspace pool");
-  void *ws = nullptr;
-  MM_HIP(hipMallocFromPoolAsync(&ws, 2 * sn * chunk * es, pool, s));
-  st.cc = ws;
-  st.rc = (char *)ws + sn * chunk * es;
+  Workspace ws{s, "hipFreeAsync (closure workspace)"};
+  int rc = ws.allocate(2 * sn * chunk * es, "hipMallocFromPoolAsync(&ws, 2 * sn * chunk * es, pool, s)");
+  if (rc) return rc;
+  st.cc = ws.bytes();
+  st.rc = ws.bytes() + sn * chunk * es;
   st.stride_ws = sn;
-  int rc = MM_OK;
   for (unsigned e0 = 0; e0 < batch && rc == MM_OK; e0 += chunk) {
     st.graphs = std::min(chunk, batch - e0);
     st.d = (char *)d + (size_t)e0 * stride_d * es;
@@ -570,9 +643,7 @@ int dispatch_closure(hipStream_t s, const mm_config_t &cfg, void *d, int *w, uns
       rc = closure_rank_update(s, cfg, q, st.w, k0);
     }
   }
-  const hipError_t f = hipFreeAsync(ws, s);
-  if (rc == MM_OK && f != hipSuccess) rc = hip_fail(f, "hipFreeAsync (closure workspace)");
-  return rc;
+  return ws.release(rc);
 }
 
 // ---- bit-packed Boolean semiring (mm_bits_*) ----------------------------------------------------------------------------
@@ -626,14 +697,11 @@ int check_bits_gemm(const mm::BitsProblem &p, BitsKernel *ker) {
 
 // The batch in launches of at most 2^22 workgroups (64 x 64-word tiles, the smaller of the two) and batch_chunk elements.
 int dispatch_bits_gemm(hipStream_t s, const mm::BitsProblem &p, BitsKernel ker) {
-  const unsigned long long tiles = (unsigned long long)((p.n + 63) / 64) * ((bits_words(p.m) + 63) / 64);
-  unsigned long long chunk = std::max(1ull, (1ull << 22) / tiles);
-  const int knob = mm::tuning(mm::TUNE_BATCH_CHUNK);
-  if (knob > 0) chunk = std::min<unsigned long long>(chunk, (unsigned)knob);
+  const unsigned chunk = chunk_of_tiles((unsigned long long)((p.n + 63) / 64) * ((bits_words(p.m) + 63) / 64), p.batch);
   (void)hipGetLastError();   // a stale error of the application's own calls must not be reported as this launch's
-  for (unsigned e0 = 0; e0 < p.batch; e0 += (unsigned)std::min<unsigned long long>(chunk, p.batch)) {
+  for (unsigned e0 = 0; e0 < p.batch; e0 += chunk) {
     mm::BitsProblem q = p;
-    q.batch = (unsigned)std::min<unsigned long long>(chunk, p.batch - e0);
+    q.batch = std::min(chunk, p.batch - e0);
     q.a += (size_t)e0 * p.stride_a;
     q.b += (size_t)e0 * p.stride_b;
     q.c += (size_t)e0 * p.stride_c;
@@ -706,14 +774,10 @@ int dispatch_bits_closure(hipStream_t s, uint32_t *d, unsigned n, size_t ldd, un
   size_t chunk = std::min<size_t>(batch, std::max<size_t>(1, kClosureWorkspaceCap / (per_graph * 4)));
   const int knob = mm::tuning(mm::TUNE_BATCH_CHUNK);
   if (knob > 0) chunk = std::min<size_t>(chunk, (unsigned)knob);
-  int dev = 0;
-  MM_HIP(hipGetDevice(&dev));
-  hipMemPool_t pool = nullptr;
-  if (int e = mm::workspace_pool(dev, &pool)) return hip_fail((hipError_t)e, "workspace pool");
-  void *ws = nullptr;
-  MM_HIP(hipMallocFromPoolAsync(&ws, per_graph * chunk * 4, pool, s));
-  uint32_t *pstar = (uint32_t *)ws, *rp = pstar + p_words, *cp = rp + r_words;   // per graph: [P | I, R, Cc], per_graph words apart
-  int rc = MM_OK;
+  Workspace ws{s, "hipFreeAsync (packed closure workspace)"};
+  int rc = ws.allocate(per_graph * chunk * 4, "hipMallocFromPoolAsync(&ws, per_graph * chunk * 4, pool, s)");
+  if (rc) return rc;
+  uint32_t *pstar = (uint32_t *)ws.bytes(), *rp = pstar + p_words, *cp = rp + r_words;   // per graph: [P | I, R, Cc], per_graph words apart
   for (unsigned e0 = 0; e0 < batch && rc == MM_OK; e0 += (unsigned)chunk) {
     const unsigned graphs = (unsigned)std::min<size_t>(chunk, batch - e0);
     uint32_t *dg = d + (size_t)e0 * stride_d;
@@ -730,9 +794,7 @@ int dispatch_bits_closure(hipStream_t s, uint32_t *d, unsigned n, size_t ldd, un
       rc = bits_closure_product(s, all);
     }
   }
-  const hipError_t f = hipFreeAsync(ws, s);
-  if (rc == MM_OK && f != hipSuccess) rc = hip_fail(f, "hipFreeAsync (packed closure workspace)");
-  return rc;
+  return ws.release(rc);
 }
 
 // ---- log semiring (mm_gemm_logsumexp_*, mm_gemm_logsumexp_nt_*): log sum exp (A + B) --------------------------------------
@@ -763,14 +825,10 @@ int check_lse(const mm_config_t *cfg, const mm::Problem &p, LseKernel *ker) {
                 (int)cfg->map_op, (int)cfg->reduce_op, (int)cfg->path);
   if (bad_knob)
     return fail(MM_ERR_BAD_ARGUMENT, "lse_variant %d is not one of -1, 0, 1, 2", mm::tuning(mm::TUNE_LSE_VARIANT));
-  if (p.k == 0 && !p.seed) return fail(MM_ERR_BAD_ARGUMENT, "size_k must be positive");
-  if (empty_batch(p)) return MM_OK;
-  if (!p.c || (p.k && (!p.a || !p.b))) return fail(MM_ERR_BAD_ARGUMENT, "null matrix pointer");   // (K = 0: A, B unread)
-  if (int rc = check_stride_c(p)) return rc;
-  if (outputs_overlap(p, mm_dtype_size(cfg->dtype)))
-    return fail(MM_ERR_BAD_ARGUMENT, "c overlaps a or b (bases %p, %p, %p)", p.a, p.b, p.c);
-  if (p.k == 0) return MM_OK;   // accumulating over no k: C keeps its value
-  *ker = k;
+  bool go;
+  const size_t es = mm_dtype_size(cfg->dtype);
+  if (int rc = check_seeded(p, es, es, &go)) return rc;
+  if (go) *ker = k;
   return MM_OK;
 }
 
@@ -806,19 +864,16 @@ int dispatch_lse_hybrid(hipStream_t s, const mm_config_t &cfg, const mm::Problem
   chunk = std::min(chunk, batch_chunk(p));
   const size_t fl = up(tiles * chunk);                                          // int32 flags, one per tile
   const size_t bytes = (fixed + per * chunk) * fs + fl * sizeof(int);
-  int dev = 0;
-  MM_HIP(hipGetDevice(&dev));
-  hipMemPool_t pool = nullptr;
-  if (int e = mm::workspace_pool(dev, &pool)) return hip_fail((hipError_t)e, "workspace pool");
-  char *ws = nullptr;
-  MM_HIP(hipMallocFromPoolAsync((void **)&ws, bytes, pool, s));
-  int rc = MM_OK;
+  Workspace ws{s, "hipFreeAsync (logsumexp workspace)"};
+  int rc = ws.allocate(bytes, "hipMallocFromPoolAsync((void **)&ws, bytes, pool, s)");
+  if (rc) return rc;
   if (mm::tuning(mm::TUNE_DEBUG_POISON) == 1) {   // every F of the workspace NaN: a read of an unwritten element shows up
-    const hipError_t e = hipMemsetAsync(ws, 0xFF, bytes, s);
+    const hipError_t e = hipMemsetAsync(ws.bytes(), 0xFF, bytes, s);
     if (e != hipSuccess) rc = hip_fail(e, "hipMemsetAsync (logsumexp workspace)");
   }
+  const auto launched = [&](int e, const char *what) { return launch_status(e, cfg, "logsumexp ", what); };
   // layout: [EA][EB][S][ra][rb] in F, then the flags
-  char *const pea = ws, *const peb = pea + (a_shared ? ea : ea * chunk) * fs, *const ps = peb + (b_shared ? eb : eb * chunk) * fs;
+  char *const pea = ws.bytes(), *const peb = pea + (a_shared ? ea : ea * chunk) * fs, *const ps = peb + (b_shared ? eb : eb * chunk) * fs;
   char *const pra = ps + sz * chunk * fs, *const prb = pra + (a_shared ? ra : ra * chunk) * fs;
   int *const flags = (int *)(prb + (b_shared ? rb : rb * chunk) * fs);
   const size_t sea = a_shared ? 0 : ea, seb = b_shared ? 0 : eb, sra = a_shared ? 0 : ra, srb = b_shared ? 0 : rb;
@@ -829,48 +884,46 @@ int dispatch_lse_hybrid(hipStream_t s, const mm_config_t &cfg, const mm::Problem
   opb.e = peb; opb.r = prb; opb.stride_x = p.stride_b; opb.stride_e = eb; opb.stride_r = rb;
   if (rc == MM_OK && a_shared) {
     opa.x = p.a; opa.count = 1;
-    rc = launch_status(mm::launch_lse_prepass(s, cfg, opa), cfg, "logsumexp ", "logsumexp prepass launch");
+    rc = launched(mm::launch_lse_prepass(s, cfg, opa), "logsumexp prepass launch");
   }
   if (rc == MM_OK && b_shared) {
     opb.x = p.b; opb.count = 1;
-    rc = launch_status(mm::launch_lse_prepass(s, cfg, opb), cfg, "logsumexp ", "logsumexp prepass launch");
+    rc = launched(mm::launch_lse_prepass(s, cfg, opb), "logsumexp prepass launch");
   }
   // S = EA @ EB: (Multiply, Add) in F on the matrix cores; one element: the single launch's kernel, else the batched one
   // resolved on the whole batch
   const mm_config_t gcfg{dbl ? MM_DTYPE_F64 : MM_DTYPE_F32, MM_OP_MULTIPLY, MM_OP_ADD, MM_PATH_AUTO, MM_A_ROW_MAJOR};
   mm::Problem whole = batched_problem(&gcfg, pea, peb, ps, np, kp, mp, p.batch, sea, seb, sz);
-  const int gk = dbl ? mm::mfma_f64_batched_resolve(whole) : mm::mfma_f32_batched_resolve(whole, f32_variant());
+  const MatrixCore &mc = *matrix_core(dbl ? FAM_MFMA_F64 : FAM_MFMA_F32);
+  const int gk = mc.resolve(whole);
   if (rc == MM_OK && p.batch > 1 && gk < 0) rc = fail(MM_ERR_UNSUPPORTED, "no batched matrix-core kernel for the logsumexp product");
   for (unsigned e0 = 0; e0 < p.batch && rc == MM_OK; e0 += chunk) {
     const unsigned ce = std::min(chunk, p.batch - e0);
     const mm::Problem q = batch_slice(p, e0, ce, es);   // this chunk's elements
     if (!a_shared) {
       opa.x = q.a; opa.count = ce;
-      if ((rc = launch_status(mm::launch_lse_prepass(s, cfg, opa), cfg, "logsumexp ", "logsumexp prepass launch"))) break;
+      if ((rc = launched(mm::launch_lse_prepass(s, cfg, opa), "logsumexp prepass launch"))) break;
     }
     if (!b_shared) {
       opb.x = q.b; opb.count = ce;
-      if ((rc = launch_status(mm::launch_lse_prepass(s, cfg, opb), cfg, "logsumexp ", "logsumexp prepass launch"))) break;
+      if ((rc = launched(mm::launch_lse_prepass(s, cfg, opb), "logsumexp prepass launch"))) break;
     }
     mm::Problem g = batched_problem(&gcfg, pea, peb, ps, np, kp, mp, ce, sea, seb, sz);
     if (p.batch == 1) {
       if ((rc = dispatch(s, gcfg, g))) break;
-    } else {
-      const int e = dbl ? mm::launch_mfma_f64_batched(s, g, gk) : mm::launch_mfma_f32_batched(s, g, gk);
-      if ((rc = launch_status(e, gcfg, "logsumexp ", "logsumexp product launch"))) break;
+    } else if ((rc = launch_status(mc.launch(s, g, gk), gcfg, "logsumexp ", "logsumexp product launch"))) {   // (the product's own)
+      break;
     }
     mm::LseEpilogue ep{};
     ep.s = ps; ep.ra = pra; ep.rb = prb; ep.c = q.c; ep.flags = flags;
     ep.n = p.n; ep.m = p.m; ep.m_p = mp; ep.batch = ce;
     ep.stride_s = sz; ep.stride_ra = sra; ep.stride_rb = srb; ep.stride_c = p.stride_c;
     ep.seed = p.seed; ep.force = mm::tuning(mm::TUNE_LSE_VARIANT) == 2;
-    if ((rc = launch_status(mm::launch_lse_epilogue(s, cfg, ep), cfg, "logsumexp ", "logsumexp epilogue launch"))) break;
+    if ((rc = launched(mm::launch_lse_epilogue(s, cfg, ep), "logsumexp epilogue launch"))) break;
     // the fallback: the exact kernel over the flagged tiles of this chunk
-    if ((rc = launch_status(mm::launch_lse_exact(s, cfg, q, flags), cfg, "logsumexp ", "logsumexp fallback launch"))) break;
+    if ((rc = launched(mm::launch_lse_exact(s, cfg, q, flags), "logsumexp fallback launch"))) break;
   }
-  const hipError_t f = hipFreeAsync(ws, s);
-  if (rc == MM_OK && f != hipSuccess) rc = hip_fail(f, "hipFreeAsync (logsumexp workspace)");
-  return rc;
+  return ws.release(rc);
 }
 
 int dispatch_lse(hipStream_t s, const mm_config_t &cfg, const mm::Problem &p, LseKernel ker) {
@@ -904,14 +957,10 @@ int check_widen(const mm_config_t *cfg, const mm::Problem &p, WidenKernel *ker) 
     return fail(MM_ERR_UNSUPPORTED, "widening serves half and int8_t with (Multiply, Add), under MM_PATH_AUTO or MM_PATH_ORDERED "
                 "(got dtype %d, map %d, reduce %d, path %d)", (int)cfg->dtype, (int)cfg->map_op, (int)cfg->reduce_op,
                 (int)cfg->path);
-  if (p.k == 0 && !p.seed) return fail(MM_ERR_BAD_ARGUMENT, "size_k must be positive");
-  if (empty_batch(p)) return MM_OK;
-  if (!p.c || (p.k && (!p.a || !p.b))) return fail(MM_ERR_BAD_ARGUMENT, "null matrix pointer");   // (K = 0: A, B unread)
-  if (int rc = check_stride_c(p)) return rc;
   const size_t es = mm_dtype_size(cfg->dtype), ws = mm_dtype_size((mm_dtype_t)mm_widen_dtype(cfg->dtype));
-  if (outputs_overlap(p, es, nullptr, ws))
-    return fail(MM_ERR_BAD_ARGUMENT, "c overlaps a or b (bases %p, %p, %p)", p.a, p.b, p.c);
-  if (p.k == 0) return MM_OK;   // accumulating over no k: C keeps its value
+  bool go;
+  if (int rc = check_seeded(p, es, ws, &go)) return rc;
+  if (!go) return MM_OK;
   *ker = widen_mfma_name(*cfg, p) ? WD_MFMA : WD_ORDERED;
   // the matrix-core kernels move 16 bytes per lane of A and B, and C is written in 64-byte runs: every element's a, b and c
   // 16-byte aligned, else widen_ordered summing in blocks: MM_PATH_AUTO's contract, bound included
@@ -984,14 +1033,10 @@ int check_nt(const mm_config_t *cfg, const mm::Problem &p, NtKernel *ker) {
   if (!nt_serves(*cfg))
     return fail(MM_ERR_UNSUPPORTED, "the A x B^T calls serve a row-major A under MM_PATH_AUTO or MM_PATH_ORDERED (got path %d, "
                 "layout_a %d)", (int)cfg->path, (int)cfg->layout_a);
-  if (p.k == 0 && !p.seed) return fail(MM_ERR_BAD_ARGUMENT, "size_k must be positive");
-  if (empty_batch(p)) return MM_OK;
-  if (!p.c || (p.k && (!p.a || !p.b))) return fail(MM_ERR_BAD_ARGUMENT, "null matrix pointer");   // (K = 0: A, B unread)
-  if (int rc = check_stride_c(p)) return rc;
   const size_t es = mm_dtype_size(cfg->dtype);
-  if (outputs_overlap(p, es))   // (B's extent is M * K in either layout)
-    return fail(MM_ERR_BAD_ARGUMENT, "c overlaps a or b (bases %p, %p, %p)", p.a, p.b, p.c);
-  if (p.k == 0) return MM_OK;   // accumulating over no k: C keeps its value
+  bool go;
+  if (int rc = check_seeded(p, es, es, &go)) return rc;
+  if (!go) return MM_OK;
   *ker = nt_kernel_for(*cfg, p);
   // valu_tile_nt moves 16 bytes per lane of A and Bt (C goes element by element); the pre-pass and the matrix-core kernels
   // 16 bytes of C as well: else ordered_nt, any element-aligned pointer
@@ -1031,42 +1076,29 @@ int dispatch_nt_prepass(hipStream_t s, const mm_config_t &cfg, const mm::Problem
   mm::Problem whole = p;   // the row-major problem the kernels see
   whole.b_transposed = false;
   whole.stride_b = b_shared ? 0 : km;
-  const Family fam = choose_batched(cfg, whole);
-  const int kernel = fam == FAM_MFMA_F32 ? mm::mfma_f32_batched_resolve(whole, f32_variant())
-                   : fam == FAM_MFMA_F64 ? mm::mfma_f64_batched_resolve(whole)
-                   : fam == FAM_MFMA_F16 ? mm::mfma_f16_batched_resolve(whole)
-                   : fam == FAM_MFMA_I8 ? mm::mfma_i8_batched_resolve(whole) : -1;
+  const MatrixCore *mc = matrix_core(choose_batched(cfg, whole));
+  const int kernel = mc ? mc->resolve(whole) : -1;
   if (kernel < 0) return nt_chunks(s, cfg, p, nt_demoted(cfg));   // (a knob changed between the check and here)
-  int dev = 0;
-  MM_HIP(hipGetDevice(&dev));
-  hipMemPool_t pool = nullptr;
-  if (int e = mm::workspace_pool(dev, &pool)) return hip_fail((hipError_t)e, "workspace pool");
-  void *ws = nullptr;
-  if (hipMallocFromPoolAsync(&ws, (b_shared ? 1 : chunk) * km * es, pool, s) != hipSuccess) {
-    (void)hipGetLastError();
-    return nt_chunks(s, cfg, p, nt_demoted(cfg));
-  }
-  int rc = MM_OK;
+  Workspace ws{s, "hipFreeAsync (A x B^T workspace)"};
+  bool full;
+  int rc = ws.try_allocate((b_shared ? 1 : chunk) * km * es, &full);
+  if (rc) return rc;
+  if (full) return nt_chunks(s, cfg, p, nt_demoted(cfg));
   for (unsigned e0 = 0; e0 < p.batch && rc == MM_OK; e0 += chunk) {
     const mm::Problem src = batch_slice(p, e0, std::min(chunk, p.batch - e0), es);   // this chunk's elements
     if (e0 == 0 || !b_shared)
-      rc = launch_status(mm::launch_transpose_batched(s, src.b, ws, p.m, p.k, (unsigned)es, b_shared ? 1 : src.batch, p.stride_b, km),
+      rc = launch_status(mm::launch_transpose_batched(s, src.b, ws.bytes(), p.m, p.k, (unsigned)es, b_shared ? 1 : src.batch, p.stride_b, km),
                          cfg, "A x B^T ", "transposition pre-pass launch");
     if (rc) break;
     mm::Problem g = src;
-    g.b = ws;
+    g.b = ws.bytes();
     g.b_transposed = false;
     g.stride_b = whole.stride_b;
     rc = for_each_chunk(g, es, batch_chunk(g), [&](const mm::Problem &q, unsigned) {
-      const int e = fam == FAM_MFMA_F32 ? mm::launch_mfma_f32_batched(s, q, kernel)
-                  : fam == FAM_MFMA_F64 ? mm::launch_mfma_f64_batched(s, q, kernel)
-                  : fam == FAM_MFMA_F16 ? mm::launch_mfma_f16_batched(s, q, kernel) : mm::launch_mfma_i8_batched(s, q, kernel);
-      return launch_status(e, cfg, "A x B^T ", "A x B^T product launch");
+      return launch_status(mc->launch(s, q, kernel), cfg, "A x B^T ", "A x B^T product launch");
     });
   }
-  const hipError_t f = hipFreeAsync(ws, s);
-  if (rc == MM_OK && f != hipSuccess) rc = hip_fail(f, "hipFreeAsync (A x B^T workspace)");
-  return rc;
+  return ws.release(rc);
 }
 
 int dispatch_nt(hipStream_t s, const mm_config_t &cfg, const mm::Problem &p, NtKernel ker) {
@@ -1878,16 +1910,9 @@ const char *mm_kernel_name(const mm_config_t *cfg, unsigned n, unsigned k, unsig
 const char *mm_kernel_name_batched(const mm_config_t *cfg, unsigned n, unsigned k, unsigned m, unsigned batch) {
   if (!valid_cfg(cfg)) return "invalid";
   const mm::Problem p = batched_problem(cfg, nullptr, nullptr, nullptr, n, k, m, batch ? batch : 1, 0, 0, 0);
-  switch (const Family fam = choose_batched(*cfg, p)) {   // the resolver dispatch_batched uses
-    case FAM_MFMA_F32: {
-      const int v = mm::mfma_f32_batched_resolve(p, f32_variant());
-      return v < 0 ? "unsupported" : mm::mfma_f32_name(v);
-    }
-    case FAM_MFMA_F64: return mm::mfma_f64_batched_name(p);
-    case FAM_MFMA_F16: return mm::mfma_f16_batched_name(p);
-    case FAM_MFMA_I8: return mm::mfma_i8_batched_name(p);
-    default: return family_name(fam);
-  }
+  const Family fam = choose_batched(*cfg, p);
+  const MatrixCore *mc = matrix_core(fam);   // the row dispatch_batched uses
+  return mc ? mc->name(p) : family_name(fam);
 }
 
 static const char *argreduce_name(const mm_config_t *cfg, unsigned n, unsigned k, unsigned m, unsigned batch, bool bt) {
