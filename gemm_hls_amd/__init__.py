@@ -35,6 +35,10 @@ EXPORTS = ["mm_init", "mm_alloc", "mm_free", "mm_copy_to_device", "mm_copy_to_ho
            "mm_gemm_logsumexp_nt_launch", "mm_kernel_name_logsumexp_nt", "mm_bits_gemm_enqueue", "mm_bits_gemm_launch",
            "mm_kernel_name_bits_gemm", "mm_bits_closure_enqueue", "mm_bits_closure_launch", "mm_kernel_name_bits_closure",
            "mm_bits_pack_enqueue", "mm_bits_pack_launch", "mm_bits_unpack_enqueue", "mm_bits_unpack_launch"]
+# what include/mm_bits_count.h declares (included by mm_gemm.h; asserted by tests/test_bits_count_capi.py).  A list of its own:
+# EXPORTS is pinned, symbol for symbol, against mm_gemm.h's own declarations and a literal prototype table
+BITS_COUNT_EXPORTS = ["mm_bits_count_enqueue", "mm_bits_count_launch", "mm_kernel_name_bits_count", "mm_bits_transpose_enqueue",
+                      "mm_bits_transpose_launch"]
 
 
 class MMError(RuntimeError):
@@ -93,13 +97,15 @@ def lib():
                  "mm_gemm_argreduce": argreduce, "mm_gemm_argreduce_nt": argreduce, "mm_gemm_logsumexp": seeded,
                  "mm_gemm_logsumexp_nt": seeded, "mm_gemm_widen": seeded, "mm_gemm_nt": seeded,
                  "mm_closure": [cfgp, vp, vp, u, u, sz], "mm_bits_gemm": [vp, vp, vp, u, u, u, sz, sz, sz, u, sz, sz, sz, i],
-                 "mm_bits_closure": [vp, u, sz, u, sz], "mm_bits_pack": convert, "mm_bits_unpack": convert}
+                 "mm_bits_closure": [vp, u, sz, u, sz], "mm_bits_pack": convert, "mm_bits_unpack": convert,
+                 "mm_bits_count": [i, vp, vp, vp, u, u, u, sz, sz, sz, u, sz, sz, sz, i], "mm_bits_transpose": convert}
         for stem, between in pairs.items():
             getattr(L, stem + "_enqueue").argtypes = [vp] + between
             getattr(L, stem + "_launch").argtypes = [i] + between + [dp]
         # mm_kernel_name<suffix>(...): a string
         shape = [cfgp, u, u, u]
-        names = {"": shape, "_closure": [cfgp, u, u, i], "_bits_gemm": [u, u, u, sz, sz, sz, u], "_bits_closure": [u, u]}
+        names = {"": shape, "_closure": [cfgp, u, u, i], "_bits_gemm": [u, u, u, sz, sz, sz, u], "_bits_closure": [u, u],
+                 "_bits_count": [u, u, u, sz, sz, sz, u]}
         names.update((suffix, shape + [u]) for suffix in ("_batched", "_argreduce", "_logsumexp", "_widen", "_nt", "_argreduce_nt",
                                                           "_logsumexp_nt"))
         for suffix, args in names.items():
@@ -698,6 +704,124 @@ def bits_closure_(d, n=None):
         raise MMError(f"d has batch stride 0: the {batch} graphs would overlap")
     _enqueue(d.device, lib().mm_bits_closure_enqueue, d.data_ptr(), n, ldd, batch or 1, stride)
     return d
+
+
+# ---- counting products on the packed format (mm_bits_count_*, A x B^T) and the packed transpose ---------------------------------
+BITS_COUNT_OPS = {"And": 0, "Xor": 1}
+
+
+def kernel_name_bits_count(n, k, m, lda=None, ldbt=None, ldc=None, batch=1):
+    """Name of the kernel bits_matmul_count / bits_addmm_count_ run; lda and ldbt (words) default to ceil(k / 32), ldc
+    (elements) to m."""
+    lda, ldbt = (bits_words(k) if ld is None else ld for ld in (lda, ldbt))
+    return lib().mm_kernel_name_bits_count(n, k, m, lda, ldbt, m if ldc is None else ldc, batch).decode()
+
+
+def _bits_count_shapes(what, a, bt, k, op):
+    if op not in BITS_COUNT_OPS:
+        raise MMError(f"{what}: op must be one of {sorted(BITS_COUNT_OPS)} (got {op!r})")
+    if not (a.is_cuda and bt.is_cuda):
+        raise MMError(f"{what} needs device tensors: there is no CPU path")
+    if a.device != bt.device:
+        raise MMError(f"operands live on different devices: {a.device} and {bt.device}")
+    if a.dim() not in (2, 3) or bt.dim() not in (2, 3):
+        raise MMError(f"{what} takes 2-D or 3-D operands")
+    n, m = a.shape[-2], bt.shape[-2]
+    ba, sa, lda = _packed_operand(a, "a", n, k)
+    bb, sb, ldbt = _packed_operand(bt, "bt", m, k)
+    batches = {x for x in (ba, bb) if x is not None and x != 1}
+    if len(batches) > 1:
+        raise MMError(f"batch sizes differ: {ba} and {bb}")
+    return n, m, (batches.pop() if batches else 1), sa, sb, lda, ldbt
+
+
+def _count_output(c, name, n, m, batch, two_d, device):
+    """(batch stride, row stride), in elements, of the int32 result `c`: (n, m), or (batch, n, m) unless two_d, with unit
+    stride along a row and its own row and batch strides."""
+    import torch
+    if c.dtype != torch.int32:
+        raise MMError(f"{name} must be a torch.int32 tensor (got {c.dtype})")
+    if not c.is_cuda or c.device != device:
+        raise MMError(f"{name} must live on {device} (got {c.device})")
+    want = (n, m) if two_d else (batch, n, m)
+    if tuple(c.shape) != want:
+        raise MMError(f"{name} has shape {tuple(c.shape)}, expected {want}")
+    if m > 1 and c.stride(-1) != 1:
+        raise MMError(f"the elements of a row of {name} must be contiguous (strides {c.stride()})")
+    ldc = c.stride(-2) if n > 1 else max(c.stride(-2), m)
+    if ldc < m:
+        raise MMError(f"{name} has row stride {ldc}, below its {m} elements")
+    sc = 0 if c.dim() == 2 or batch == 1 else c.stride(0)
+    if batch > 1 and sc <= 0:
+        raise MMError(f"{name} has batch stride {sc}: the {batch} outputs would overlap")
+    return sc, ldc
+
+
+def bits_matmul_count(a, bt, k, op="And", out=None):
+    """Packed counting product on torch's current stream (mm_bits_count_enqueue): C[i][j] = sum_k (A[i][k] op Bt[j][k]), op
+    "And" (common neighbours, intersections) or "Xor" (Hamming distances).  a: (N, W) and bt: (M, W), both packed along K,
+    torch.int32, W >= ceil(k / 32); either may be 3-D, or expanded with batch stride 0.  Row strides are taken from the
+    tensors, so a column slice of whole words is an operand without a copy; padding bits are ignored.  Returns torch.int32
+    (N, M) when both operands are 2-D, else (B, N, M); out: an int32 tensor of that shape with its own row stride.
+    Asynchronous."""
+    import torch
+    n, m, batch, sa, sb, lda, ldbt = _bits_count_shapes("bits_matmul_count", a, bt, k, op)
+    two_d = a.dim() == 2 and bt.dim() == 2
+    if out is None:
+        out = torch.empty((n, m) if two_d else (batch, n, m), dtype=torch.int32, device=a.device)
+        sc, ldc = (n * m if batch > 1 else 0), m
+    else:
+        sc, ldc = _count_output(out, "out", n, m, batch, two_d, a.device)
+    _enqueue(a.device, lib().mm_bits_count_enqueue, BITS_COUNT_OPS[op], a.data_ptr(), bt.data_ptr(), out.data_ptr(), n, k, m,
+             lda, ldbt, ldc, batch, sa, sb, sc, 0)
+    return out
+
+
+def bits_addmm_count_(c, a, bt, k, op="And"):
+    """In place C += counts on torch's current stream (mm_bits_count_enqueue, accumulate), mod 2^32; a, bt and op as for
+    bits_matmul_count, c: torch.int32 (N, M) or (B, N, M) with its own row stride, not overlapping a or bt.  Two calls on
+    the halves of K equal one call on all of it.  Returns c.  Asynchronous."""
+    n, m, batch, sa, sb, lda, ldbt = _bits_count_shapes("bits_addmm_count_", a, bt, k, op)
+    two_d = c.dim() == 2
+    if two_d and batch != 1:
+        raise MMError(f"c has shape {tuple(c.shape)}, expected ({batch}, {n}, {m})")
+    if not two_d and c.dim() == 3 and batch == 1:
+        batch = c.shape[0]
+    sc, ldc = _count_output(c, "c", n, m, batch, two_d, a.device)
+    _enqueue(a.device, lib().mm_bits_count_enqueue, BITS_COUNT_OPS[op], a.data_ptr(), bt.data_ptr(), c.data_ptr(), n, k, m,
+             lda, ldbt, ldc, batch, sa, sb, sc, 1)
+    return c
+
+
+def transpose_bits(p, cols, out=None):
+    """Packed transpose on torch's current stream (mm_bits_transpose_enqueue): packed torch.int32 (..., rows, W), W >=
+    ceil(cols / 32), to packed (..., cols, ceil(rows / 32)) with out[..., j, i] = p[..., i, j] -- a K x M operand of
+    bits_matmul as the M x K operand of bits_matmul_count.  Padding bits of p are ignored, those of the result are 0.  out: a
+    packed tensor of the result's shape (more words per row allowed; they are left alone)."""
+    import torch
+    if not p.is_cuda:
+        raise MMError("transpose_bits needs a device tensor: there is no CPU path")
+    if p.dim() < 2:
+        raise MMError(f"transpose_bits takes a (..., rows, W) tensor; got shape {tuple(p.shape)}")
+    lead = tuple(p.shape[:-2])
+    if p.dim() > 3:
+        p = p.contiguous().reshape(-1, *p.shape[-2:])
+    rows = p.shape[-2]
+    batch, stride, ld = _packed_operand(p, "p", rows, cols)
+    if out is None:
+        out = torch.empty(lead + (cols, bits_words(rows)), dtype=torch.int32, device=p.device)
+    elif out.device != p.device or tuple(out.shape[:-2]) != lead:
+        raise MMError(f"out has shape {tuple(out.shape)} on {out.device}; expected {lead + (cols, 'W')} on {p.device}")
+    o = out
+    if out.dim() > 3:
+        if not out.is_contiguous():
+            raise MMError("out with more than one batch dimension must be contiguous")
+        o = out.reshape(-1, *out.shape[-2:])
+    bo, so, ldo = _packed_operand(o, "out", cols, rows)
+    if (batch or 1) > 1 and so == 0:
+        raise MMError(f"out has batch stride 0: the {batch} outputs would overlap")
+    _enqueue(p.device, lib().mm_bits_transpose_enqueue, p.data_ptr(), o.data_ptr(), rows, cols, ld, ldo, batch or 1, stride, so)
+    return out
 
 
 def row_slab(cfg, n, k, m, world_size, rank):

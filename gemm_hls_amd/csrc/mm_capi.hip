@@ -92,11 +92,11 @@ std::atomic<int> g_tuning[mm::TUNE_COUNT];
 const char *const kTuneName[mm::TUNE_COUNT] = {"f32_variant", "f64_variant", "f16_variant", "i8_variant", "band_rows",
                                                "valu_variant", "split_variant", "f32_splitk", "ablations", "debug_poison", "kxn_prepass_min_m",
                                                "md_virtual_devices", "ordered_variant", "half_contract", "batch_chunk",
-                                               "closure_block", "lse_variant", "bits_variant"};
+                                               "closure_block", "lse_variant", "bits_variant", "bits_count_variant"};
 const char *const kTuneEnv[mm::TUNE_COUNT] = {"MM_F32_VARIANT", "MM_F64_VARIANT", "MM_F16_VARIANT", "MM_I8_VARIANT",
                                               "MM_BAND_ROWS", "MM_VALU_VARIANT", "MM_SPLIT_VARIANT", "MM_F32_SPLITK", "MM_ABLATIONS", "MM_DEBUG_POISON", "MM_KXN_PREPASS_MIN_M",
                                               "MM_MD_VIRTUAL_DEVICES", "MM_ORDERED_VARIANT", "MM_HALF_CONTRACT", "MM_BATCH_CHUNK",
-                                              "MM_CLOSURE_BLOCK", "MM_LSE_VARIANT", "MM_BITS_VARIANT"};
+                                              "MM_CLOSURE_BLOCK", "MM_LSE_VARIANT", "MM_BITS_VARIANT", "MM_BITS_COUNT_VARIANT"};
 void tuning_init() {
   for (int i = 0; i < mm::TUNE_COUNT; ++i) {
     const char *e = getenv(kTuneEnv[i]);
@@ -734,6 +734,91 @@ int dispatch_bits_convert(hipStream_t s, const mm::BitsConvert &c, bool to_bits)
   return e ? hip_fail((hipError_t)e, to_bits ? "pack kernel launch" : "unpack kernel launch") : MM_OK;
 }
 
+// ---- bit-packed counting product (mm_bits_count_*) and packed transpose (mm_bits_transpose_*) -----------------------------------
+constexpr unsigned long long kBitsCountTileMin = 256;   // 128 x 128 tiles of C from which bits_count_tile serves: one per CU
+
+// The kernel by shape, ld and knob alone (mm_kernel_name_bits_count); alignment may still demote BITS_TILE at launch.
+BitsKernel bits_count_kernel_for(unsigned n, unsigned m, size_t lda, size_t ldbt, size_t ldc) {
+  const int v = mm::tuning(mm::TUNE_BITS_COUNT_VARIANT);
+  if (v < -1 || v > 1) return BITS_INVALID;
+  if (v == 0 || !mm::bits_count_tile_serves(lda, ldbt, ldc)) return BITS_PLAIN;
+  const unsigned long long tiles = (unsigned long long)(((size_t)n + 127) / 128) * (((size_t)m + 127) / 128);
+  return v == 1 || tiles >= kBitsCountTileMin ? BITS_TILE : BITS_PLAIN;
+}
+
+// The launch-time half of the rule: a, bt and c in 16-byte accesses, for every element of the batch.
+BitsKernel bits_count_demote(const mm::BitsProblem &p, BitsKernel ker) {
+  if (ker != BITS_TILE) return ker;
+  const bool aligned = (((uintptr_t)p.a | (uintptr_t)p.b | (uintptr_t)p.c) & 15u) == 0 &&
+                       (p.batch <= 1 || (p.stride_a % 4 == 0 && p.stride_b % 4 == 0 && p.stride_c % 4 == 0));
+  return aligned ? BITS_TILE : BITS_PLAIN;
+}
+
+// All argument checks of a counting product (p.b: Bt, M x K), before any device is touched.  *ker = BITS_NONE: nothing to launch.
+int check_bits_count(int op, const mm::BitsProblem &p, BitsKernel *ker) {
+  *ker = BITS_NONE;
+  if (op != MM_BITS_COUNT_AND && op != MM_BITS_COUNT_XOR)
+    return fail(MM_ERR_BAD_ARGUMENT, "op %d is not MM_BITS_COUNT_AND (0) or MM_BITS_COUNT_XOR (1)", op);
+  const BitsKernel k = bits_count_kernel_for(p.n, p.m, p.lda, p.ldb, p.ldc);
+  if (k == BITS_INVALID)
+    return fail(MM_ERR_BAD_ARGUMENT, "bits_count_variant %d is not one of -1, 0, 1", mm::tuning(mm::TUNE_BITS_COUNT_VARIANT));
+  if (p.batch == 0 || p.n == 0 || p.m == 0) return MM_OK;
+  if (!p.c || (p.k && (!p.a || !p.b))) return fail(MM_ERR_BAD_ARGUMENT, "null matrix pointer");   // (K = 0: A, Bt unread)
+  const size_t kw = bits_words(p.k);
+  if (p.lda < kw || p.ldb < kw || p.ldc < p.m)
+    return fail(MM_ERR_BAD_ARGUMENT, "a row stride is below its row: lda %zu (needs %zu words), ldbt %zu (%zu words), ldc %zu (%u elements)",
+                p.lda, kw, p.ldb, kw, p.ldc, p.m);
+  const size_t c_elems = bits_span(p.n, p.m, p.ldc, 1, 0);
+  if (p.batch > 1 && p.stride_c < c_elems)
+    return fail(MM_ERR_BAD_ARGUMENT, "stride_c %zu < (N - 1) ldc + M = %zu: the outputs of the batch would overlap", p.stride_c, c_elems);
+  const size_t a_bytes = 4 * bits_span(p.n, kw, p.lda, p.batch, p.stride_a), b_bytes = 4 * bits_span(p.m, kw, p.ldb, p.batch, p.stride_b);
+  const size_t c_bytes = 4 * bits_span(p.n, p.m, p.ldc, p.batch, p.stride_c);
+  if (spans_overlap(p.c, c_bytes, p.a, a_bytes) || spans_overlap(p.c, c_bytes, p.b, b_bytes))
+    return fail(MM_ERR_BAD_ARGUMENT, "c overlaps a or bt (bases %p, %p, %p)", (const void *)p.a, (const void *)p.b, (void *)p.c);
+  if (p.k == 0 && p.seed) return MM_OK;   // accumulating over no k: C keeps its value
+  *ker = bits_count_demote(p, k);
+  return MM_OK;
+}
+
+// The batch in launches of at most 2^22 workgroups (64 x 64 tiles, the smaller of the two) and batch_chunk elements.
+int dispatch_bits_count(hipStream_t s, int op, const mm::BitsProblem &p, BitsKernel ker) {
+  const unsigned chunk = chunk_of_tiles((unsigned long long)((p.n + 63) / 64) * ((p.m + 63) / 64), p.batch);
+  (void)hipGetLastError();   // a stale error of the application's own calls must not be reported as this launch's
+  for (unsigned e0 = 0; e0 < p.batch; e0 += chunk) {
+    mm::BitsProblem q = p;
+    q.batch = std::min(chunk, p.batch - e0);
+    q.a += (size_t)e0 * p.stride_a;
+    q.b += (size_t)e0 * p.stride_b;
+    q.c += (size_t)e0 * p.stride_c;
+    if (int e = mm::launch_bits_count(s, q, op == MM_BITS_COUNT_XOR, ker == BITS_TILE))
+      return hip_fail((hipError_t)e, "packed counting kernel launch");
+  }
+  return MM_OK;
+}
+
+// c.src rows x cols, c.dst cols x rows, both packed: check_bits_convert's refusals with both sides in words
+int check_bits_transpose(const mm::BitsConvert &c, bool *nothing) {
+  *nothing = c.rows == 0 || c.cols == 0 || c.batch == 0;
+  if (*nothing) return MM_OK;
+  if (!c.src || !c.dst) return fail(MM_ERR_BAD_ARGUMENT, "null matrix pointer");
+  const size_t src_row = bits_words(c.cols), dst_row = bits_words(c.rows);
+  if (c.ld_src < src_row || c.ld_dst < dst_row)
+    return fail(MM_ERR_BAD_ARGUMENT, "a row stride is below its row: source %zu (needs %zu), destination %zu (%zu)", c.ld_src,
+                src_row, c.ld_dst, dst_row);
+  if (c.batch > 1 && c.stride_dst < bits_span(c.cols, dst_row, c.ld_dst, 1, 0))
+    return fail(MM_ERR_BAD_ARGUMENT, "destination batch stride %zu: the outputs of the batch would overlap", c.stride_dst);
+  if (spans_overlap(c.dst, 4 * bits_span(c.cols, dst_row, c.ld_dst, c.batch, c.stride_dst), c.src,
+                    4 * bits_span(c.rows, src_row, c.ld_src, c.batch, c.stride_src)))
+    return fail(MM_ERR_BAD_ARGUMENT, "the destination overlaps the source (bases %p, %p)", c.src, c.dst);
+  return MM_OK;
+}
+
+int dispatch_bits_transpose(hipStream_t s, const mm::BitsConvert &c) {
+  (void)hipGetLastError();
+  const int e = mm::launch_bits_transpose(s, c);
+  return e ? hip_fail((hipError_t)e, "packed transpose kernel launch") : MM_OK;
+}
+
 constexpr unsigned kBitsClosureBlock = 64;   // one wavefront closes a diagonal block: one row of 64 bits per lane
 
 int check_bits_closure(const void *d, unsigned n, size_t ldd, unsigned batch, size_t stride_d, bool *nothing) {
@@ -1231,6 +1316,18 @@ int run_bits_convert(const Target &t, const mm::BitsConvert &c, bool to_bits) {
   return run(t, nothing, [&](hipStream_t s) { return dispatch_bits_convert(s, c, to_bits); });
 }
 
+int run_bits_count(const Target &t, int op, const mm::BitsProblem &p) {
+  BitsKernel ker;
+  if (int rc = check_bits_count(op, p, &ker)) return rc;
+  return run(t, ker == BITS_NONE, [&](hipStream_t s) { return dispatch_bits_count(s, op, p, ker); });
+}
+
+int run_bits_transpose(const Target &t, const mm::BitsConvert &c) {
+  bool nothing;
+  if (int rc = check_bits_transpose(c, &nothing)) return rc;
+  return run(t, nothing, [&](hipStream_t s) { return dispatch_bits_transpose(s, c); });
+}
+
 int run_bits_closure(const Target &t, void *d, unsigned n, size_t ldd, unsigned batch, size_t stride_d) {
   bool nothing;
   if (int rc = check_bits_closure(d, n, ldd, batch, stride_d, &nothing)) return rc;
@@ -1589,6 +1686,30 @@ int mm_bits_pack_launch(int device, const void *bytes, void *packed, unsigned ro
                         unsigned batch, size_t stride_bytes, size_t stride_packed, double *elapsed_seconds) {
   return run_bits_convert(timed_on(device, elapsed_seconds),
                           {bytes, packed, rows, cols, ld_bytes, ld_packed, batch, stride_bytes, stride_packed}, true);
+}
+
+int mm_bits_count_enqueue(void *hip_stream, int op, const void *a, const void *bt, void *c, unsigned n, unsigned k, unsigned m,
+                          size_t lda, size_t ldbt, size_t ldc, unsigned batch, size_t stride_a, size_t stride_bt, size_t stride_c,
+                          int accumulate) {
+  return run_bits_count(on_stream(hip_stream), op, {(const uint32_t *)a, (const uint32_t *)bt, (uint32_t *)c, n, k, m, lda, ldbt, ldc,
+                                                    batch, stride_a, stride_bt, stride_c, accumulate != 0});
+}
+
+int mm_bits_count_launch(int device, int op, const void *a, const void *bt, void *c, unsigned n, unsigned k, unsigned m, size_t lda,
+                         size_t ldbt, size_t ldc, unsigned batch, size_t stride_a, size_t stride_bt, size_t stride_c, int accumulate,
+                         double *elapsed_seconds) {
+  return run_bits_count(timed_on(device, elapsed_seconds), op, {(const uint32_t *)a, (const uint32_t *)bt, (uint32_t *)c, n, k, m, lda,
+                                                                ldbt, ldc, batch, stride_a, stride_bt, stride_c, accumulate != 0});
+}
+
+int mm_bits_transpose_enqueue(void *hip_stream, const void *src, void *dst, unsigned rows, unsigned cols, size_t ld_src,
+                              size_t ld_dst, unsigned batch, size_t stride_src, size_t stride_dst) {
+  return run_bits_transpose(on_stream(hip_stream), {src, dst, rows, cols, ld_src, ld_dst, batch, stride_src, stride_dst});
+}
+
+int mm_bits_transpose_launch(int device, const void *src, void *dst, unsigned rows, unsigned cols, size_t ld_src, size_t ld_dst,
+                             unsigned batch, size_t stride_src, size_t stride_dst, double *elapsed_seconds) {
+  return run_bits_transpose(timed_on(device, elapsed_seconds), {src, dst, rows, cols, ld_src, ld_dst, batch, stride_src, stride_dst});
 }
 
 int mm_bits_unpack_enqueue(void *hip_stream, const void *packed, void *bytes, unsigned rows, unsigned cols, size_t ld_packed,
@@ -1990,6 +2111,15 @@ const char *mm_kernel_name_bits_gemm(unsigned n, unsigned k, unsigned m, size_t 
     case BITS_TILE: return "bits_tile";
     case BITS_INVALID: return "invalid";
     default: return "bits_plain";
+  }
+}
+
+const char *mm_kernel_name_bits_count(unsigned n, unsigned k, unsigned m, size_t lda, size_t ldbt, size_t ldc, unsigned batch) {
+  (void)k, (void)batch;   // the batch is chunked, never a different kernel
+  switch (bits_count_kernel_for(n, m, lda, ldbt, ldc)) {   // the choice check_bits_count makes, before alignment
+    case BITS_TILE: return "bits_count_tile";
+    case BITS_INVALID: return "invalid";
+    default: return "bits_count_plain";
   }
 }
 

@@ -204,6 +204,14 @@ struct BitsConvert {
 };
 int launch_bits_pack(hipStream_t s, const BitsConvert &c);
 int launch_bits_unpack(hipStream_t s, const BitsConvert &c);
+// Bit-packed counting product (mm_bits_count_*, mm_bits_count.hip): C[i][j] = sum_k (A[i][k] op Bt[j][k]), op AND or XOR, as
+// int32.  p.b is Bt, M x K packed along K (ldb = ldbt, words); p.c is N x M int32 (ldc and stride_c in elements); seed: C +=.
+// tile: "bits_count_tile" (bits_count_tile_serves() on the ld's, 16-byte aligned bases and batch strides), else
+// "bits_count_plain" (anything).
+bool bits_count_tile_serves(size_t lda, size_t ldbt, size_t ldc);   // the ld half of the rule; the tile-count half is mm_capi.hip's
+int launch_bits_count(hipStream_t s, const BitsProblem &p, bool xor_op, bool tile);
+// src rows x cols -> dst cols x rows, both packed (ld and batch strides in words); dst's padding bits are written 0.
+int launch_bits_transpose(hipStream_t s, const BitsConvert &c);
 // The wavefront kernel of the packed closure (mm_bits_closure.hip): closes block [k0, k0 + min(64, n - k0)) of `graphs` graphs
 // at d + e * stride_d.  pstar null: writes the closed block back into D (the on-chip closure, k0 = 0, n <= 64); else leaves D
 // alone and writes P | I as 64 rows x 2 words at pstar + e * stride_p.
@@ -404,6 +412,8 @@ enum Tunable {
                            //                 the fallback (the cross-check); -1: the default (hybrid)
   TUNE_BITS_VARIANT,       // MM_BITS_VARIANT  mm_bits_gemm_*: 0 bits_plain always, 1 bits_tile wherever its ld rule holds (any M);
                            //                 -1: the default (bits_tile for M > 2048)
+  TUNE_BITS_COUNT_VARIANT, // MM_BITS_COUNT_VARIANT  mm_bits_count_*: 0 bits_count_plain always, 1 bits_count_tile wherever its ld rule
+                           //                 holds (any shape); -1: the default (bits_count_tile from 256 tiles of 128 x 128)
   TUNE_COUNT
 };
 int tuning(Tunable t);  // mm_capi.hip

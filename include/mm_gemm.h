@@ -563,6 +563,9 @@ int mm_bits_unpack_enqueue(void *hip_stream, const void *packed_dev, void *bytes
 int mm_bits_unpack_launch(int device, const void *packed_dev, void *bytes_dev, unsigned rows, unsigned cols, size_t ld_packed,
                           size_t ld_bytes, unsigned batch, size_t stride_packed, size_t stride_bytes, double *elapsed_seconds);
 
+/* Counting products on the packed format (popcount AND / XOR to int32, A x B^T: mm_bits_count_*) and the packed transpose
+ * (mm_bits_transpose_*): "mm_bits_count.h", a header of their own, included at the end of this one. */
+
 /* One node, `device_count` GPUs, rows of C split into contiguous slabs (device g gets the rows mm_row_slab() names), B
  * replicated, no collective: every outer tile of C is independent (kernel/Compute.cpp:53-60, kernel/Memory.cpp:114-127,
  * 272-286, 367-391).  Host pointers in, host pointer out; copies are outside the timed region exactly as in
@@ -658,7 +661,7 @@ int mm_kernel_info(const mm_config_t *cfg, unsigned size_n, unsigned size_k, uns
  * 0.2-30 % slower (its release fence writes the L2 back; profiles/r06d_*), kept as the cross-check of the shipped flag protocol; 9 stream-K in
  * single ranges with its own fix-up kernel (cross-check, its own bits).
  * "closure_block": the block size of mm_closure_* (see there).  "lse_variant": the kernels of mm_gemm_logsumexp_* (see there).
- * "bits_variant": the kernels of mm_bits_gemm_* (see there).
+ * "bits_variant": the kernels of mm_bits_gemm_* (see there).  "bits_count_variant": the kernels of mm_bits_count_* (see there).
  * "debug_poison" = 1 fills the scratch that kernels hand partial tiles through, and C itself (pure output), with NaN before
  * every stream-K launch: a read of anything the launch did not write, or a tile nobody finished, then shows in C (tests only).  "md_virtual_devices": see mm_gemm_multi_device.  Any
  * other id is refused: the retired schedules and the work-skipping ablations of the measurement history exist only in the
@@ -675,4 +678,5 @@ const char *mm_last_error(void);
 #ifdef __cplusplus
 }
 #endif
+#include "mm_bits_count.h"
 #endif /* MM_GEMM_H */

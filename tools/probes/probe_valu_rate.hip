@@ -79,6 +79,14 @@ __global__ __launch_bounds__(1024) void k(float *out, unsigned long long *cyc, f
         asm volatile("v_mul_f64 %0, %1, %2" : "=v"(s0) : "v"(dx), "v"(da[(i + 1) & 15]));
         asm volatile("v_add_f64 %0, %0, %1" : "+v"(da[i]) : "v"(s0));
       }
+      // the packed counting products (mm_bits_count.hip): per output and 32 k one AND and one accumulating population count
+      if (MODE == 22) asm volatile("v_and_b32 %0, %0, %1" : "+v"(a[i]) : "v"(x));
+      if (MODE == 23) asm volatile("v_bcnt_u32_b32 %0, %1, %0" : "+v"(a[i]) : "v"(x));
+      if (MODE == 24) {
+        float s0;
+        asm volatile("v_and_b32 %0, %1, %2" : "=v"(s0) : "v"(x), "v"(a[(i + 1) & 15]));
+        asm volatile("v_bcnt_u32_b32 %0, %1, %0" : "+v"(a[i]) : "v"(s0));
+      }
       // the float min-plus inner loop as valu_tile compiles it: per accumulator and pair of k-steps
       // two adds into temporaries and ONE v_min3 (acc, s0, s1): 3 instructions per 4 operations
       if (MODE == 9) {
@@ -171,6 +179,9 @@ int main() {
     run<19>("unfused mul-add f32 packed: v_pk_mul + v_pk_add", 2, 4, wps, d, dc);
     run<20>("unfused mul-add f16 packed: v_pk_mul_f16 + v_pk_add_f16", 2, 4, wps, d, dc);
     run<21>("unfused mul-add f64: v_mul_f64 + v_add_f64", 2, 2, wps, d, dc);
+    run<22>("v_and_b32", 1, 0, wps, d, dc);
+    run<23>("v_bcnt_u32_b32 (accumulating)", 1, 0, wps, d, dc);
+    run<24>("count step: v_and_b32 + v_bcnt_u32_b32", 2, 1, wps, d, dc);
   }
   return 0;
 }
