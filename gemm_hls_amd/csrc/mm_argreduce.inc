@@ -12,6 +12,7 @@
 //     map, 16-byte aligned operands -- what valu_tile_serves() serves -- and an element of at most 4 bytes: 8 x 8
 //     8-byte values, their indices and the prefetch do not fit 256 VGPRs (the compiler spilled to AGPRs, and the kernel
 //     ran slower than argreduce), so the 8-byte types are not instantiated here.
+//     valu_tile_kernel's geometry: constants and Vec4 in mm_tile128.h, the staging written out here (why: that header).
 //   * argreduce_kernel: 64 x 64 outputs per 256-thread workgroup, 4 x 4 per thread, fully predicated: any shape, any
 //     element-aligned pointer, every map.  The parity anchor (MM_PATH_ORDERED always runs it).  Tile origin and staging:
 //     mm_tile64.h.
@@ -23,12 +24,11 @@
 // BT = false compiles to what it did before the flag existed (profiles/nt_products_isa_identity.txt).
 // Included once per element-type group (mm_argreduce_*.hip) to keep compile units parallel; every unit says
 // `#pragma clang fp contract(off)` before including this: the map is one rounded operation, like Naive's.
+#include "mm_tile128.h"
 #include "mm_tile64.h"
 
 namespace mm {
 namespace {
-
-template <typename T> struct alignas(4 * sizeof(T)) ArVec4 { T v[4]; };
 
 // true when the mapped value s replaces acc (the select of Op<RED, T>::apply(acc, s))
 template <int RED, typename T> __device__ __forceinline__ bool ar_takes(T s, T acc) {
@@ -43,18 +43,16 @@ template <int RED, typename T> __device__ __forceinline__ T ar_start() {
   else return Op<RED, T>::identity();
 }
 
-constexpr int AR_BM = 128, AR_BN = 128, AR_BK = 16, AR_PAD = 4;
-
 template <typename T, int MAP, int RED, bool AT, bool BT>
 __global__ __launch_bounds__(256) void argreduce_tile_kernel(const T *__restrict__ A, const T *__restrict__ B,
                                                              T *__restrict__ C, int *__restrict__ I, unsigned N, unsigned K,
                                                              unsigned M, unsigned tiles_n, unsigned tiles_m, unsigned kBand,
                                                              unsigned batch, size_t stride_a, size_t stride_b,
                                                              size_t stride_c, int index_base, int seeded) {
-  __shared__ __attribute__((aligned(16))) T As[AR_BK][AR_BM + AR_PAD];
-  __shared__ __attribute__((aligned(16))) T Bs[AR_BK][AR_BN + AR_PAD];
-  using V = ArVec4<T>;
-  using VI = ArVec4<int>;
+  __shared__ __attribute__((aligned(16))) T As[kBK128][kTile128 + kPad128];
+  __shared__ __attribute__((aligned(16))) T Bs[kBK128][kTile128 + kPad128];
+  using V = Vec4<T>;
+  using VI = Vec4<int>;
   const unsigned tid = threadIdx.x, tx = tid % 16, ty = tid / 16;
   // batched_tile()'s (element, tile) decomposition, with I moved by the element like C (same element strides)
   const unsigned tiles = tiles_n * tiles_m;
@@ -63,9 +61,8 @@ __global__ __launch_bounds__(256) void argreduce_tile_kernel(const T *__restrict
   B += e * stride_b;
   C += e * stride_c;
   I += e * stride_c;
-  const unsigned band = lin / (kBand * tiles_m), within = lin % (kBand * tiles_m);
-  const unsigned rows_in_band = min(kBand, tiles_n - band * kBand);
-  const unsigned row0 = (band * kBand + within % rows_in_band) * AR_BM, col0 = (within / rows_in_band) * AR_BN;
+  unsigned row0, col0;
+  band_origin(lin, tiles_n, tiles_m, kBand, kTile128, kTile128, row0, col0);
 
   // The chain runs from `start` (Min: +inf, Max: -inf for floating types; identity() for integers) with no index, and
   // the seed (C and I, or identity() and -1) is merged in at the store: the chain from the seed S takes the first k of the
@@ -126,15 +123,15 @@ __global__ __launch_bounds__(256) void argreduce_tile_kernel(const T *__restrict
   stage(tid, ra0, rb0);
   stage(tid + 256, ra1, rb1);
   __syncthreads();
-  for (unsigned k0 = 0; k0 < K; k0 += AR_BK) {
-    const bool more = k0 + AR_BK < K;
+  for (unsigned k0 = 0; k0 < K; k0 += kBK128) {
+    const bool more = k0 + kBK128 < K;
     if (more) {   // in flight under this slab's VALU work
-      ra0 = fetch_a(k0 + AR_BK, tid);
-      ra1 = fetch_a(k0 + AR_BK, tid + 256);
-      rb0 = fetch_b(k0 + AR_BK, tid);
-      rb1 = fetch_b(k0 + AR_BK, tid + 256);
+      ra0 = fetch_a(k0 + kBK128, tid);
+      ra1 = fetch_a(k0 + kBK128, tid + 256);
+      rb0 = fetch_b(k0 + kBK128, tid);
+      rb1 = fetch_b(k0 + kBK128, tid + 256);
     }
-    const unsigned kmax = min((unsigned)AR_BK, K - k0);
+    const unsigned kmax = min((unsigned)kBK128, K - k0);
     const int kg0 = index_base + (int)k0;   // global k of the slab's first step; uniform
 #pragma unroll 1
     for (unsigned kk = 0; kk < kmax; ++kk) {
@@ -278,7 +275,7 @@ int ar_launch(hipStream_t s, const Problem &p, int *index, int index_base, bool 
     if constexpr (MAP == MM_OP_AND || sizeof(T) > 4) {
       return kErrNotSupported;
     } else {
-      const unsigned tiles_n = (p.n + AR_BM - 1) / AR_BM, tiles_m = (p.m + AR_BN - 1) / AR_BN;
+      const unsigned tiles_n = (p.n + kTile128 - 1) / kTile128, tiles_m = (p.m + kTile128 - 1) / kTile128;
       MM_AR_LAUNCH(argreduce_tile_kernel, dim3(tiles_n * tiles_m * p.batch), (const T *)p.a, (const T *)p.b, (T *)p.c, index,
                    p.n, p.k, p.m, tiles_n, tiles_m, band_rows(), p.batch, p.stride_a, p.stride_b, p.stride_c, index_base,
                    seeded);

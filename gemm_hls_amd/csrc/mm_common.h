@@ -470,6 +470,18 @@ __device__ __forceinline__ unsigned xcd_remap(unsigned bid, unsigned nwg) {
   return base + slot;
 }
 
+// The band rasterisation above, on the device: the first row and column of the bm x bn tile that linear tile id `lin` names in
+// a grid of tiles_n x tiles_m tiles with bands of kBand tile-rows.  bm = bn = 1: the tile's row and column index.
+__device__ __forceinline__ void band_origin(unsigned lin, unsigned tiles_n, unsigned tiles_m, unsigned kBand, unsigned bm,
+                                            unsigned bn, unsigned &row0, unsigned &col0) {
+  const unsigned band = lin / (kBand * tiles_m), within = lin % (kBand * tiles_m);
+  const unsigned rows_in_band = min(kBand, tiles_n - band * kBand);
+  row0 = (band * kBand + within % rows_in_band) * bm, col0 = (within / rows_in_band) * bn;
+}
+
+// One LDS-DMA piece of an asm statement that saves and restores m0: 64 lanes x 16 B from (uniform base sb + per-lane offset vo) to LDS at la
+#define MM_DMA_PIECE(vo, sb, la) "s_mov_b32 m0, " la "\n\ts_nop 0\n\tglobal_load_lds_dwordx4 " vo ", " sb "\n\t"
+
 // The three forms every kernel of the older families exists in, a template parameter of the kernel: the single launch,
 // the strided-batched launch, and the batched launch whose reduction starts at the value C holds (Problem::seed; Seeded
 // implies batched).  Every form takes the batched argument list (..., batch, stride_a, stride_b, stride_c); Form::Single

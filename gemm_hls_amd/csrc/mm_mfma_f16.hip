@@ -38,8 +38,6 @@ namespace {
 
 #include "mm_mfma_f16_kernels.inc"
 
-#undef MM_DMA_PIECE
-
 }  // namespace
 
 bool mfma_f16_serves(const Problem &p) {

@@ -78,9 +78,8 @@ __global__ __launch_bounds__(G::THREADS) void mfma_f16_kernel(const _Float16 *__
 
   const unsigned nwg = tiles_n * tiles_m;
   const unsigned lin = form_tile<F>(A, B, C, nwg, batch, stride_a, stride_b, stride_c);
-  const unsigned band = lin / (kBand * tiles_m), within = lin % (kBand * tiles_m);
-  const unsigned rows_in_band = min(kBand, tiles_n - band * kBand);
-  const unsigned row0 = (band * kBand + within % rows_in_band) * G::BM, col0 = (within / rows_in_band) * G::BN;
+  unsigned row0, col0;
+  band_origin(lin, tiles_n, tiles_m, kBand, G::BM, G::BN, row0, col0);
 
   // ---- DMA sources ---------------------------------------------------------------------------
   size_t a_row_off[G::LA];
@@ -318,9 +317,6 @@ struct GeoPP {
   static constexpr int BROW = BN * 2;
 };
 
-// one LDS-DMA piece: 64 lanes x 16 B from (uniform base + per-lane 32-bit offset) to LDS at m0
-#define MM_DMA_PIECE(vo, sb, la) "s_mov_b32 m0, " la "\n\ts_nop 0\n\tglobal_load_lds_dwordx4 " vo ", " sb "\n\t"
-
 template <Form F, bool AT, typename CT = _Float16>  // AT: A stored K x N (MM_TRANSPOSED_A): the A slab is staged and gathered exactly like B's
 __global__ __launch_bounds__(GeoPP::THREADS) void mfma_f16_pp_kernel(const _Float16 *__restrict__ A,
                                                                        const _Float16 *__restrict__ B,
@@ -340,6 +336,7 @@ __global__ __launch_bounds__(GeoPP::THREADS) void mfma_f16_pp_kernel(const _Floa
 
   const unsigned nwg = tiles_n * tiles_m;
   const unsigned lin = form_tile<F>(A, B, C, nwg, batch, stride_a, stride_b, stride_c);
+  // (not band_origin: through it the Batched K x N form with a wide C was allocated other registers, profiles/tile128_isa_identity.txt)
   const unsigned band = lin / (kBand * tiles_m), within = lin % (kBand * tiles_m);
   const unsigned rows_in_band = min(kBand, tiles_n - band * kBand);
   const unsigned row0 = (band * kBand + within % rows_in_band) * G::BM, col0 = (within / rows_in_band) * G::BN;
@@ -546,9 +543,8 @@ __global__ __launch_bounds__(GeoPP2::THREADS) void mfma_f16_pp2_kernel(const _Fl
   const unsigned lo = lane & 31u, hi = lane >> 5;
 
   const unsigned lin = form_tile<F>(A, B, C, tiles_n * tiles_m, batch, stride_a, stride_b, stride_c);
-  const unsigned band = lin / (kBand * tiles_m), within = lin % (kBand * tiles_m);
-  const unsigned rows_in_band = min(kBand, tiles_n - band * kBand);
-  const unsigned row0 = (band * kBand + within % rows_in_band) * G::BM, col0 = (within / rows_in_band) * G::BN;
+  unsigned row0, col0;
+  band_origin(lin, tiles_n, tiles_m, kBand, G::BM, G::BN, row0, col0);
 
   // ---- DMA offsets: A double slab = 32 pieces of 8 rows x 128 B (4 per wave), B slab = 16 pieces of 2 k-rows
   unsigned voff_a[4], voff_b[2];
@@ -769,9 +765,8 @@ __global__ __launch_bounds__(GeoPP2::THREADS) void mfma_f16_pp2s_kernel(const _F
   const unsigned l15 = lane & 15u, g = lane >> 4;
 
   const unsigned lin = form_tile<F>(A, B, C, tiles_n * tiles_m, batch, stride_a, stride_b, stride_c);
-  const unsigned band = lin / (kBand * tiles_m), within = lin % (kBand * tiles_m);
-  const unsigned rows_in_band = min(kBand, tiles_n - band * kBand);
-  const unsigned row0 = (band * kBand + within % rows_in_band) * G::BM, col0 = (within / rows_in_band) * G::BN;
+  unsigned row0, col0;
+  band_origin(lin, tiles_n, tiles_m, kBand, G::BM, G::BN, row0, col0);
 
   unsigned voff_a[4], voff_b[2];
 #pragma unroll

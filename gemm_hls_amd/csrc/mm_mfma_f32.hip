@@ -125,11 +125,9 @@ __global__ __launch_bounds__(G::THREADS, G::MIN_WAVES) void mfma_f32_batched_ker
     const float *__restrict__ A, const float *__restrict__ B, float *__restrict__ C, unsigned N, unsigned K, unsigned M,
     unsigned tiles_n, unsigned tiles_m, unsigned kBand, unsigned batch, size_t stride_a, size_t stride_b, size_t stride_c) {
   const unsigned lin = batched_tile(A, B, C, tiles_n * tiles_m, batch, stride_a, stride_b, stride_c);
-  const unsigned band = lin / (kBand * tiles_m), within = lin % (kBand * tiles_m);
-  const unsigned rows_in_band = min(kBand, tiles_n - band * kBand);
-  const unsigned tile_row = band * kBand + within % rows_in_band;
-  const unsigned tile_col = within / rows_in_band;
-  tile_body<G, AT, false, SEED>(A, B, C, N, K, M, K, M, N, M, tile_row * G::BM, tile_col * G::BN);
+  unsigned row0, col0;
+  band_origin(lin, tiles_n, tiles_m, kBand, G::BM, G::BN, row0, col0);
+  tile_body<G, AT, false, SEED>(A, B, C, N, K, M, K, M, N, M, row0, col0);
 }
 
 template <typename G, bool AT, bool SEED>

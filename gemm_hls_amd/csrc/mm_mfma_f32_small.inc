@@ -46,9 +46,8 @@ __global__ __launch_bounds__(G::THREADS, G::PER_CU) void mfma_f32_small_kernel(
     K = min(kChunk, K - kbeg);
   }
   const unsigned lin = xcd_remap(bid, nwg);
-  const unsigned band = lin / (kBand * tiles_m), within = lin % (kBand * tiles_m);
-  const unsigned rows_in_band = min(kBand, tiles_n - band * kBand);
-  const unsigned row0 = (band * kBand + within % rows_in_band) * G::BM, col0 = (within / rows_in_band) * G::BN;
+  unsigned row0, col0;
+  band_origin(lin, tiles_n, tiles_m, kBand, G::BM, G::BN, row0, col0);
 
   const unsigned lane = threadIdx.x & 63u;
   const unsigned wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);

@@ -152,9 +152,8 @@ void mfma_f32_split_kernel(const char *__restrict__ Ap, const char *__restrict__
   const unsigned lo = lane & 31u, hi = lane >> 5;
 
   const unsigned lin = xcd_remap(blockIdx.x, tiles_n * tiles_m);
-  const unsigned band = lin / (kBand * tiles_m), within = lin % (kBand * tiles_m);
-  const unsigned rows_in_band = min(kBand, tiles_n - band * kBand);
-  const unsigned tile_r = band * kBand + within % rows_in_band, tile_c = within / rows_in_band;
+  unsigned tile_r, tile_c;   // tile indices: the packed operands are addressed by tile
+  band_origin(lin, tiles_n, tiles_m, kBand, 1, 1, tile_r, tile_c);
 
   // ---- DMA: wavefront w moves fragment w of each plane of the tile's A slab and B slab (1 KiB pieces: source plane
   // stride 8 KiB in the packed layout, LDS plane stride FR KiB); a 128-row tile is one half of a packed 256-row block

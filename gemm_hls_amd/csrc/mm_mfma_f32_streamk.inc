@@ -27,9 +27,8 @@ __global__ __launch_bounds__(G::THREADS, G::MIN_WAVES) void mfma_f32_streamk_ker
   const unsigned first_tile = u0 / spt;
   for (unsigned u = u0; u < u1;) {
     const unsigned tile = u / spt, s0 = u - tile * spt, s1 = min(spt, s0 + (u1 - u));
-    const unsigned band = tile / (kBand * tiles_m), within = tile % (kBand * tiles_m);
-    const unsigned rows_in_band = min(kBand, tiles_n - band * kBand);
-    const unsigned row0 = (band * kBand + within % rows_in_band) * G::BM, col0 = (within / rows_in_band) * G::BN;
+    unsigned row0, col0;
+    band_origin(tile, tiles_n, tiles_m, kBand, G::BM, G::BN, row0, col0);
     const unsigned kbeg = s0 * G::BK, klen = (s1 - s0) * G::BK;
     const float *a = A + kbeg, *b = B + (size_t)kbeg * M;
     if (s0 == 0 && s1 == spt) {
@@ -360,9 +359,8 @@ __global__ __launch_bounds__(256) void streamk_fixup_kernel(const float *__restr
   while (w + 1 < nwg && sk_range_begin(units, w + 1, nwg) <= u_lo) ++w;
   while (w > 0 && sk_range_begin(units, w, nwg) > u_lo) --w;
   if (sk_range_begin(units, w + 1, nwg) >= u_hi) return;   // one range holds the whole tile
-  const unsigned band = tile / (kBand * tiles_m), within = tile % (kBand * tiles_m);
-  const unsigned rows_in_band = min(kBand, tiles_n - band * kBand);
-  const unsigned row0 = (band * kBand + within % rows_in_band) * BM, col0 = (within / rows_in_band) * BN;
+  unsigned row0, col0;
+  band_origin(tile, tiles_n, tiles_m, kBand, BM, BN, row0, col0);
   constexpr int QUADS = BM * BN / 4 / 256;
   f32x4 acc[QUADS];
 #pragma unroll

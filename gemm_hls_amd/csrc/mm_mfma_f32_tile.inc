@@ -515,11 +515,8 @@ __global__ __launch_bounds__(G::THREADS, G::MIN_WAVES) void mfma_f32_kernel(cons
     K = min(kChunk, K - kbeg);
   }
   // ---- workgroup -> output tile: XCD-contiguous chunks, then bands of kBand tile-rows ------------
-  const unsigned lin = xcd_remap(bid, nwg);
-  const unsigned band = lin / (kBand * tiles_m), within = lin % (kBand * tiles_m);
-  const unsigned rows_in_band = min(kBand, tiles_n - band * kBand);
-  const unsigned tile_row = band * kBand + within % rows_in_band;
-  const unsigned tile_col = within / rows_in_band;
-  tile_body<G, AT>(A, B, C, N, K, M, lda, M, N, M, tile_row * G::BM, tile_col * G::BN);
+  unsigned row0, col0;
+  band_origin(xcd_remap(bid, nwg), tiles_n, tiles_m, kBand, G::BM, G::BN, row0, col0);
+  tile_body<G, AT>(A, B, C, N, K, M, lda, M, N, M, row0, col0);
 }
 

@@ -17,9 +17,8 @@ __global__ __launch_bounds__(G::THREADS, G::MIN_WAVES) void mfma_f64_kernel(  //
 
   const unsigned nwg = tiles_n * tiles_m;
   const unsigned lin = form_tile<F>(A, B, C, nwg, batch, stride_a, stride_b, stride_c);
-  const unsigned band = lin / (kBand * tiles_m), within = lin % (kBand * tiles_m);
-  const unsigned rows_in_band = min(kBand, tiles_n - band * kBand);
-  const unsigned row0 = (band * kBand + within % rows_in_band) * G::BM, col0 = (within / rows_in_band) * G::BN;
+  unsigned row0, col0;
+  band_origin(lin, tiles_n, tiles_m, kBand, G::BM, G::BN, row0, col0);
 
   size_t a_row_off[G::LA];
   unsigned a_kchunk[G::LA];

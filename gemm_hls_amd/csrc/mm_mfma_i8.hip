@@ -32,7 +32,6 @@ namespace mm {
 namespace {
 
 #include "mm_mfma_i8_kernels.inc"
-#undef MM_DMA_PIECE
 
 }  // namespace
 

@@ -66,9 +66,8 @@ __global__ __launch_bounds__(G::THREADS) void mfma_i8_kernel(const signed char *
   const unsigned lo = lane & 31u, hi = lane >> 5;
 
   const unsigned lin = form_tile<F>(A, B, C, tiles_n * tiles_m, batch, stride_a, stride_b, stride_c);
-  const unsigned band = lin / (kBand * tiles_m), within = lin % (kBand * tiles_m);
-  const unsigned rows_in_band = min(kBand, tiles_n - band * kBand);
-  const unsigned row0 = (band * kBand + within % rows_in_band) * G::BM, col0 = (within / rows_in_band) * G::BN;
+  unsigned row0, col0;
+  band_origin(lin, tiles_n, tiles_m, kBand, G::BM, G::BN, row0, col0);
 
   // ---- DMA sources ---------------------------------------------------------------------------
   size_t a_row_off[G::LA];
@@ -265,7 +264,6 @@ struct GeoI8PP {
   static constexpr int LDS_BYTES = NS * STAGE_BYTES;
   static constexpr int BROW = BN;
 };
-#define MM_DMA_PIECE(vo, sb, la) "s_mov_b32 m0, " la "\n\ts_nop 0\n\tglobal_load_lds_dwordx4 " vo ", " sb "\n\t"
 
 template <Form F, bool AT, typename CT = signed char>  // AT: A stored K x N, staged and gathered like B
 __global__ __launch_bounds__(GeoI8PP::THREADS) void mfma_i8_pp_kernel(const signed char *__restrict__ A,
@@ -285,6 +283,7 @@ __global__ __launch_bounds__(GeoI8PP::THREADS) void mfma_i8_pp_kernel(const sign
   const unsigned l15 = lane & 15u, g = lane >> 4;
 
   const unsigned lin = form_tile<F>(A, B, C, tiles_n * tiles_m, batch, stride_a, stride_b, stride_c);
+  // (not band_origin: through it the Batched K x N form with a wide C was allocated other registers, profiles/tile128_isa_identity.txt)
   const unsigned band = lin / (kBand * tiles_m), within = lin % (kBand * tiles_m);
   const unsigned rows_in_band = min(kBand, tiles_n - band * kBand);
   const unsigned row0 = (band * kBand + within % rows_in_band) * G::BM, col0 = (within / rows_in_band) * G::BN;
@@ -457,9 +456,8 @@ __global__ __launch_bounds__(GeoI8PP2::THREADS) void mfma_i8_pp2_kernel(const si
   const unsigned lo = lane & 31u, hi = lane >> 5;
 
   const unsigned lin = form_tile<F>(A, B, C, tiles_n * tiles_m, batch, stride_a, stride_b, stride_c);
-  const unsigned band = lin / (kBand * tiles_m), within = lin % (kBand * tiles_m);
-  const unsigned rows_in_band = min(kBand, tiles_n - band * kBand);
-  const unsigned row0 = (band * kBand + within % rows_in_band) * G::BM, col0 = (within / rows_in_band) * G::BN;
+  unsigned row0, col0;
+  band_origin(lin, tiles_n, tiles_m, kBand, G::BM, G::BN, row0, col0);
 
   unsigned voff_a[4], voff_b[2];
 #pragma unroll
@@ -647,9 +645,8 @@ __global__ __launch_bounds__(GeoI8PP2::THREADS) void mfma_i8_pp2s_kernel(const s
   const unsigned l15 = lane & 15u, g = lane >> 4;
 
   const unsigned lin = form_tile<F>(A, B, C, tiles_n * tiles_m, batch, stride_a, stride_b, stride_c);
-  const unsigned band = lin / (kBand * tiles_m), within = lin % (kBand * tiles_m);
-  const unsigned rows_in_band = min(kBand, tiles_n - band * kBand);
-  const unsigned row0 = (band * kBand + within % rows_in_band) * G::BM, col0 = (within / rows_in_band) * G::BN;
+  unsigned row0, col0;
+  band_origin(lin, tiles_n, tiles_m, kBand, G::BM, G::BN, row0, col0);
 
   unsigned voff_a[4], voff_b[2];
 #pragma unroll

@@ -9,7 +9,7 @@ bool valu_tile_nt_serves(const mm_config_t &cfg, const Problem &p) {
   const bool map_ok = cfg.map_op == MM_OP_MULTIPLY || cfg.map_op == MM_OP_ADD || cfg.map_op == MM_OP_MIN || cfg.map_op == MM_OP_MAX;
   const bool red_ok = cfg.reduce_op == MM_OP_ADD || cfg.reduce_op == MM_OP_MIN || cfg.reduce_op == MM_OP_MAX;
   if (!map_ok || !red_ok) return false;
-  return switch_dtype<AllTypes>(cfg.dtype, [&](auto t) { return (int)vt_nt_shape_serves<type_of<decltype(t)>>(p); }) == 1;
+  return switch_dtype<AllTypes>(cfg.dtype, [&](auto t) { return (int)vt_dma_k_serves<type_of<decltype(t)>>(p); }) == 1;
 }
 
 // the p.batch elements of p (strides p.stride_*), accumulating into C for p.seed

@@ -99,6 +99,29 @@ def test_batched_auto_exact_configs_equal_the_single_launch(dtype, mp, rd, shape
         assert sr.same_bits(got, single), (e, g.kernel_name(cfg, n, k, m), g.kernel_name_batched(cfg, n, k, m, batch))
 
 
+def test_batched_synchronous_row_major_tile_kernel_ragged_below_a_slab():
+    """valu_variant 0 with a row-major A: the Batched form of the synchronous register-tile kernel, which the cases above (DMA-staged,
+    or synchronous with a K x N A) do not launch.  130 x 132 is two tiles each way with a last tile of 2 rows and 4 columns, K = 4
+    is less than a slab, and the element strides are padded by 16 elements (the tile kernels want 16-byte aligned elements).
+    Integer (Add, Min): every element Naive's bits, C's pads untouched."""
+    n, k, m, batch, pad = 130, 4, 132, 3, 16
+    sa, sb, sc = n * k + pad, k * m + pad, n * m + pad
+    rng = np.random.default_rng(n + k + m)
+    a, b = random_operands("int", (batch, sa), rng), random_operands("int", (batch, sb), rng)
+    c_init = np.full((batch - 1) * sc + n * m, -7, dtype=np.int32)
+    cfg = g.make_config("int", "Add", "Min")
+    g.set_tuning("valu_variant", 0)
+    try:
+        assert g.kernel_name_batched(cfg, n, k, m, batch) == "valu_tile"
+        c = batched_launch(cfg, a.ravel(), b.ravel(), n, k, m, batch, sa, sb, sc, c_init=c_init)
+    finally:
+        g.set_tuning("valu_variant", -1)
+    for e in range(batch):
+        want = _oracle.naive("int", "Add", "Min", a[e, :n * k].reshape(n, k), b[e, :k * m].reshape(k, m))
+        assert sr.same_bits(element(c, e, sc, n, m), want), (e, sr.first_difference(element(c, e, sc, n, m), want))
+        assert np.all(c[e * sc + n * m:(e + 1) * sc] == -7), e
+
+
 # ---- floating (Multiply, Add) --------------------------------------------------------------------------------------
 @pytest.mark.parametrize("variant", [-1, 33, 8, 35])
 @pytest.mark.parametrize("ta", [False, True], ids=["rowmajorA", "KxN_A"])
