@@ -13,6 +13,7 @@
 //                       cross-check of the default (f16_variant 100); also what round 2 shipped
 //   pingpong_k32        32-deep slabs with 64-byte A rows (K % 32 == 0, K >= 128), row-major and K x N A
 //   slab64              one barrier per 64-deep slab (K % 16 == 0; any N; 256 x 256, or 128 x 256 for small problems)
+// The two pingpong_NxNxK kernels share their protocol and geometry with the int8 pair: mm_pingpong2.h.
 // Each is one row of kTable at the end of mm_mfma_f16_kernels.inc (name, wide twin, geometry, instruction, efficiency); this unit
 // holds the rules that pick a row (resolve) and launches it through the include's launch_kind.
 // The schedules and ablations these went through (lock step, early barrier, DMA cache policies, no-DMA / no-read power
@@ -32,6 +33,7 @@
 #include <type_traits>
 
 #include "mm_common.h"
+#include "mm_pingpong2.h"
 
 namespace mm {
 namespace {

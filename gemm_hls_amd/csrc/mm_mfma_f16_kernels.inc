@@ -507,24 +507,10 @@ __global__ __launch_bounds__(GeoPP::THREADS) void mfma_f16_pp_kernel(const _Floa
 }
 
 // -------------------------------------------------------------------------------------------------
-// Ping-pong with full-line A requests.  A 32-deep slab gives A rows of 64 bytes, i.e. TWO L2 requests per 128-byte
-// line (one per slab); measured: 817 M vs 546 M L2 requests per 16384^3 launch at identical misses, on a kernel
-// whose power budget goes into exactly that path (DESIGN.md 3.2).  Here A is staged in DOUBLE slabs
-// [256 rows][64 k] (128-byte rows, one request per line, chunk index ^ (row>>1)&7), each double slab
-// serving two consecutive segments; B stays in 32-deep slabs.  LDS: 3 A double slabs (96 KiB) +
-// 4 B slabs (64 KiB) = all 160 KiB.  A wave still issues 4 DMA pieces per load segment: 2 of A
-// (its half of double slab u/2 + 2) and 2 of B (slab u + 3); the counted vmcnt(8) and the barrier
-// pairing are unchanged.  Requirements: K % 64 == 0, K >= 256.
+// Ping-pong with full-line A requests (mm_pingpong2.h: the protocol and the geometry); B in 32-deep slabs [32 k][256 cols],
+// 512-byte k-rows.  Requirements: K % 64 == 0, K >= 256.
 // pingpong_32x32x16: this organisation on v_mfma_f32_32x32x16_f16 (4 x 2 accumulators of 32 x 32 per wavefront).
-struct GeoPP2 {
-  static constexpr int BM = 256, BN = 256, BK = 32, THREADS = 512;
-  static constexpr int TM = 4, TN = 2;
-  static constexpr int A2_BYTES = BM * 64 * 2, NA = 3;          // A double slab: 32 KiB, ring of 3
-  static constexpr int B_BYTES = BK * BN * 2, NB = 4;           // B slab: 16 KiB, ring of 4
-  static constexpr int B_REGION = NA * A2_BYTES;
-  static constexpr int LDS_BYTES = NA * A2_BYTES + NB * B_BYTES;  // 163840 = the whole LDS of a CU
-  static constexpr int BROW = BN * 2;
-};
+using GeoPP2 = GeoPingPong2<2>;
 
 template <Form F, typename CT = _Float16>
 __global__ __launch_bounds__(GeoPP2::THREADS) void mfma_f16_pp2_kernel(const _Float16 *__restrict__ A,
@@ -564,26 +550,24 @@ __global__ __launch_bounds__(GeoPP2::THREADS) void mfma_f16_pp2_kernel(const _Fl
   const unsigned lds0 = (unsigned)(size_t)(__attribute__((address_space(3))) char *)smem;
   const unsigned U = K / G::BK, UD = U / 2;
   // half `h` (pieces wave+16h, wave+16h+8) of A double slab `ds` into A buffer `abuf`, and B slab `slab` into B buffer `bbuf`
-#define MM_PP2_ISSUE(V0, V1, SB, L0, L1)                                                                   \
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %4\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %3"       \
-               "\n\ts_mov_b32 m0, %5\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %2, %3\n\ts_mov_b32 m0, %0" \
-               : "=&s"(keep)                                                                               \
-               : "v"(V0), "v"(V1), "s"(SB), "s"(L0), "s"(L1)                                               \
-               : "memory")
   auto issue_a = [&](unsigned ds, unsigned abuf, int h) {
     const char *ap = a_base + (size_t)min(ds, UD - 1) * 128;
     const unsigned la0 = lds0 + abuf * G::A2_BYTES + (wave + 16 * h) * 1024, la1 = la0 + 8 * 1024;
-    const unsigned v0 = h ? voff_a[2] : voff_a[0], v1 = h ? voff_a[3] : voff_a[1];
     unsigned keep;
-    MM_PP2_ISSUE(v0, v1, ap, la0, la1);
+    asm volatile("s_mov_b32 %0, m0\n\t" MM_DMA_PIECE("%1", "%3", "%4") MM_DMA_PIECE("%2", "%3", "%5") "s_mov_b32 m0, %0"
+                 : "=&s"(keep)
+                 : "v"(h ? voff_a[2] : voff_a[0]), "v"(h ? voff_a[3] : voff_a[1]), "s"(ap), "s"(la0), "s"(la1)
+                 : "memory");
   };
   auto issue_b = [&](unsigned slab, unsigned bbuf) {
     const char *bp = b_base + (size_t)min(slab, U - 1) * G::BK * M * 2;
     const unsigned lb0 = lds0 + G::B_REGION + bbuf * G::B_BYTES + wave * 1024, lb1 = lb0 + 8 * 1024;
     unsigned keep;
-    MM_PP2_ISSUE(voff_b[0], voff_b[1], bp, lb0, lb1);
+    asm volatile("s_mov_b32 %0, m0\n\t" MM_DMA_PIECE("%1", "%3", "%4") MM_DMA_PIECE("%2", "%3", "%5") "s_mov_b32 m0, %0"
+                 : "=&s"(keep)
+                 : "v"(voff_b[0]), "v"(voff_b[1]), "s"(bp), "s"(lb0), "s"(lb1)
+                 : "memory");
   };
-#undef MM_PP2_ISSUE
 
   // ---- fragment addresses.  A: row = wm*128 + mi*32 + lo, logical chunk = 4*h + 2*ks + hi (h = slab parity),
   //      physical = logical ^ ((lo>>1)&7) = (4h | 2ks) ^ c with c = hi ^ ((lo>>1)&7)
@@ -784,26 +768,24 @@ __global__ __launch_bounds__(GeoPP2::THREADS) void mfma_f16_pp2s_kernel(const _F
   const char *b_base = (const char *)B + (size_t)col0 * 2;
   const unsigned lds0 = (unsigned)(size_t)(__attribute__((address_space(3))) char *)smem;
   const unsigned U = K / G::BK, UD = U / 2;
-#define MM_PP2_ISSUE(V0, V1, SB, L0, L1)                                                                   \
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %4\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %3"       \
-               "\n\ts_mov_b32 m0, %5\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %2, %3\n\ts_mov_b32 m0, %0" \
-               : "=&s"(keep)                                                                               \
-               : "v"(V0), "v"(V1), "s"(SB), "s"(L0), "s"(L1)                                               \
-               : "memory")
   auto issue_a = [&](unsigned ds, unsigned abuf, int h) {
     const char *ap = a_base + (size_t)min(ds, UD - 1) * 128;
     const unsigned la0 = lds0 + abuf * G::A2_BYTES + (wave + 16 * h) * 1024, la1 = la0 + 8 * 1024;
-    const unsigned v0 = h ? voff_a[2] : voff_a[0], v1 = h ? voff_a[3] : voff_a[1];
     unsigned keep;
-    MM_PP2_ISSUE(v0, v1, ap, la0, la1);
+    asm volatile("s_mov_b32 %0, m0\n\t" MM_DMA_PIECE("%1", "%3", "%4") MM_DMA_PIECE("%2", "%3", "%5") "s_mov_b32 m0, %0"
+                 : "=&s"(keep)
+                 : "v"(h ? voff_a[2] : voff_a[0]), "v"(h ? voff_a[3] : voff_a[1]), "s"(ap), "s"(la0), "s"(la1)
+                 : "memory");
   };
   auto issue_b = [&](unsigned slab, unsigned bbuf) {
     const char *bp = b_base + (size_t)min(slab, U - 1) * G::BK * M * 2;
     const unsigned lb0 = lds0 + G::B_REGION + bbuf * G::B_BYTES + wave * 1024, lb1 = lb0 + 8 * 1024;
     unsigned keep;
-    MM_PP2_ISSUE(voff_b[0], voff_b[1], bp, lb0, lb1);
+    asm volatile("s_mov_b32 %0, m0\n\t" MM_DMA_PIECE("%1", "%3", "%4") MM_DMA_PIECE("%2", "%3", "%5") "s_mov_b32 m0, %0"
+                 : "=&s"(keep)
+                 : "v"(voff_b[0]), "v"(voff_b[1]), "s"(bp), "s"(lb0), "s"(lb1)
+                 : "memory");
   };
-#undef MM_PP2_ISSUE
 
   // A: row = wm*128 + rb*16 + l15, logical chunk = 4*H + g (H = slab parity inside the double slab), physical = logical ^ (row>>1)&7
   const unsigned a_row_byte = (wm * 128 + l15) * 128;

@@ -8,6 +8,7 @@
 #include <type_traits>   // std::integral_constant in the kernels
 
 #include "mm_common.h"
+#include "mm_pingpong2.h"
 
 namespace mm {
 namespace {

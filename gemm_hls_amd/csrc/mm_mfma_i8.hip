@@ -11,6 +11,7 @@
 //
 // Kernels in this file, as in mm_mfma_f16.hip: pingpong_16x16x64 (default: K % 128 == 0, K >= 512, row-major A),
 // pingpong_32x32x32 (cross-check, i8_variant 100), pingpong_k64 (K % 64 == 0; row-major and K x N A), slab128 (K % 32 == 0).
+// The two pingpong_NxNxK kernels share their protocol and geometry with the half pair: mm_pingpong2.h.
 // Each is one row of kTable at the end of mm_mfma_i8_kernels.inc; this unit picks the row (resolve) and launches it through the
 // include's launch_kind.  Lock-step ablations: tools/lab/lab_mfma_i8.hip.
 // Organisation of slab128 as mm_mfma_f16.hip's slab64: 256 x 256 x 128(bytes) slabs, 8 wavefronts of 64 x 128, A operand
@@ -27,6 +28,7 @@
 #include <type_traits>
 
 #include "mm_common.h"
+#include "mm_pingpong2.h"
 
 namespace mm {
 namespace {

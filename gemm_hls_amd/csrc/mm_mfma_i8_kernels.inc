@@ -428,16 +428,9 @@ __global__ __launch_bounds__(GeoI8PP::THREADS) void mfma_i8_pp_kernel(const sign
   }
 }
 
-// Ping-pong with full-line A requests (see mfma_f16_pp2_kernel in mm_mfma_f16.hip): A staged in
-// double slabs [256 rows][128 B] (ring of 3 x 32 KiB, chunk ^ (row>>1)&7), B in 64-deep slabs (ring of
-// 4 x 16 KiB); all 160 KiB of LDS.  Requirements: K % 128 == 0, K >= 512.
-struct GeoI8PP2 {
-  static constexpr int BM = 256, BN = 256, BK = 64, THREADS = 512;
-  static constexpr int TM = 4, TN = 2;
-  static constexpr int A2_BYTES = BM * 128, NA = 3, B_BYTES = BK * BN, NB = 4;
-  static constexpr int B_REGION = NA * A2_BYTES, LDS_BYTES = NA * A2_BYTES + NB * B_BYTES;
-  static constexpr int BROW = BN;
-};
+// Ping-pong with full-line A requests (mm_pingpong2.h: the protocol and the geometry); B in 64-deep slabs [64 k][256 cols],
+// 256-byte k-rows.  Requirements: K % 128 == 0, K >= 512.
+using GeoI8PP2 = GeoPingPong2<1>;
 
 template <Form F, typename CT = signed char>
 __global__ __launch_bounds__(GeoI8PP2::THREADS) void mfma_i8_pp2_kernel(const signed char *__restrict__ A,

@@ -193,20 +193,30 @@ def test_batched_half_wide_contract_and_reference_contract(ta):
         assert sr.same_bits(element(c, e, n * m, n, m), want), e
 
 
-@pytest.mark.parametrize("shape,ta,batch,family", [((256, 256, 256), False, 6, "mfma_f16_256x256_pingpong_16x16x32"),
-                                                  ((130, 160, 264), False, 3, "mfma_f16_256x256_pingpong_k32"),
-                                                  ((128, 48, 256), False, 3, "mfma_f16_64x256x64_slab64"),
-                                                  ((264, 160, 256), True, 3, "mfma_f16_256x256_pingpong_k32_KxN"),
-                                                  ((264, 48, 256), True, 3, "mfma_f16_256x256x64_slab64_KxN")],
-                         ids=["pp16", "ppk32", "slab64_64", "ppk32_kxn", "slab64_kxn"])
-def test_batched_half_matrix_core_kernels_keep_the_wide_contract(shape, ta, batch, family):
+# pp32: the Batched form of the 32x32x16 kernel (f16_variant 100).  300 x 320 x 264 is two tiles each way, both ragged, and ten
+# 32-deep slabs: two trips of the 4-slab loop and its even-pair tail.
+@pytest.mark.parametrize("shape,ta,batch,family,pin", [((256, 256, 256), False, 6, "mfma_f16_256x256_pingpong_16x16x32", None),
+                                                      ((130, 160, 264), False, 3, "mfma_f16_256x256_pingpong_k32", None),
+                                                      ((128, 48, 256), False, 3, "mfma_f16_64x256x64_slab64", None),
+                                                      ((264, 160, 256), True, 3, "mfma_f16_256x256_pingpong_k32_KxN", None),
+                                                      ((264, 48, 256), True, 3, "mfma_f16_256x256x64_slab64_KxN", None),
+                                                      ((300, 320, 264), False, 2, "mfma_f16_256x256_pingpong_32x32x16", ("f16_variant", 100))],
+                         ids=["pp16", "ppk32", "slab64_64", "ppk32_kxn", "slab64_kxn", "pp32"])
+def test_batched_half_matrix_core_kernels_keep_the_wide_contract(shape, ta, batch, family, pin):
     n, k, m = shape
     rng = np.random.default_rng(n + 3 * k + m)
     a = rng.uniform(0.5, 2.0, size=(batch, k, n) if ta else (batch, n, k)).astype(np.float16)
     b = rng.uniform(0.5, 2.0, size=(batch, k, m)).astype(np.float16)
     cfg = g.make_config("half", transposed_a=ta)
-    assert g.kernel_name_batched(cfg, n, k, m, batch) == family
-    c = batched_launch(cfg, a.ravel(), b.ravel(), n, k, m, batch, n * k, k * m, n * m)
+    old = g.get_tuning(pin[0]) if pin else None
+    try:
+        if pin:
+            g.set_tuning(*pin)
+        assert g.kernel_name_batched(cfg, n, k, m, batch) == family
+        c = batched_launch(cfg, a.ravel(), b.ravel(), n, k, m, batch, n * k, k * m, n * m)
+    finally:
+        if pin:
+            g.set_tuning(pin[0], old)
     for e in range(batch):
         wide = _oracle.naive("half", "Multiply", "Add", a[e], b[e], transposed_a=ta, wide_half=True)
         got = element(c, e, n * m, n, m)
@@ -234,11 +244,24 @@ def test_batched_broadcast_operand_equals_per_element_launches(dtype, mp, rd, wh
             assert sr.same_bits(element(c, e, n * m, n, m), single), e
 
 
-@pytest.mark.parametrize("dtype,mp,rd,path", [("float", "Multiply", "Add", g.PATH_AUTO), ("float", "Add", "Min", g.PATH_AUTO),
-                                              ("uint8_t", "Max", "Min", g.PATH_AUTO), ("double", "Multiply", "Max", g.PATH_ORDERED)],
-                         ids=lambda x: str(x))
-def test_batched_padded_strides_leave_the_gaps_untouched(dtype, mp, rd, path):
-    n, k, m, batch = 40, 64, 48, 4
+# (dtype, map, reduce, path, (n, k, m), batch, (knob, value) or None, the kernel the batch must run on or None).  The last case:
+# the Batched form of the int8 32x32x32 kernel (i8_variant 100) on two ragged tiles each way and ten 64-deep slabs -- two trips
+# of its 4-slab loop and the even-pair tail.
+PADDED = [("float", "Multiply", "Add", g.PATH_AUTO, (40, 64, 48), 4, None, None),
+          ("float", "Add", "Min", g.PATH_AUTO, (40, 64, 48), 4, None, None),
+          ("uint8_t", "Max", "Min", g.PATH_AUTO, (40, 64, 48), 4, None, None),
+          ("double", "Multiply", "Max", g.PATH_ORDERED, (40, 64, 48), 4, None, None),
+          ("int8_t", "Multiply", "Add", g.PATH_AUTO, (300, 640, 272), 2, ("i8_variant", 100), "mfma_i8_256x256_pingpong_32x32x32")]
+
+
+@pytest.mark.parametrize("dtype,mp,rd,path,shape,batch,pin,family", PADDED,
+                         ids=["-".join(str(x) for x in c[:4]) + ("-" + c[7] if c[7] else "") for c in PADDED])
+def test_batched_padded_strides_leave_the_gaps_untouched(dtype, mp, rd, path, shape, batch, pin, family, request):
+    n, k, m = shape
+    if pin:
+        old = g.get_tuning(pin[0])
+        request.addfinalizer(lambda: g.set_tuning(pin[0], old))
+        g.set_tuning(*pin)
     es = np.dtype(_oracle.NP_DTYPES[dtype]).itemsize
     pad = 64 // es   # keeps every element 16-byte aligned
     sa, sb, sc = n * k + pad, k * m + 2 * pad, n * m + 3 * pad
@@ -247,9 +270,13 @@ def test_batched_padded_strides_leave_the_gaps_untouched(dtype, mp, rd, path):
     b = random_operands(dtype, ((batch - 1) * sb + k * m,), rng)
     sentinel = np.full((batch - 1) * sc + n * m, 77, dtype=a.dtype)
     cfg = g.make_config(dtype, mp, rd, path)
+    if family:
+        assert g.kernel_name_batched(cfg, n, k, m, batch) == family
     c = batched_launch(cfg, a, b, n, k, m, batch, sa, sb, sc, c_init=sentinel)
     for e in range(batch):
         ae, be, ce = element(a, e, sa, n, k), element(b, e, sb, k, m), element(c, e, sc, n, m)
+        if family:   # the 8-bit product: the low 8 bits of the exact sums
+            assert np.array_equal(ce, (ae.astype(np.int32) @ be.astype(np.int32)).astype(np.int8)), e
         if (dtype, mp, rd, path) == ("float", "Multiply", "Add", g.PATH_AUTO):   # the bound, not the single launch's order
             exact = ae.astype(np.float64) @ be.astype(np.float64)
             assert normwise(ce, exact, np.abs(ae.astype(np.float64)) @ np.abs(be.astype(np.float64))) < NORTH_STAR_F32, e

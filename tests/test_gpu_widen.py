@@ -153,12 +153,23 @@ def test_widen_every_kernel_plain_and_seeded(dtype, pin, transposed, shape, kern
             assert _bits_equal(seeded[e], ref(a[e], b[e], seed[e])), f"batched seeded {e}"
 
 
+# The last two shapes run pinned to the 32x32 instruction forms (PINNED): two ragged tiles each way and ten slabs -- two trips of the
+# full-line ping-pong kernels' 4-slab loop and its even-pair tail -- for their Batched and Seeded forms with a wide C.
+PINNED = {("half", (300, 320, 264)): (("f16_variant", 100), "mfma_f16_256x256_pingpong_32x32x16_wide"),
+          ("int8_t", (300, 640, 272)): (("i8_variant", 100), "mfma_i8_256x256_pingpong_32x32x32_wide")}
+
+
 @pytest.mark.parametrize("dtype,shape", [("half", (130, 256, 264)), ("half", (70, 48, 72)), ("half", (33, 40, 20)),
-                                         ("int8_t", (130, 512, 272)), ("int8_t", (70, 96, 80)), ("int8_t", (33, 40, 20))])
+                                         ("int8_t", (130, 512, 272)), ("int8_t", (70, 96, 80)), ("int8_t", (33, 40, 20)),
+                                         ("half", (300, 320, 264)), ("int8_t", (300, 640, 272))])
 def test_widen_batches_broadcast_chunks_and_batch_position(dtype, shape, knob):
     torch, dev = _torch()
     n, k, m = shape
     batch = 5
+    if (dtype, shape) in PINNED:
+        pin, kernel = PINNED[(dtype, shape)]
+        knob(*pin)
+        assert g.kernel_name_widen(g.make_config(dtype), n, k, m) == kernel
     rng = np.random.default_rng(n + k)
     kind = "full" if dtype == "int8_t" else "wide"
     a, b = _operands(dtype, (batch, n, k), kind, rng), _operands(dtype, (batch, k, m), kind, rng)
@@ -184,6 +195,14 @@ def test_widen_batches_broadcast_chunks_and_batch_position(dtype, shape, knob):
         seeded = g.addmm_wide_(c.clone(), at, bt, dtype, path)
         knob("batch_chunk", -1)
         assert torch.equal(g.addmm_wide_(c.clone(), at, bt, dtype, path), seeded), "accumulating in chunks of 2"
+        sh = seeded.cpu().numpy()
+        for e in range(batch):   # the product accumulated into itself
+            if dtype == "int8_t":
+                assert np.array_equal(sh[e], _int_ref(a[e], b[e], ch[e])), (path, e)
+            elif path == g.PATH_ORDERED:
+                assert _bits_equal(sh[e], _f32_loop(a[e], b[e], ch[e])), e
+            else:
+                _check_bound(f"seeded batch element {e}", sh[e], a[e], b[e], ch[e])
         # broadcast operands: a 2-D B, an expanded A; the same bits as the materialised batch
         assert torch.equal(g.matmul_wide(at, bt[0], dtype, path), g.matmul_wide(at, bt[0:1].expand(batch, k, m).contiguous(), dtype, path))
         ab = g.matmul_wide(at[1:2].expand(batch, n, k), bt, dtype, path)

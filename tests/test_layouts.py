@@ -4,7 +4,8 @@ enumerates the lanes of each hardware service group and checks that
     matrix element the MFMA operand needs (the permutation pair is an involution), and
   * every ds_read_b128 service group touches 16 distinct 16-byte slots of the 256-byte bank row
     (MI355X_MICROARCH.md, LDS table: b128 is served in 4 groups of 16 lanes, bank = (addr/4) % 64).
-The formulas are the ones in gemm_hls_amd/csrc/mm_mfma_{f32,f64,f16}.hip."""
+The formulas are the ones in gemm_hls_amd/csrc/mm_mfma_{f32,f64}.hip and mm_mfma_{f16,i8}_kernels.inc; the A double slab of the
+full-line ping-pong kernels is described once, in mm_pingpong2.h."""
 import itertools
 
 import pytest
@@ -214,7 +215,8 @@ def test_pingpong_a_image_64_byte_rows_roundtrip_and_banks():
 
 
 def test_pingpong_a_image_full_line_rows_roundtrip_and_banks():
-    """mfma_f16_pp2_kernel / mfma_i8_pp2_kernel: A double slab [256 rows][128 B], DMA piece = 8 rows,
+    """mfma_f16_pp2_kernel / mfma_i8_pp2_kernel (image: mm_pingpong2.h; formulas: each kernel's voff_a and a_off in
+    mm_mfma_{f16,i8}_kernels.inc): A double slab [256 rows][128 B], DMA piece = 8 rows,
     source chunk = pc ^ ((row>>1)&7); fragment chunk (4*h + 2*ks + hi) for slab parity h."""
     lds = {}
     for piece in range(32):
@@ -314,7 +316,7 @@ def test_valu_tile_dma_a_pairs_roundtrip_and_banks():
 
 # ---------------------------------------------------------------- 16 x 16 matrix instructions (round 3) ------------
 def test_pingpong_16x16_a_operand_on_full_line_rows_roundtrip_and_banks():
-    """mfma_f16_pp2s_kernel / mfma_i8_pp2s_kernel: the A double slab of the full-line kernels, unchanged
+    """mfma_f16_pp2s_kernel / mfma_i8_pp2s_kernel: the A double slab of the full-line kernels (mm_pingpong2.h), unchanged
     ([256 rows][128 B], source chunk = pc ^ ((row>>1)&7)), read for the 16x16x32 (16x16x64) operand: lane l takes row
     l&15 of a 16-row block and the 16-byte chunk 4*H + (l>>4) (H = slab parity inside the double slab)."""
     lds = {}

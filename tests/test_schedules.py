@@ -1,6 +1,7 @@
 """CPU model of the hand-over protocol of the DMA-ring kernels (no GPU needed).
 
-The ping-pong kernels (gemm_hls_amd/csrc/mm_mfma_f16.hip, mm_mfma_i8.hip, the fp32 variant) and the
+The ping-pong kernels (gemm_hls_amd/csrc/mm_mfma_f16_kernels.inc, mm_mfma_i8_kernels.inc, the fp32 variant; the protocol of
+the four full-line ones is described in mm_pingpong2.h) and the
 DMA-staged VALU kernel (mm_valu_tile.inc) order LDS traffic with nothing but counted `s_waitcnt
 vmcnt(N)` and `s_barrier`.  A wrong count does not fail a test reliably -- the DMA usually lands in
 time anyway -- so the protocol is checked here by construction: each wave's program is replayed as
@@ -96,9 +97,10 @@ def test_pingpong_ring_of_four(slabs, lockstep):
 
 @pytest.mark.parametrize("slabs", [8, 10, 18, 32])
 def test_pingpong_full_line_a_requests(slabs):
-    """mfma_f16_pp2_kernel / mfma_i8_pp2_kernel: A in double slabs (ring of 3, two halves of 2 pieces
-    per wave), B in slabs (ring of 4, 2 pieces per wave); prologue in the order of four virtual
-    segments; vmcnt(8) at the end of every load segment."""
+    """mfma_f16_pp2_kernel / mfma_i8_pp2_kernel and their 16x16 forms mfma_f16_pp2s_kernel / mfma_i8_pp2s_kernel
+    (mm_pingpong2.h; the four bodies write the same protocol out, which this replay takes on trust): A in double slabs
+    (ring of 3, two halves of 2 pieces per wave), B in slabs (ring of 4, 2 pieces per wave); prologue in the order of
+    four virtual segments; vmcnt(8) at the end of every load segment."""
     A = lambda d: ("A", d)
     B = lambda s: ("B", s)
     waves = []
