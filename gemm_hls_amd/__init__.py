@@ -34,11 +34,9 @@ EXPORTS = ["mm_init", "mm_alloc", "mm_free", "mm_copy_to_device", "mm_copy_to_ho
            "mm_gemm_argreduce_nt_launch", "mm_kernel_name_argreduce_nt", "mm_gemm_logsumexp_nt_enqueue",
            "mm_gemm_logsumexp_nt_launch", "mm_kernel_name_logsumexp_nt", "mm_bits_gemm_enqueue", "mm_bits_gemm_launch",
            "mm_kernel_name_bits_gemm", "mm_bits_closure_enqueue", "mm_bits_closure_launch", "mm_kernel_name_bits_closure",
-           "mm_bits_pack_enqueue", "mm_bits_pack_launch", "mm_bits_unpack_enqueue", "mm_bits_unpack_launch"]
-# what include/mm_bits_count.h declares (included by mm_gemm.h; asserted by tests/test_bits_count_capi.py).  A list of its own:
-# EXPORTS is pinned, symbol for symbol, against mm_gemm.h's own declarations and a literal prototype table
-BITS_COUNT_EXPORTS = ["mm_bits_count_enqueue", "mm_bits_count_launch", "mm_kernel_name_bits_count", "mm_bits_transpose_enqueue",
-                      "mm_bits_transpose_launch"]
+           "mm_bits_pack_enqueue", "mm_bits_pack_launch", "mm_bits_unpack_enqueue", "mm_bits_unpack_launch",
+           "mm_bits_count_enqueue", "mm_bits_count_launch", "mm_kernel_name_bits_count", "mm_bits_transpose_enqueue",
+           "mm_bits_transpose_launch"]
 
 
 class MMError(RuntimeError):
@@ -589,6 +587,20 @@ def pack_bits(x):
     return out
 
 
+def _row_rule(x, name, rows, row, unit):
+    """(batch or None, batch stride, row stride) of a 2-D or 3-D tensor of `rows` rows of `row` units ("words", "elements")
+    each: unit stride along the row; the row stride is the tensor's own and at least `row`; the batch stride of one matrix
+    is 0."""
+    if x.shape[-1] > 1 and x.stride(-1) != 1:
+        raise MMError(f"the {unit} of a row of {name} must be contiguous (strides {x.stride()})")
+    ld = x.stride(-2) if rows > 1 else max(x.stride(-2), row)
+    if ld < row:
+        raise MMError(f"{name} has row stride {ld}, below its {row} {unit}")
+    if x.dim() == 2:
+        return None, 0, ld
+    return x.shape[0], (0 if x.shape[0] == 1 else x.stride(0)), ld
+
+
 def _packed_operand(x, name, rows, cols):
     """(batch or None, batch stride, row stride), in words, of a packed operand: torch.int32, (rows, W) or (B, rows, W) with
     W >= ceil(cols / 32) and unit stride along the words; the row stride is the tensor's own, so a slice of whole words of
@@ -599,16 +611,38 @@ def _packed_operand(x, name, rows, cols):
         raise MMError(f"{name} must be a packed torch.int32 tensor (got {x.dtype})")
     if x.dim() not in (2, 3) or x.shape[-2] != rows or x.shape[-1] < words:
         raise MMError(f"{name} has shape {tuple(x.shape)}, expected ({rows}, W) or (B, {rows}, W) with W >= {words}")
-    if x.shape[-1] > 1 and x.stride(-1) != 1:
-        raise MMError(f"the words of a row of {name} must be contiguous (strides {x.stride()})")
-    ld = x.stride(-2) if rows > 1 else max(x.stride(-2), words)
-    if ld < words:
-        raise MMError(f"{name} has row stride {ld}, below its {words} words")
-    if x.dim() == 2:
-        return None, 0, ld
-    if x.stride(0) < 0:
+    batch, stride, ld = _row_rule(x, name, rows, words, "words")
+    if x.dim() == 3 and x.stride(0) < 0:
         raise MMError(f"{name} has a negative batch stride")
-    return x.shape[0], (0 if x.shape[0] == 1 else x.stride(0)), ld
+    return batch, stride, ld
+
+
+def _count_output(c, name, n, m, batch, two_d, device):
+    """(batch stride, row stride), in elements, of the int32 result `c`: (n, m), or (batch, n, m) unless two_d, with unit
+    stride along a row and its own row and batch strides."""
+    import torch
+    if c.dtype != torch.int32:
+        raise MMError(f"{name} must be a torch.int32 tensor (got {c.dtype})")
+    if not c.is_cuda or c.device != device:
+        raise MMError(f"{name} must live on {device} (got {c.device})")
+    want = (n, m) if two_d else (batch, n, m)
+    if tuple(c.shape) != want:
+        raise MMError(f"{name} has shape {tuple(c.shape)}, expected {want}")
+    return _row_rule(c, name, n, m, "elements")[1:]
+
+
+def _flat_batch(what, p, cols):
+    """(p, leading dimensions, rows, batch or None, batch stride, row stride) of a packed (..., rows, W) tensor with its
+    leading dimensions as one batch: 2-D and 3-D as they lie, more dimensions through a dense copy."""
+    if not p.is_cuda:
+        raise MMError(f"{what} needs a device tensor: there is no CPU path")
+    if p.dim() < 2:
+        raise MMError(f"{what} takes a (..., rows, W) tensor; got shape {tuple(p.shape)}")
+    lead = tuple(p.shape[:-2])
+    if p.dim() > 3:
+        p = p.contiguous().reshape(-1, *p.shape[-2:])
+    rows = p.shape[-2]
+    return (p, lead, rows) + _packed_operand(p, "p", rows, cols)
 
 
 def unpack_bits(p, cols, dtype=None):
@@ -618,35 +652,73 @@ def unpack_bits(p, cols, dtype=None):
     dtype = torch.bool if dtype is None else dtype
     if dtype not in (torch.bool, torch.uint8):
         raise MMError(f"unpack_bits writes torch.bool or torch.uint8 (got {dtype})")
-    if not p.is_cuda:
-        raise MMError("unpack_bits needs a device tensor: there is no CPU path")
-    if p.dim() < 2:
-        raise MMError(f"unpack_bits takes a (..., rows, W) tensor; got shape {tuple(p.shape)}")
-    shape = tuple(p.shape[:-1]) + (cols,)
-    if p.dim() > 3:
-        p = p.contiguous().reshape(-1, *p.shape[-2:])
-    rows = p.shape[-2]
-    batch, stride, ld = _packed_operand(p, "p", rows, cols)
-    out = torch.empty(shape, dtype=dtype, device=p.device)
+    p, lead, rows, batch, stride, ld = _flat_batch("unpack_bits", p, cols)
+    out = torch.empty(lead + (rows, cols), dtype=dtype, device=p.device)
     _enqueue(p.device, lib().mm_bits_unpack_enqueue, p.data_ptr(), out.data_ptr(), rows, cols, ld, cols, batch or 1, stride,
              rows * cols)
     return out
 
 
-def _bits_shapes(what, a, b, k, m):
+def _packed_pair(what, a, b, b_name, b_rows, b_cols, k):
+    """(n, b's rows, batch, stride_a, stride_b, lda, ldb) of a packed product's operands: a is (N, k) packed along k, b is
+    (b_rows, b_cols) packed along b_cols -- its own row count when b_rows is None -- each 2-D, 3-D, or expanded with batch
+    stride 0."""
     if not (a.is_cuda and b.is_cuda):
         raise MMError(f"{what} needs device tensors: there is no CPU path")
     if a.device != b.device:
         raise MMError(f"operands live on different devices: {a.device} and {b.device}")
     if a.dim() not in (2, 3) or b.dim() not in (2, 3):
         raise MMError(f"{what} takes 2-D or 3-D operands")
-    n = a.shape[-2]
+    n, b_rows = a.shape[-2], (b.shape[-2] if b_rows is None else b_rows)
     ba, sa, lda = _packed_operand(a, "a", n, k)
-    bb, sb, ldb = _packed_operand(b, "b", k, m)
+    bb, sb, ldb = _packed_operand(b, b_name, b_rows, b_cols)
     batches = {x for x in (ba, bb) if x is not None and x != 1}
     if len(batches) > 1:
         raise MMError(f"batch sizes differ: {ba} and {bb}")
-    return n, (batches.pop() if batches else 1), sa, sb, lda, ldb
+    return n, b_rows, (batches.pop() if batches else 1), sa, sb, lda, ldb
+
+
+def _packed_product(what, symbol, a, b, k, m=None, *, nt=False, counts=False, op=None, c=None, out=None):
+    """The skeleton of every packed product wrapper, as _product is of the dense ones: check the operands, derive the shapes,
+    check or allocate C, enqueue lib().<symbol>.
+
+    nt: b is bt, (M, k) packed along k, and m is its row count; otherwise b is (k, m) packed along m.  counts: C holds int32
+    elements, (N, M) with ldc and stride_c in elements; otherwise packed words, (N, W >= ceil(m / 32)).  op: the counting
+    op's code, which leads the C call's arguments.  c: the in-place form, which accumulates and takes its batch from c, over
+    which 2-D operands broadcast; otherwise the result is out or new, 2-D when both operands are.  Returns C."""
+    import torch
+    n, b_rows, batch, sa, sb, lda, ldb = _packed_pair(what, a, b, *(("bt", None, k) if nt else ("b", k, m)), k)
+    m = b_rows if nt else m
+    in_place, two_d = c is not None, a.dim() == 2 and b.dim() == 2
+    if in_place and counts:
+        two_d = c.dim() == 2
+        if two_d and batch != 1:
+            raise MMError(f"c has shape {tuple(c.shape)}, expected ({batch}, {n}, {m})")
+        if not two_d and c.dim() == 3 and batch == 1:
+            batch = c.shape[0]
+        sc, ldc = _count_output(c, "c", n, m, batch, two_d, a.device)
+    elif in_place:
+        if not c.is_cuda or c.device != a.device:
+            raise MMError(f"c must live on {a.device} (got {c.device})")
+        bc, sc, ldc = _packed_operand(c, "c", n, m)
+        if batch not in (1, bc or 1):
+            raise MMError(f"c has shape {tuple(c.shape)}, expected ({batch}, {n}, W)")
+        batch = bc or 1
+    elif out is None:
+        row = m if counts else bits_words(m)
+        c = torch.empty((n, row) if two_d else (batch, n, row), dtype=torch.int32, device=a.device)
+        sc, ldc = ((n * m if batch > 1 else 0), m) if counts else _packed_operand(c, "out", n, m)[1:]
+    elif counts:
+        c, (sc, ldc) = out, _count_output(out, "out", n, m, batch, two_d, a.device)
+    else:
+        if out.device != a.device or out.dim() != (2 if two_d else 3) or (not two_d and out.shape[0] != batch):
+            raise MMError(f"out has shape {tuple(out.shape)} on {out.device}; expected {'(N, W)' if two_d else f'({batch}, N, W)'} on {a.device}")
+        c, (bc, sc, ldc) = out, _packed_operand(out, "out", n, m)
+    if (in_place or out is not None) and batch > 1 and sc <= 0:
+        raise MMError(f"{'c' if in_place else 'out'} has batch stride {sc}: the {batch} outputs would overlap")
+    _enqueue(a.device, getattr(lib(), symbol), *(() if op is None else (op,)), a.data_ptr(), b.data_ptr(), c.data_ptr(), n, k, m,
+             lda, ldb, ldc, batch, sa, sb, sc, int(in_place))
+    return c
 
 
 def bits_matmul(a, b, k, m, out=None):
@@ -656,37 +728,14 @@ def bits_matmul(a, b, k, m, out=None):
     ceil(m / 32), and row strides are taken from the tensors, so p[:, 1:3] of a wider packed matrix is a valid a without a
     copy.  Returns (N, ceil(m / 32)) when both operands are 2-D, else (B, N, ceil(m / 32)); out: a packed tensor of that
     shape (more words per row allowed; they are left alone).  Padding bits of the result are 0.  Asynchronous."""
-    import torch
-    n, batch, sa, sb, lda, ldb = _bits_shapes("bits_matmul", a, b, k, m)
-    two_d = a.dim() == 2 and b.dim() == 2
-    if out is None:
-        out = torch.empty((n, bits_words(m)) if two_d else (batch, n, bits_words(m)), dtype=torch.int32, device=a.device)
-    elif out.device != a.device or out.dim() != (2 if two_d else 3) or (not two_d and out.shape[0] != batch):
-        raise MMError(f"out has shape {tuple(out.shape)} on {out.device}; expected {'(N, W)' if two_d else f'({batch}, N, W)'} on {a.device}")
-    bc, sc, ldc = _packed_operand(out, "out", n, m)
-    if batch > 1 and sc == 0:
-        raise MMError(f"out has batch stride 0: the {batch} outputs would overlap")
-    _enqueue(a.device, lib().mm_bits_gemm_enqueue, a.data_ptr(), b.data_ptr(), out.data_ptr(), n, k, m, lda, ldb, ldc, batch,
-             sa, sb, sc, 0)
-    return out
+    return _packed_product("bits_matmul", "mm_bits_gemm_enqueue", a, b, k, m, out=out)
 
 
 def bits_addmm_(c, a, b, k, m):
     """In place C <- C | A B on torch's current stream (mm_bits_gemm_enqueue, accumulate); a and b as for bits_matmul, c:
     (N, Wm) or (B, N, Wm) packed torch.int32 with its own row stride, not overlapping a or b.  Two calls on the halves of K
     equal one call on all of it.  Returns c.  Asynchronous."""
-    n, batch, sa, sb, lda, ldb = _bits_shapes("bits_addmm_", a, b, k, m)
-    if not c.is_cuda or c.device != a.device:
-        raise MMError(f"c must live on {a.device} (got {c.device})")
-    bc, sc, ldc = _packed_operand(c, "c", n, m)
-    if batch not in (1, bc or 1):
-        raise MMError(f"c has shape {tuple(c.shape)}, expected ({batch}, {n}, W)")
-    batch = bc or 1
-    if batch > 1 and sc == 0:
-        raise MMError(f"c has batch stride 0: the {batch} outputs would overlap")
-    _enqueue(a.device, lib().mm_bits_gemm_enqueue, a.data_ptr(), b.data_ptr(), c.data_ptr(), n, k, m, lda, ldb, ldc, batch,
-             sa, sb, sc, 1)
-    return c
+    return _packed_product("bits_addmm_", "mm_bits_gemm_enqueue", a, b, k, m, c=c)
 
 
 def bits_closure_(d, n=None):
@@ -710,51 +759,17 @@ def bits_closure_(d, n=None):
 BITS_COUNT_OPS = {"And": 0, "Xor": 1}
 
 
+def _count_op(what, op):
+    if op not in BITS_COUNT_OPS:
+        raise MMError(f"{what}: op must be one of {sorted(BITS_COUNT_OPS)} (got {op!r})")
+    return BITS_COUNT_OPS[op]
+
+
 def kernel_name_bits_count(n, k, m, lda=None, ldbt=None, ldc=None, batch=1):
     """Name of the kernel bits_matmul_count / bits_addmm_count_ run; lda and ldbt (words) default to ceil(k / 32), ldc
     (elements) to m."""
     lda, ldbt = (bits_words(k) if ld is None else ld for ld in (lda, ldbt))
     return lib().mm_kernel_name_bits_count(n, k, m, lda, ldbt, m if ldc is None else ldc, batch).decode()
-
-
-def _bits_count_shapes(what, a, bt, k, op):
-    if op not in BITS_COUNT_OPS:
-        raise MMError(f"{what}: op must be one of {sorted(BITS_COUNT_OPS)} (got {op!r})")
-    if not (a.is_cuda and bt.is_cuda):
-        raise MMError(f"{what} needs device tensors: there is no CPU path")
-    if a.device != bt.device:
-        raise MMError(f"operands live on different devices: {a.device} and {bt.device}")
-    if a.dim() not in (2, 3) or bt.dim() not in (2, 3):
-        raise MMError(f"{what} takes 2-D or 3-D operands")
-    n, m = a.shape[-2], bt.shape[-2]
-    ba, sa, lda = _packed_operand(a, "a", n, k)
-    bb, sb, ldbt = _packed_operand(bt, "bt", m, k)
-    batches = {x for x in (ba, bb) if x is not None and x != 1}
-    if len(batches) > 1:
-        raise MMError(f"batch sizes differ: {ba} and {bb}")
-    return n, m, (batches.pop() if batches else 1), sa, sb, lda, ldbt
-
-
-def _count_output(c, name, n, m, batch, two_d, device):
-    """(batch stride, row stride), in elements, of the int32 result `c`: (n, m), or (batch, n, m) unless two_d, with unit
-    stride along a row and its own row and batch strides."""
-    import torch
-    if c.dtype != torch.int32:
-        raise MMError(f"{name} must be a torch.int32 tensor (got {c.dtype})")
-    if not c.is_cuda or c.device != device:
-        raise MMError(f"{name} must live on {device} (got {c.device})")
-    want = (n, m) if two_d else (batch, n, m)
-    if tuple(c.shape) != want:
-        raise MMError(f"{name} has shape {tuple(c.shape)}, expected {want}")
-    if m > 1 and c.stride(-1) != 1:
-        raise MMError(f"the elements of a row of {name} must be contiguous (strides {c.stride()})")
-    ldc = c.stride(-2) if n > 1 else max(c.stride(-2), m)
-    if ldc < m:
-        raise MMError(f"{name} has row stride {ldc}, below its {m} elements")
-    sc = 0 if c.dim() == 2 or batch == 1 else c.stride(0)
-    if batch > 1 and sc <= 0:
-        raise MMError(f"{name} has batch stride {sc}: the {batch} outputs would overlap")
-    return sc, ldc
 
 
 def bits_matmul_count(a, bt, k, op="And", out=None):
@@ -764,33 +779,16 @@ def bits_matmul_count(a, bt, k, op="And", out=None):
     tensors, so a column slice of whole words is an operand without a copy; padding bits are ignored.  Returns torch.int32
     (N, M) when both operands are 2-D, else (B, N, M); out: an int32 tensor of that shape with its own row stride.
     Asynchronous."""
-    import torch
-    n, m, batch, sa, sb, lda, ldbt = _bits_count_shapes("bits_matmul_count", a, bt, k, op)
-    two_d = a.dim() == 2 and bt.dim() == 2
-    if out is None:
-        out = torch.empty((n, m) if two_d else (batch, n, m), dtype=torch.int32, device=a.device)
-        sc, ldc = (n * m if batch > 1 else 0), m
-    else:
-        sc, ldc = _count_output(out, "out", n, m, batch, two_d, a.device)
-    _enqueue(a.device, lib().mm_bits_count_enqueue, BITS_COUNT_OPS[op], a.data_ptr(), bt.data_ptr(), out.data_ptr(), n, k, m,
-             lda, ldbt, ldc, batch, sa, sb, sc, 0)
-    return out
+    return _packed_product("bits_matmul_count", "mm_bits_count_enqueue", a, bt, k, nt=True, counts=True,
+                           op=_count_op("bits_matmul_count", op), out=out)
 
 
 def bits_addmm_count_(c, a, bt, k, op="And"):
     """In place C += counts on torch's current stream (mm_bits_count_enqueue, accumulate), mod 2^32; a, bt and op as for
     bits_matmul_count, c: torch.int32 (N, M) or (B, N, M) with its own row stride, not overlapping a or bt.  Two calls on
     the halves of K equal one call on all of it.  Returns c.  Asynchronous."""
-    n, m, batch, sa, sb, lda, ldbt = _bits_count_shapes("bits_addmm_count_", a, bt, k, op)
-    two_d = c.dim() == 2
-    if two_d and batch != 1:
-        raise MMError(f"c has shape {tuple(c.shape)}, expected ({batch}, {n}, {m})")
-    if not two_d and c.dim() == 3 and batch == 1:
-        batch = c.shape[0]
-    sc, ldc = _count_output(c, "c", n, m, batch, two_d, a.device)
-    _enqueue(a.device, lib().mm_bits_count_enqueue, BITS_COUNT_OPS[op], a.data_ptr(), bt.data_ptr(), c.data_ptr(), n, k, m,
-             lda, ldbt, ldc, batch, sa, sb, sc, 1)
-    return c
+    return _packed_product("bits_addmm_count_", "mm_bits_count_enqueue", a, bt, k, nt=True, counts=True,
+                           op=_count_op("bits_addmm_count_", op), c=c)
 
 
 def transpose_bits(p, cols, out=None):
@@ -799,15 +797,7 @@ def transpose_bits(p, cols, out=None):
     bits_matmul as the M x K operand of bits_matmul_count.  Padding bits of p are ignored, those of the result are 0.  out: a
     packed tensor of the result's shape (more words per row allowed; they are left alone)."""
     import torch
-    if not p.is_cuda:
-        raise MMError("transpose_bits needs a device tensor: there is no CPU path")
-    if p.dim() < 2:
-        raise MMError(f"transpose_bits takes a (..., rows, W) tensor; got shape {tuple(p.shape)}")
-    lead = tuple(p.shape[:-2])
-    if p.dim() > 3:
-        p = p.contiguous().reshape(-1, *p.shape[-2:])
-    rows = p.shape[-2]
-    batch, stride, ld = _packed_operand(p, "p", rows, cols)
+    p, lead, rows, batch, stride, ld = _flat_batch("transpose_bits", p, cols)
     if out is None:
         out = torch.empty(lead + (cols, bits_words(rows)), dtype=torch.int32, device=p.device)
     elif out.device != p.device or tuple(out.shape[:-2]) != lead:

@@ -655,134 +655,96 @@ size_t bits_span(unsigned rows, size_t row, size_t ld, unsigned batch, size_t st
   return rows && row && batch ? (size_t)(batch - 1) * stride + (size_t)(rows - 1) * ld + row : 0;
 }
 
-// The kernel by shape, ld and knob alone (mm_kernel_name_bits_gemm); alignment may still demote BITS_TILE at launch.
-BitsKernel bits_kernel_for(unsigned m, size_t ldb, size_t ldc) {
-  const int v = mm::tuning(mm::TUNE_BITS_VARIANT);
+// A kernel knob of the packed products: -1 the product's own rule (by_shape), 0 the plain kernel always, 1 the tile kernel
+// wherever its ld rule holds (serves); alignment may still demote BITS_TILE at launch.
+BitsKernel bits_kernel_by_knob(mm::Tunable knob, bool serves, bool by_shape) {
+  const int v = mm::tuning(knob);
   if (v < -1 || v > 1) return BITS_INVALID;
-  if (v == 0 || !mm::bits_tile_serves(ldb, ldc)) return BITS_PLAIN;
-  return v == 1 || m > 2048 ? BITS_TILE : BITS_PLAIN;   // below 65 words the tile's second word per lane would be idle
+  if (v == 0 || !serves) return BITS_PLAIN;
+  return v == 1 || by_shape ? BITS_TILE : BITS_PLAIN;
 }
 
-// The launch-time half of the rule: b in 16-byte and c in 8-byte accesses, for every element of the batch.
-BitsKernel bits_demote(const mm::BitsProblem &p, BitsKernel ker) {
+// The kernel by shape, ld and knob alone (mm_kernel_name_bits_gemm).
+BitsKernel bits_kernel_for(unsigned m, size_t ldb, size_t ldc) {
+  // below 65 words the tile's second word per lane would be idle
+  return bits_kernel_by_knob(mm::TUNE_BITS_VARIANT, mm::bits_tile_serves(ldb, ldc), m > 2048);
+}
+
+constexpr unsigned long long kBitsCountTileMin = 256;   // 128 x 128 tiles of C from which bits_count_tile serves: one per CU
+
+// The kernel by shape, ld and knob alone (mm_kernel_name_bits_count).
+BitsKernel bits_count_kernel_for(unsigned n, unsigned m, size_t lda, size_t ldbt, size_t ldc) {
+  const unsigned long long tiles = (unsigned long long)(((size_t)n + 127) / 128) * (((size_t)m + 127) / 128);
+  return bits_kernel_by_knob(mm::TUNE_BITS_COUNT_VARIANT, mm::bits_count_tile_serves(lda, ldbt, ldc), tiles >= kBitsCountTileMin);
+}
+
+// What is a packed product's own in its argument checks; everything else the two products share (check_bits_product).
+struct BitsProduct {
+  mm::Tunable knob;        // the knob of its kernels
+  BitsKernel ker;          // its kernel by shape, ld and knob
+  unsigned b_rows;         // B as it is stored: K x ceil(M / 32) words, or (Bt) M x ceil(K / 32) words
+  size_t b_row;
+  size_t c_row;            // a row of C: ceil(M / 32) words, or M int32 elements -- 4 bytes each either way
+  unsigned align[3];       // bytes to which the tile kernel needs a, b and c aligned, base and batch stride (0: to nothing)
+  const char *b_name, *c_row_text, *ld_text;
+};
+
+BitsProduct bits_gemm_rules(const mm::BitsProblem &p) {
+  const size_t mw = bits_words(p.m);
+  return {mm::TUNE_BITS_VARIANT, bits_kernel_for(p.m, p.ldb, p.ldc), p.k, mw, mw, {0, 16, 8}, "b", "ceil(M / 32)",
+          "a row stride is below its row's words: lda %zu (needs %zu), ldb %zu (%zu), ldc %zu (%zu)"};
+}
+
+BitsProduct bits_count_rules(const mm::BitsProblem &p) {   // p.b: Bt, M x K
+  return {mm::TUNE_BITS_COUNT_VARIANT, bits_count_kernel_for(p.n, p.m, p.lda, p.ldb, p.ldc), p.m, bits_words(p.k), p.m, {16, 16, 16},
+          "bt", "M", "a row stride is below its row: lda %zu (needs %zu words), ldbt %zu (%zu words), ldc %zu (%zu elements)"};
+}
+
+// The launch-time half of the serving rule: the tile kernel's wide accesses, for every element of the batch.
+BitsKernel bits_demote(const mm::BitsProblem &p, BitsKernel ker, const unsigned (&align)[3]) {
   if (ker != BITS_TILE) return ker;
-  const bool aligned = ((uintptr_t)p.b & 15u) == 0 && ((uintptr_t)p.c & 7u) == 0 &&
-                       (p.batch <= 1 || (p.stride_b % 4 == 0 && p.stride_c % 2 == 0));
-  return aligned ? BITS_TILE : BITS_PLAIN;
+  const void *const base[3] = {p.a, p.b, p.c};
+  const size_t stride[3] = {p.stride_a, p.stride_b, p.stride_c};
+  for (int i = 0; i < 3; ++i)
+    if (align[i] && (((uintptr_t)base[i] & (align[i] - 1)) != 0 || (p.batch > 1 && stride[i] % (align[i] / 4) != 0))) return BITS_PLAIN;
+  return BITS_TILE;
 }
 
 // All argument checks of a packed product, before any device is touched.  *ker = BITS_NONE: nothing to launch.
-int check_bits_gemm(const mm::BitsProblem &p, BitsKernel *ker) {
+int check_bits_product(const mm::BitsProblem &p, const BitsProduct &r, BitsKernel *ker) {
   *ker = BITS_NONE;
-  const BitsKernel k = bits_kernel_for(p.m, p.ldb, p.ldc);
-  if (k == BITS_INVALID) return fail(MM_ERR_BAD_ARGUMENT, "bits_variant %d is not one of -1, 0, 1", mm::tuning(mm::TUNE_BITS_VARIANT));
+  if (r.ker == BITS_INVALID) return fail(MM_ERR_BAD_ARGUMENT, "%s %d is not one of -1, 0, 1", kTuneName[r.knob], mm::tuning(r.knob));
   if (p.batch == 0 || p.n == 0 || p.m == 0) return MM_OK;
   if (!p.c || (p.k && (!p.a || !p.b))) return fail(MM_ERR_BAD_ARGUMENT, "null matrix pointer");   // (K = 0: A, B unread)
-  const size_t kw = bits_words(p.k), mw = bits_words(p.m);
-  if (p.lda < kw || p.ldc < mw || (p.k && p.ldb < mw))
-    return fail(MM_ERR_BAD_ARGUMENT, "a row stride is below its row's words: lda %zu (needs %zu), ldb %zu (%zu), ldc %zu (%zu)",
-                p.lda, kw, p.ldb, mw, p.ldc, mw);
-  const size_t c_words = bits_span(p.n, mw, p.ldc, 1, 0);
-  if (p.batch > 1 && p.stride_c < c_words)
-    return fail(MM_ERR_BAD_ARGUMENT, "stride_c %zu < (N - 1) ldc + ceil(M / 32) = %zu: the outputs of the batch would overlap",
-                p.stride_c, c_words);
-  const size_t a_bytes = 4 * bits_span(p.n, kw, p.lda, p.batch, p.stride_a), b_bytes = 4 * bits_span(p.k, mw, p.ldb, p.batch, p.stride_b);
-  const size_t c_bytes = 4 * bits_span(p.n, mw, p.ldc, p.batch, p.stride_c);
+  const size_t kw = bits_words(p.k);
+  if (p.lda < kw || p.ldc < r.c_row || (r.b_rows && p.ldb < r.b_row))
+    return fail(MM_ERR_BAD_ARGUMENT, r.ld_text, p.lda, kw, p.ldb, r.b_row, p.ldc, r.c_row);
+  const size_t c_units = bits_span(p.n, r.c_row, p.ldc, 1, 0);
+  if (p.batch > 1 && p.stride_c < c_units)
+    return fail(MM_ERR_BAD_ARGUMENT, "stride_c %zu < (N - 1) ldc + %s = %zu: the outputs of the batch would overlap", p.stride_c,
+                r.c_row_text, c_units);
+  const size_t a_bytes = 4 * bits_span(p.n, kw, p.lda, p.batch, p.stride_a);
+  const size_t b_bytes = 4 * bits_span(r.b_rows, r.b_row, p.ldb, p.batch, p.stride_b);
+  const size_t c_bytes = 4 * bits_span(p.n, r.c_row, p.ldc, p.batch, p.stride_c);
   if (spans_overlap(p.c, c_bytes, p.a, a_bytes) || spans_overlap(p.c, c_bytes, p.b, b_bytes))
-    return fail(MM_ERR_BAD_ARGUMENT, "c overlaps a or b (bases %p, %p, %p)", (const void *)p.a, (const void *)p.b, (void *)p.c);
+    return fail(MM_ERR_BAD_ARGUMENT, "c overlaps a or %s (bases %p, %p, %p)", r.b_name, (const void *)p.a, (const void *)p.b,
+                (void *)p.c);
   if (p.k == 0 && p.seed) return MM_OK;   // accumulating over no k: C keeps its value
-  *ker = bits_demote(p, k);
+  *ker = bits_demote(p, r.ker, r.align);
   return MM_OK;
 }
 
-// The batch in launches of at most 2^22 workgroups (64 x 64-word tiles, the smaller of the two) and batch_chunk elements.
-int dispatch_bits_gemm(hipStream_t s, const mm::BitsProblem &p, BitsKernel ker) {
-  const unsigned chunk = chunk_of_tiles((unsigned long long)((p.n + 63) / 64) * ((bits_words(p.m) + 63) / 64), p.batch);
-  (void)hipGetLastError();   // a stale error of the application's own calls must not be reported as this launch's
-  for (unsigned e0 = 0; e0 < p.batch; e0 += chunk) {
-    mm::BitsProblem q = p;
-    q.batch = std::min(chunk, p.batch - e0);
-    q.a += (size_t)e0 * p.stride_a;
-    q.b += (size_t)e0 * p.stride_b;
-    q.c += (size_t)e0 * p.stride_c;
-    if (int e = mm::launch_bits_gemm(s, q, ker == BITS_TILE)) return hip_fail((hipError_t)e, "packed product kernel launch");
-  }
-  return MM_OK;
-}
-
-// pack (to_bits) / unpack: *nothing: an empty call
-int check_bits_convert(const mm::BitsConvert &c, bool to_bits, bool *nothing) {
-  *nothing = c.rows == 0 || c.cols == 0 || c.batch == 0;
-  if (*nothing) return MM_OK;
-  if (!c.src || !c.dst) return fail(MM_ERR_BAD_ARGUMENT, "null matrix pointer");
-  const size_t words = bits_words(c.cols), src_row = to_bits ? c.cols : words, dst_row = to_bits ? words : c.cols;
-  if (c.ld_src < src_row || c.ld_dst < dst_row)
-    return fail(MM_ERR_BAD_ARGUMENT, "a row stride is below its row: source %zu (needs %zu), destination %zu (%zu)", c.ld_src,
-                src_row, c.ld_dst, dst_row);
-  if (c.batch > 1 && c.stride_dst < bits_span(c.rows, dst_row, c.ld_dst, 1, 0))
-    return fail(MM_ERR_BAD_ARGUMENT, "destination batch stride %zu: the outputs of the batch would overlap", c.stride_dst);
-  const size_t src_unit = to_bits ? 1 : 4, dst_unit = to_bits ? 4 : 1;
-  if (spans_overlap(c.dst, dst_unit * bits_span(c.rows, dst_row, c.ld_dst, c.batch, c.stride_dst), c.src,
-                    src_unit * bits_span(c.rows, src_row, c.ld_src, c.batch, c.stride_src)))
-    return fail(MM_ERR_BAD_ARGUMENT, "the destination overlaps the source (bases %p, %p)", c.src, c.dst);
-  return MM_OK;
-}
-
-int dispatch_bits_convert(hipStream_t s, const mm::BitsConvert &c, bool to_bits) {
-  (void)hipGetLastError();
-  const int e = to_bits ? mm::launch_bits_pack(s, c) : mm::launch_bits_unpack(s, c);
-  return e ? hip_fail((hipError_t)e, to_bits ? "pack kernel launch" : "unpack kernel launch") : MM_OK;
-}
-
-// ---- bit-packed counting product (mm_bits_count_*) and packed transpose (mm_bits_transpose_*) -----------------------------------
-constexpr unsigned long long kBitsCountTileMin = 256;   // 128 x 128 tiles of C from which bits_count_tile serves: one per CU
-
-// The kernel by shape, ld and knob alone (mm_kernel_name_bits_count); alignment may still demote BITS_TILE at launch.
-BitsKernel bits_count_kernel_for(unsigned n, unsigned m, size_t lda, size_t ldbt, size_t ldc) {
-  const int v = mm::tuning(mm::TUNE_BITS_COUNT_VARIANT);
-  if (v < -1 || v > 1) return BITS_INVALID;
-  if (v == 0 || !mm::bits_count_tile_serves(lda, ldbt, ldc)) return BITS_PLAIN;
-  const unsigned long long tiles = (unsigned long long)(((size_t)n + 127) / 128) * (((size_t)m + 127) / 128);
-  return v == 1 || tiles >= kBitsCountTileMin ? BITS_TILE : BITS_PLAIN;
-}
-
-// The launch-time half of the rule: a, bt and c in 16-byte accesses, for every element of the batch.
-BitsKernel bits_count_demote(const mm::BitsProblem &p, BitsKernel ker) {
-  if (ker != BITS_TILE) return ker;
-  const bool aligned = (((uintptr_t)p.a | (uintptr_t)p.b | (uintptr_t)p.c) & 15u) == 0 &&
-                       (p.batch <= 1 || (p.stride_a % 4 == 0 && p.stride_b % 4 == 0 && p.stride_c % 4 == 0));
-  return aligned ? BITS_TILE : BITS_PLAIN;
-}
-
-// All argument checks of a counting product (p.b: Bt, M x K), before any device is touched.  *ker = BITS_NONE: nothing to launch.
 int check_bits_count(int op, const mm::BitsProblem &p, BitsKernel *ker) {
   *ker = BITS_NONE;
   if (op != MM_BITS_COUNT_AND && op != MM_BITS_COUNT_XOR)
     return fail(MM_ERR_BAD_ARGUMENT, "op %d is not MM_BITS_COUNT_AND (0) or MM_BITS_COUNT_XOR (1)", op);
-  const BitsKernel k = bits_count_kernel_for(p.n, p.m, p.lda, p.ldb, p.ldc);
-  if (k == BITS_INVALID)
-    return fail(MM_ERR_BAD_ARGUMENT, "bits_count_variant %d is not one of -1, 0, 1", mm::tuning(mm::TUNE_BITS_COUNT_VARIANT));
-  if (p.batch == 0 || p.n == 0 || p.m == 0) return MM_OK;
-  if (!p.c || (p.k && (!p.a || !p.b))) return fail(MM_ERR_BAD_ARGUMENT, "null matrix pointer");   // (K = 0: A, Bt unread)
-  const size_t kw = bits_words(p.k);
-  if (p.lda < kw || p.ldb < kw || p.ldc < p.m)
-    return fail(MM_ERR_BAD_ARGUMENT, "a row stride is below its row: lda %zu (needs %zu words), ldbt %zu (%zu words), ldc %zu (%u elements)",
-                p.lda, kw, p.ldb, kw, p.ldc, p.m);
-  const size_t c_elems = bits_span(p.n, p.m, p.ldc, 1, 0);
-  if (p.batch > 1 && p.stride_c < c_elems)
-    return fail(MM_ERR_BAD_ARGUMENT, "stride_c %zu < (N - 1) ldc + M = %zu: the outputs of the batch would overlap", p.stride_c, c_elems);
-  const size_t a_bytes = 4 * bits_span(p.n, kw, p.lda, p.batch, p.stride_a), b_bytes = 4 * bits_span(p.m, kw, p.ldb, p.batch, p.stride_b);
-  const size_t c_bytes = 4 * bits_span(p.n, p.m, p.ldc, p.batch, p.stride_c);
-  if (spans_overlap(p.c, c_bytes, p.a, a_bytes) || spans_overlap(p.c, c_bytes, p.b, b_bytes))
-    return fail(MM_ERR_BAD_ARGUMENT, "c overlaps a or bt (bases %p, %p, %p)", (const void *)p.a, (const void *)p.b, (void *)p.c);
-  if (p.k == 0 && p.seed) return MM_OK;   // accumulating over no k: C keeps its value
-  *ker = bits_count_demote(p, k);
-  return MM_OK;
+  return check_bits_product(p, bits_count_rules(p), ker);
 }
 
-// The batch in launches of at most 2^22 workgroups (64 x 64 tiles, the smaller of the two) and batch_chunk elements.
-int dispatch_bits_count(hipStream_t s, int op, const mm::BitsProblem &p, BitsKernel ker) {
-  const unsigned chunk = chunk_of_tiles((unsigned long long)((p.n + 63) / 64) * ((p.m + 63) / 64), p.batch);
+// The packed twin of for_each_chunk: fn(slice) over the batch in launches of at most 2^22 workgroups -- `tiles` per element,
+// counted in the smaller of a product's two tiles -- and batch_chunk elements.
+template <class F> int for_each_bits_chunk(const mm::BitsProblem &p, unsigned long long tiles, F &&fn) {
+  const unsigned chunk = chunk_of_tiles(tiles, p.batch);
   (void)hipGetLastError();   // a stale error of the application's own calls must not be reported as this launch's
   for (unsigned e0 = 0; e0 < p.batch; e0 += chunk) {
     mm::BitsProblem q = p;
@@ -790,33 +752,58 @@ int dispatch_bits_count(hipStream_t s, int op, const mm::BitsProblem &p, BitsKer
     q.a += (size_t)e0 * p.stride_a;
     q.b += (size_t)e0 * p.stride_b;
     q.c += (size_t)e0 * p.stride_c;
-    if (int e = mm::launch_bits_count(s, q, op == MM_BITS_COUNT_XOR, ker == BITS_TILE))
-      return hip_fail((hipError_t)e, "packed counting kernel launch");
+    if (int rc = fn(q)) return rc;
   }
   return MM_OK;
 }
 
-// c.src rows x cols, c.dst cols x rows, both packed: check_bits_convert's refusals with both sides in words
-int check_bits_transpose(const mm::BitsConvert &c, bool *nothing) {
+int dispatch_bits_gemm(hipStream_t s, const mm::BitsProblem &p, BitsKernel ker) {   // tiles of 64 x 64 words
+  return for_each_bits_chunk(p, (unsigned long long)((p.n + 63) / 64) * ((bits_words(p.m) + 63) / 64), [&](const mm::BitsProblem &q) {
+    const int e = mm::launch_bits_gemm(s, q, ker == BITS_TILE);
+    return e ? hip_fail((hipError_t)e, "packed product kernel launch") : MM_OK;
+  });
+}
+
+int dispatch_bits_count(hipStream_t s, int op, const mm::BitsProblem &p, BitsKernel ker) {   // tiles of 64 x 64 elements
+  return for_each_bits_chunk(p, (unsigned long long)((p.n + 63) / 64) * ((p.m + 63) / 64), [&](const mm::BitsProblem &q) {
+    const int e = mm::launch_bits_count(s, q, op == MM_BITS_COUNT_XOR, ker == BITS_TILE);
+    return e ? hip_fail((hipError_t)e, "packed counting kernel launch") : MM_OK;
+  });
+}
+
+// ---- pack, unpack and the packed transpose: one check, each side given as it is stored ---------------------------------------
+enum BitsConversion { BITS_PACK, BITS_UNPACK, BITS_TRANSPOSE };
+struct BitsSide {
+  unsigned rows;
+  size_t row, unit;   // units of a row, bytes of a unit: bytes of the unpacked form, words of the packed one
+};
+
+// *nothing: an empty call
+int check_bits_convert(const mm::BitsConvert &c, const BitsSide &src, const BitsSide &dst, bool *nothing) {
   *nothing = c.rows == 0 || c.cols == 0 || c.batch == 0;
   if (*nothing) return MM_OK;
   if (!c.src || !c.dst) return fail(MM_ERR_BAD_ARGUMENT, "null matrix pointer");
-  const size_t src_row = bits_words(c.cols), dst_row = bits_words(c.rows);
-  if (c.ld_src < src_row || c.ld_dst < dst_row)
+  if (c.ld_src < src.row || c.ld_dst < dst.row)
     return fail(MM_ERR_BAD_ARGUMENT, "a row stride is below its row: source %zu (needs %zu), destination %zu (%zu)", c.ld_src,
-                src_row, c.ld_dst, dst_row);
-  if (c.batch > 1 && c.stride_dst < bits_span(c.cols, dst_row, c.ld_dst, 1, 0))
+                src.row, c.ld_dst, dst.row);
+  if (c.batch > 1 && c.stride_dst < bits_span(dst.rows, dst.row, c.ld_dst, 1, 0))
     return fail(MM_ERR_BAD_ARGUMENT, "destination batch stride %zu: the outputs of the batch would overlap", c.stride_dst);
-  if (spans_overlap(c.dst, 4 * bits_span(c.cols, dst_row, c.ld_dst, c.batch, c.stride_dst), c.src,
-                    4 * bits_span(c.rows, src_row, c.ld_src, c.batch, c.stride_src)))
+  if (spans_overlap(c.dst, dst.unit * bits_span(dst.rows, dst.row, c.ld_dst, c.batch, c.stride_dst), c.src,
+                    src.unit * bits_span(src.rows, src.row, c.ld_src, c.batch, c.stride_src)))
     return fail(MM_ERR_BAD_ARGUMENT, "the destination overlaps the source (bases %p, %p)", c.src, c.dst);
   return MM_OK;
 }
 
-int dispatch_bits_transpose(hipStream_t s, const mm::BitsConvert &c) {
+int dispatch_bits_convert(hipStream_t s, const mm::BitsConvert &c, BitsConversion how) {
+  static constexpr struct {
+    int (*launch)(hipStream_t, const mm::BitsConvert &);
+    const char *what;
+  } kConversions[] = {{mm::launch_bits_pack, "pack kernel launch"},
+                      {mm::launch_bits_unpack, "unpack kernel launch"},
+                      {mm::launch_bits_transpose, "packed transpose kernel launch"}};
   (void)hipGetLastError();
-  const int e = mm::launch_bits_transpose(s, c);
-  return e ? hip_fail((hipError_t)e, "packed transpose kernel launch") : MM_OK;
+  const int e = kConversions[how].launch(s, c);
+  return e ? hip_fail((hipError_t)e, kConversions[how].what) : MM_OK;
 }
 
 constexpr unsigned kBitsClosureBlock = 64;   // one wavefront closes a diagonal block: one row of 64 bits per lane
@@ -835,8 +822,8 @@ int check_bits_closure(const void *d, unsigned n, size_t ldd, unsigned batch, si
 
 // One product of a closure round on the graphs of a chunk: the library's own operands, no argument checks.
 int bits_closure_product(hipStream_t s, const mm::BitsProblem &p) {
-  const BitsKernel k = bits_kernel_for(p.m, p.ldb, p.ldc);
-  return dispatch_bits_gemm(s, p, bits_demote(p, k == BITS_INVALID ? BITS_PLAIN : k));
+  const BitsProduct r = bits_gemm_rules(p);
+  return dispatch_bits_gemm(s, p, bits_demote(p, r.ker == BITS_INVALID ? BITS_PLAIN : r.ker, r.align));
 }
 
 // The packed closure on stream `s`, never synchronising the host.  n <= 64: the wavefront kernel in place, 2^20 graphs per
@@ -1306,14 +1293,8 @@ int run_closure(const Target &t, const mm_config_t *cfg, void *d, int *witness, 
 
 int run_bits_gemm(const Target &t, const mm::BitsProblem &p) {
   BitsKernel ker;
-  if (int rc = check_bits_gemm(p, &ker)) return rc;
+  if (int rc = check_bits_product(p, bits_gemm_rules(p), &ker)) return rc;
   return run(t, ker == BITS_NONE, [&](hipStream_t s) { return dispatch_bits_gemm(s, p, ker); });
-}
-
-int run_bits_convert(const Target &t, const mm::BitsConvert &c, bool to_bits) {
-  bool nothing;
-  if (int rc = check_bits_convert(c, to_bits, &nothing)) return rc;
-  return run(t, nothing, [&](hipStream_t s) { return dispatch_bits_convert(s, c, to_bits); });
 }
 
 int run_bits_count(const Target &t, int op, const mm::BitsProblem &p) {
@@ -1322,10 +1303,14 @@ int run_bits_count(const Target &t, int op, const mm::BitsProblem &p) {
   return run(t, ker == BITS_NONE, [&](hipStream_t s) { return dispatch_bits_count(s, op, p, ker); });
 }
 
-int run_bits_transpose(const Target &t, const mm::BitsConvert &c) {
+// c.src rows x cols; c.dst the same in the other form, or (the transpose) cols x rows packed
+int run_bits_convert(const Target &t, const mm::BitsConvert &c, BitsConversion how) {
+  const BitsSide bytes{c.rows, c.cols, 1}, words{c.rows, bits_words(c.cols), 4}, turned{c.cols, bits_words(c.rows), 4};
   bool nothing;
-  if (int rc = check_bits_transpose(c, &nothing)) return rc;
-  return run(t, nothing, [&](hipStream_t s) { return dispatch_bits_transpose(s, c); });
+  if (int rc = check_bits_convert(c, how == BITS_PACK ? bytes : words, how == BITS_PACK ? words : how == BITS_UNPACK ? bytes : turned,
+                                  &nothing))
+    return rc;
+  return run(t, nothing, [&](hipStream_t s) { return dispatch_bits_convert(s, c, how); });
 }
 
 int run_bits_closure(const Target &t, void *d, unsigned n, size_t ldd, unsigned batch, size_t stride_d) {
@@ -1679,13 +1664,13 @@ int mm_bits_closure_launch(int device, void *d, unsigned n, size_t ldd, unsigned
 
 int mm_bits_pack_enqueue(void *hip_stream, const void *bytes, void *packed, unsigned rows, unsigned cols, size_t ld_bytes,
                          size_t ld_packed, unsigned batch, size_t stride_bytes, size_t stride_packed) {
-  return run_bits_convert(on_stream(hip_stream), {bytes, packed, rows, cols, ld_bytes, ld_packed, batch, stride_bytes, stride_packed}, true);
+  return run_bits_convert(on_stream(hip_stream), {bytes, packed, rows, cols, ld_bytes, ld_packed, batch, stride_bytes, stride_packed}, BITS_PACK);
 }
 
 int mm_bits_pack_launch(int device, const void *bytes, void *packed, unsigned rows, unsigned cols, size_t ld_bytes, size_t ld_packed,
                         unsigned batch, size_t stride_bytes, size_t stride_packed, double *elapsed_seconds) {
   return run_bits_convert(timed_on(device, elapsed_seconds),
-                          {bytes, packed, rows, cols, ld_bytes, ld_packed, batch, stride_bytes, stride_packed}, true);
+                          {bytes, packed, rows, cols, ld_bytes, ld_packed, batch, stride_bytes, stride_packed}, BITS_PACK);
 }
 
 int mm_bits_count_enqueue(void *hip_stream, int op, const void *a, const void *bt, void *c, unsigned n, unsigned k, unsigned m,
@@ -1704,23 +1689,24 @@ int mm_bits_count_launch(int device, int op, const void *a, const void *bt, void
 
 int mm_bits_transpose_enqueue(void *hip_stream, const void *src, void *dst, unsigned rows, unsigned cols, size_t ld_src,
                               size_t ld_dst, unsigned batch, size_t stride_src, size_t stride_dst) {
-  return run_bits_transpose(on_stream(hip_stream), {src, dst, rows, cols, ld_src, ld_dst, batch, stride_src, stride_dst});
+  return run_bits_convert(on_stream(hip_stream), {src, dst, rows, cols, ld_src, ld_dst, batch, stride_src, stride_dst}, BITS_TRANSPOSE);
 }
 
 int mm_bits_transpose_launch(int device, const void *src, void *dst, unsigned rows, unsigned cols, size_t ld_src, size_t ld_dst,
                              unsigned batch, size_t stride_src, size_t stride_dst, double *elapsed_seconds) {
-  return run_bits_transpose(timed_on(device, elapsed_seconds), {src, dst, rows, cols, ld_src, ld_dst, batch, stride_src, stride_dst});
+  return run_bits_convert(timed_on(device, elapsed_seconds), {src, dst, rows, cols, ld_src, ld_dst, batch, stride_src, stride_dst},
+                          BITS_TRANSPOSE);
 }
 
 int mm_bits_unpack_enqueue(void *hip_stream, const void *packed, void *bytes, unsigned rows, unsigned cols, size_t ld_packed,
                            size_t ld_bytes, unsigned batch, size_t stride_packed, size_t stride_bytes) {
-  return run_bits_convert(on_stream(hip_stream), {packed, bytes, rows, cols, ld_packed, ld_bytes, batch, stride_packed, stride_bytes}, false);
+  return run_bits_convert(on_stream(hip_stream), {packed, bytes, rows, cols, ld_packed, ld_bytes, batch, stride_packed, stride_bytes}, BITS_UNPACK);
 }
 
 int mm_bits_unpack_launch(int device, const void *packed, void *bytes, unsigned rows, unsigned cols, size_t ld_packed, size_t ld_bytes,
                           unsigned batch, size_t stride_packed, size_t stride_bytes, double *elapsed_seconds) {
   return run_bits_convert(timed_on(device, elapsed_seconds),
-                          {packed, bytes, rows, cols, ld_packed, ld_bytes, batch, stride_packed, stride_bytes}, false);
+                          {packed, bytes, rows, cols, ld_packed, ld_bytes, batch, stride_packed, stride_bytes}, BITS_UNPACK);
 }
 
 // Rows per device of the N split: ceil(N / G) rounded up to whole tile rows of the kernel that will run on a slab of that
@@ -2107,7 +2093,7 @@ const char *mm_kernel_name_closure(const mm_config_t *cfg, unsigned n, unsigned 
 
 const char *mm_kernel_name_bits_gemm(unsigned n, unsigned k, unsigned m, size_t lda, size_t ldb, size_t ldc, unsigned batch) {
   (void)n, (void)k, (void)lda, (void)batch;   // the batch is chunked, never a different kernel
-  switch (bits_kernel_for(m, ldb, ldc)) {     // the choice check_bits_gemm makes, before alignment
+  switch (bits_kernel_for(m, ldb, ldc)) {     // the choice bits_gemm_rules makes, before alignment
     case BITS_TILE: return "bits_tile";
     case BITS_INVALID: return "invalid";
     default: return "bits_plain";
@@ -2116,7 +2102,7 @@ const char *mm_kernel_name_bits_gemm(unsigned n, unsigned k, unsigned m, size_t 
 
 const char *mm_kernel_name_bits_count(unsigned n, unsigned k, unsigned m, size_t lda, size_t ldbt, size_t ldc, unsigned batch) {
   (void)k, (void)batch;   // the batch is chunked, never a different kernel
-  switch (bits_count_kernel_for(n, m, lda, ldbt, ldc)) {   // the choice check_bits_count makes, before alignment
+  switch (bits_count_kernel_for(n, m, lda, ldbt, ldc)) {   // the choice bits_count_rules makes, before alignment
     case BITS_TILE: return "bits_count_tile";
     case BITS_INVALID: return "invalid";
     default: return "bits_count_plain";

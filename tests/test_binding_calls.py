@@ -5,7 +5,9 @@ gemm_hls_amd._enqueue is replaced by a recorder.  For every wrapper the recorded
 order, shapes, batch, strides, index_base, accumulate flag -- and every refusal's full message is compared with a literal.
 The literals were recorded once from the binding as it stood before its wrappers were folded into one skeleton; they are
 never computed from the code under test.  Two messages of matmul and bmm (devices that differ, a dtype that does not match)
-are the exception: those two wrappers took the other wrappers' wording of the same facts with the skeleton.  One more table pins the ctypes prototype of every exported symbol."""
+are the exception: those two wrappers took the other wrappers' wording of the same facts with the skeleton.  The packed
+counting wrappers' and the packed transpose's calls and refusals were recorded the same way, before their skeleton.  One more
+table pins the ctypes prototype of every exported symbol."""
 import collections
 import ctypes
 
@@ -164,6 +166,9 @@ def _call_cases():
             t.a(B, N, 2, strides=(64, 5, 1), dtype=i32), t.b(B, 40, 3, strides=(0, 3, 1), dtype=i32), 40, 70),
         "bits_matmul/wider_out": lambda t: g.bits_matmul(t.a(N, 2, dtype=i32), t.b(40, 3, dtype=i32), 40, 70,
                                                          out=t.c(N, 4, dtype=i32)),
+        # no columns, and a batch of no rows: a fresh result's strides are what torch gives an empty tensor
+        "bits_matmul/no_columns": lambda t: g.bits_matmul(t.a(N, 2, dtype=i32), t.b(40, 0, dtype=i32), 40, 0),
+        "bits_matmul/3d_no_rows": lambda t: g.bits_matmul(t.a(B, 0, 2, dtype=i32), t.b(B, 40, 3, dtype=i32), 40, 70),
         "bits_addmm_/2d": lambda t: g.bits_addmm_(t.c(N, 3, dtype=i32), t.a(N, 2, dtype=i32), t.b(40, 3, dtype=i32), 40, 70),
         "bits_addmm_/c_over_2d_operands": lambda t: g.bits_addmm_(
             t.c(B, N, 3, strides=(100, 4, 1), dtype=i32), t.a(N, 2, dtype=i32), t.b(40, 3, dtype=i32), 40, 70),
@@ -175,6 +180,19 @@ def _call_cases():
         "pack_bits/3d_row_stride": lambda t: g.pack_bits(t.a(B, N, 70, strides=(700, 80, 1), dtype=u8)),
         "unpack_bits/2d": lambda t: g.unpack_bits(t.a(N, 3, dtype=i32), 70),
         "unpack_bits/3d_wider_rows_uint8": lambda t: g.unpack_bits(t.a(B, N, 4, dtype=i32), 70, u8),
+        "bits_matmul_count/2d": lambda t: g.bits_matmul_count(t.a(N, 2, dtype=i32), t.b(M, 2, dtype=i32), 40),
+        # a column slice of whole words (row stride 5), a broadcast bt, a 3-D a, Xor, an out with its own row stride
+        "bits_matmul_count/sliced_a_expanded_bt_xor_out": lambda t: g.bits_matmul_count(
+            t.a(B, N, 2, strides=(40, 5, 1), dtype=i32), t.b(B, M, 2, strides=(0, 2, 1), dtype=i32), 64, op="Xor",
+            out=t.c(B, N, M, strides=(200, 16, 1), dtype=i32)),
+        "bits_matmul_count/3d_a_2d_bt": lambda t: g.bits_matmul_count(
+            t.a(B, N, 2, strides=(40, 5, 1), dtype=i32), t.b(M, 2, dtype=i32), 64),
+        "bits_addmm_count_/3d_a_2d_bt": lambda t: g.bits_addmm_count_(
+            t.c(B, N, M, strides=(200, 16, 1), dtype=i32), t.a(B, N, 2, strides=(40, 5, 1), dtype=i32), t.b(M, 2, dtype=i32), 33),
+        "transpose_bits/3d_row_stride": lambda t: g.transpose_bits(t.a(B, 70, 6, strides=(500, 7, 1), dtype=i32), 130),
+        "transpose_bits/2d_wider_out": lambda t: g.transpose_bits(t.a(70, 5, dtype=i32), 130, out=t.c(130, 4, dtype=i32)),
+        # more batch dimensions: one flat batch of a dense copy
+        "transpose_bits/4d": lambda t: g.transpose_bits(t.a(2, B, 70, 5, dtype=i32), 130),
     }
     for key, fn in other.items():
         cases[key] = (None, fn)
@@ -247,6 +265,8 @@ OTHER_CALLS = {
     "bits_matmul/sliced_a_expanded_b": ("mm_bits_gemm_enqueue", None, (A_, B_, 0, 8, 40, 70, 5, 3, 3, 3, 64, 0, 24, 0),
                                         (((3, 8, 3), i32),)),
     "bits_matmul/wider_out": ("mm_bits_gemm_enqueue", None, (A_, B_, C_, 8, 40, 70, 2, 3, 4, 1, 0, 0, 0, 0), (((8, 4), i32),)),
+    "bits_matmul/no_columns": ("mm_bits_gemm_enqueue", None, (A_, B_, 0, 8, 40, 0, 2, 1, 1, 1, 0, 0, 0, 0), (((8, 0), i32),)),
+    "bits_matmul/3d_no_rows": ("mm_bits_gemm_enqueue", None, (A_, B_, 0, 0, 40, 70, 2, 3, 3, 3, 2, 120, 3, 0), (((3, 0, 3), i32),)),
     "bits_addmm_/2d": ("mm_bits_gemm_enqueue", None, (A_, B_, C_, 8, 40, 70, 2, 3, 3, 1, 0, 0, 0, 1), (((8, 3), i32),)),
     "bits_addmm_/c_over_2d_operands": ("mm_bits_gemm_enqueue", None, (A_, B_, C_, 8, 40, 70, 2, 3, 4, 3, 0, 0, 100, 1),
                                        (((3, 8, 3), i32),)),
@@ -257,6 +277,17 @@ OTHER_CALLS = {
     "pack_bits/3d_row_stride": ("mm_bits_pack_enqueue", None, (A_, 0, 8, 70, 80, 3, 3, 700, 24), (((3, 8, 3), i32),)),
     "unpack_bits/2d": ("mm_bits_unpack_enqueue", None, (A_, 0, 8, 70, 3, 70, 1, 0, 560), (((8, 70), "bool"),)),
     "unpack_bits/3d_wider_rows_uint8": ("mm_bits_unpack_enqueue", None, (A_, 0, 8, 70, 4, 70, 3, 32, 560), (((3, 8, 70), "uint8"),)),
+    "bits_matmul_count/2d": ("mm_bits_count_enqueue", None, (0, A_, B_, 0, 8, 40, 12, 2, 2, 12, 1, 0, 0, 0, 0), (((8, 12), i32),)),
+    "bits_matmul_count/sliced_a_expanded_bt_xor_out": ("mm_bits_count_enqueue", None,
+                                                       (1, A_, B_, C_, 8, 64, 12, 5, 2, 16, 3, 40, 0, 200, 0), (((3, 8, 12), i32),)),
+    "bits_matmul_count/3d_a_2d_bt": ("mm_bits_count_enqueue", None, (0, A_, B_, 0, 8, 64, 12, 5, 2, 12, 3, 40, 0, 96, 0),
+                                     (((3, 8, 12), i32),)),
+    "bits_addmm_count_/3d_a_2d_bt": ("mm_bits_count_enqueue", None, (0, A_, B_, C_, 8, 33, 12, 5, 2, 16, 3, 40, 0, 200, 1),
+                                     (((3, 8, 12), i32),)),
+    "transpose_bits/3d_row_stride": ("mm_bits_transpose_enqueue", None, (A_, 0, 70, 130, 7, 3, 3, 500, 390), (((3, 130, 3), i32),)),
+    "transpose_bits/2d_wider_out": ("mm_bits_transpose_enqueue", None, (A_, C_, 70, 130, 5, 4, 1, 0, 0), (((130, 4), i32),)),
+    # (the dense copy of a meta tensor has no address)
+    "transpose_bits/4d": ("mm_bits_transpose_enqueue", None, (0, 0, 70, 130, 5, 3, 6, 350, 390), (((2, 3, 130, 3), i32),)),
 }
 
 
@@ -287,8 +318,10 @@ EXPECTED_CALLS = {key: expected_call(key) for key in CALL_CASES}
 def test_the_tables_cover_every_wrapper():
     assert set(SYMBOLS) == set(SPECS) and set(OTHER_CALLS) <= set(CALL_CASES)
     covered = {key.split("/")[0] for key in CALL_CASES}
-    assert covered == set(SPECS) | {"closure_", "bits_matmul", "bits_addmm_", "bits_closure_", "pack_bits", "unpack_bits"}
+    assert covered == set(SPECS) | {"closure_", "bits_matmul", "bits_addmm_", "bits_closure_", "pack_bits", "unpack_bits",
+                                    "bits_matmul_count", "bits_addmm_count_", "transpose_bits"}
     assert {key.split("/")[0] for key in REFUSAL_CASES} == set(SPECS)
+    assert {key.split("/")[0] for key in OTHER_REFUSALS} == {"bits_matmul_count", "bits_addmm_count_", "transpose_bits"}
 
 
 @pytest.mark.parametrize("key", sorted(CALL_CASES))
@@ -446,6 +479,82 @@ def test_refusal_message(key, recorded):
     assert run_refusal_case(key, recorded) == EXPECTED_REFUSALS[key]
 
 
+# ---- refusals of the packed counting wrappers and the packed transpose -----------------------------------------------------
+def _claims(x, device):
+    """x, claiming to live on `device`."""
+    x.device = device
+    return x
+
+
+def _count_refusals():
+    i32 = torch.int32
+    cases = {}
+    both = {"bits_matmul_count": lambda t, a, bt, k, **kw: g.bits_matmul_count(a, bt, k, **kw),
+            "bits_addmm_count_": lambda t, a, bt, k, **kw: g.bits_addmm_count_(t.c(N, M, dtype=i32), a, bt, k, **kw)}
+    for name, call in both.items():
+        def add(case, fn, call=call, name=name):
+            cases[f"{name}/{case}"] = lambda t: fn(t, call)
+        a, bt = (lambda t: t.a(N, 2, dtype=i32)), (lambda t: t.b(M, 2, dtype=i32))
+        add("dtype_a", lambda t, call: call(t, t.a(N, 2, dtype=torch.int64), bt(t), 40))
+        add("dtype_bt", lambda t, call: call(t, a(t), t.b(M, 2, dtype=torch.uint8), 40))
+        add("k_beyond_the_words", lambda t, call: call(t, a(t), bt(t), 65))
+        add("bt_one_word", lambda t, call: call(t, a(t), t.b(M, 1, dtype=i32), 40))
+        add("batch", lambda t, call: call(t, t.a(B, N, 2, dtype=i32), t.b(2, M, 2, dtype=i32), 40))
+        add("other_device_bt", lambda t, call: call(t, a(t), _claims(t.b(M, 2, dtype=i32), torch.device("cuda", 1)), 40))
+        add("op", lambda t, call: call(t, a(t), bt(t), 40, op="Or"))
+        add("a_4d", lambda t, call: call(t, t.a(2, B, N, 2, dtype=i32), bt(t), 40))
+        add("a_words_not_contiguous", lambda t, call: call(t, t.a(N, 2, strides=(4, 2), dtype=i32), bt(t), 40))
+    a, bt = (lambda t: t.a(N, 2, dtype=i32)), (lambda t: t.b(M, 2, dtype=i32))
+    cases.update({
+        "bits_matmul_count/cpu": lambda t: g.bits_matmul_count(torch.zeros(4, 1, dtype=i32), torch.zeros(4, 1, dtype=i32), 4),
+        "bits_matmul_count/out_dtype": lambda t: g.bits_matmul_count(a(t), bt(t), 40, out=t.c(N, M, dtype=torch.float32)),
+        "bits_matmul_count/out_shape": lambda t: g.bits_matmul_count(a(t), bt(t), 40, out=t.c(N, M + 1, dtype=i32)),
+        "bits_addmm_count_/batch_into_2d_c": lambda t: g.bits_addmm_count_(t.c(N, M, dtype=i32), t.a(B, N, 2, dtype=i32), bt(t), 40),
+        "bits_addmm_count_/c_expanded": lambda t: g.bits_addmm_count_(t.c(B, N, M, strides=(0, M, 1), dtype=i32), a(t), bt(t), 40),
+        "transpose_bits/cpu": lambda t: g.transpose_bits(torch.zeros(4, 1, dtype=i32), 4),
+        "transpose_bits/dtype": lambda t: g.transpose_bits(t.a(70, 5, dtype=torch.int16), 130),
+        "transpose_bits/cols_beyond_the_words": lambda t: g.transpose_bits(t.a(70, 4, dtype=i32), 130),
+        "transpose_bits/out_rows_beyond_its_words": lambda t: g.transpose_bits(t.a(70, 5, dtype=i32), 130, out=t.c(130, 2, dtype=i32)),
+    })
+    return cases
+
+
+OTHER_REFUSALS = _count_refusals()
+# what both counting wrappers say of their operands; {w}: the wrapper
+COUNT_OPERAND_MESSAGES = {
+    "dtype_a": "a must be a packed torch.int32 tensor (got torch.int64)",
+    "dtype_bt": "bt must be a packed torch.int32 tensor (got torch.uint8)",
+    "k_beyond_the_words": "a has shape (8, 2), expected (8, W) or (B, 8, W) with W >= 3",
+    "bt_one_word": "bt has shape (12, 1), expected (12, W) or (B, 12, W) with W >= 2",
+    "batch": "batch sizes differ: 3 and 2",
+    "other_device_bt": "operands live on different devices: meta and cuda:1",
+    "op": "{w}: op must be one of ['And', 'Xor'] (got 'Or')",
+    "a_4d": "{w} takes 2-D or 3-D operands",
+    "a_words_not_contiguous": "the words of a row of a must be contiguous (strides (4, 2))",
+}
+EXPECTED_OTHER_REFUSALS = {
+    "bits_matmul_count/cpu": "bits_matmul_count needs device tensors: there is no CPU path",
+    "bits_matmul_count/out_dtype": "out must be a torch.int32 tensor (got torch.float32)",
+    "bits_matmul_count/out_shape": "out has shape (8, 13), expected (8, 12)",
+    "bits_addmm_count_/batch_into_2d_c": "c has shape (8, 12), expected (3, 8, 12)",
+    "bits_addmm_count_/c_expanded": "c has batch stride 0: the 3 outputs would overlap",
+    "transpose_bits/cpu": "transpose_bits needs a device tensor: there is no CPU path",
+    "transpose_bits/dtype": "p must be a packed torch.int32 tensor (got torch.int16)",
+    "transpose_bits/cols_beyond_the_words": "p has shape (70, 4), expected (70, W) or (B, 70, W) with W >= 5",
+    "transpose_bits/out_rows_beyond_its_words": "out has shape (130, 2), expected (130, W) or (B, 130, W) with W >= 3",
+}
+EXPECTED_OTHER_REFUSALS.update((f"{w}/{case}", message.format(w=w)) for w in ("bits_matmul_count", "bits_addmm_count_")
+                               for case, message in COUNT_OPERAND_MESSAGES.items())
+
+
+@pytest.mark.parametrize("key", sorted(OTHER_REFUSALS))
+def test_other_refusal_message(key, recorded):
+    with pytest.raises(g.MMError) as info:
+        OTHER_REFUSALS[key](Make())
+    assert info.type is g.MMError and recorded == [], key
+    assert str(info.value) == EXPECTED_OTHER_REFUSALS[key]
+
+
 # ---- prototypes ----------------------------------------------------------------------------------------------------------------
 def _type_name(tp):
     # (where unsigned long long has unsigned long's size, ctypes makes them one type: c_size_t's name wins here)
@@ -531,6 +640,11 @@ EXPECTED_PROTOTYPES = {
     "mm_bits_pack_launch": f"i <- i {BITS_CONVERT} d*",
     "mm_bits_unpack_enqueue": f"i <- vp {BITS_CONVERT}",
     "mm_bits_unpack_launch": f"i <- i {BITS_CONVERT} d*",
+    "mm_bits_count_enqueue": f"i <- vp i {BITS_GEMM}",
+    "mm_bits_count_launch": f"i <- i i {BITS_GEMM} d*",
+    "mm_kernel_name_bits_count": "str <- u u u sz sz sz u",
+    "mm_bits_transpose_enqueue": f"i <- vp {BITS_CONVERT}",
+    "mm_bits_transpose_launch": f"i <- i {BITS_CONVERT} d*",
 }
 
 

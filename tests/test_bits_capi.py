@@ -4,6 +4,7 @@ extents are no-ops; the kernel names follow the serving rule on both sides of ea
 scratch, a private segment or AGPRs; and the numpy restatement of the storage format that the GPU tests use puts every bit
 where include/mm_gemm.h says."""
 import ctypes
+import functools
 import os
 import re
 import subprocess
@@ -12,7 +13,9 @@ import numpy as np
 import pytest
 
 import _bits_ref as br
+import _bits_rig
 import gemm_hls_amd as g
+from _bits_rig import LAUNCH, _err
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = open(os.path.join(ROOT, "include", "mm_gemm.h")).read()
@@ -25,10 +28,6 @@ MM_OK, MM_ERR_NO_DEVICE, MM_ERR_BAD_ARGUMENT = 0, 1, 2
 A0, B0, C0 = 1 << 24, 2 << 24, 3 << 24
 N, K, M = 70, 100, 130          # 4 words of K, 5 words of M
 KW, MW = 4, 5
-
-
-def _err():
-    return g.lib().mm_last_error().decode()
 
 
 def _gemm(launch, a=A0, b=B0, c=C0, n=N, k=K, m=M, lda=KW, ldb=MW, ldc=MW, batch=1, sa=0, sb=0, sc=0, acc=0, device=0):
@@ -61,7 +60,7 @@ def _convert(launch, to_bits, src=A0, dst=C0, rows=N, cols=M, ld_src=None, ld_ds
     return rc
 
 
-LAUNCH = pytest.mark.parametrize("launch", [False, True], ids=["enqueue", "launch"])
+_Variant = functools.partial(_bits_rig._Variant, "bits_variant")
 
 
 def test_bits_symbols_declared_exported_and_bound():
@@ -99,19 +98,6 @@ def test_bits_gemm_refusals_without_a_device(launch):
         assert _gemm(launch, acc=acc, batch=4, sc=1 << 10, sb=1 << 10, a=C0 + 3 * (4 << 10)) == MM_ERR_BAD_ARGUMENT
     with _Variant(2):
         assert _gemm(launch) == MM_ERR_BAD_ARGUMENT and "bits_variant" in _err()
-
-
-class _Variant:
-    """bits_variant set for the duration of a with-block."""
-    def __init__(self, value):
-        self.value = value
-
-    def __enter__(self):
-        self.old = g.get_tuning("bits_variant")
-        g.set_tuning("bits_variant", self.value)
-
-    def __exit__(self, *exc):
-        g.set_tuning("bits_variant", self.old)
 
 
 @LAUNCH

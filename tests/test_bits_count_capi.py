@@ -1,9 +1,10 @@
-"""CPU tests of the packed counting calls (mm_bits_count_*, mm_kernel_name_bits_count, mm_bits_transpose_*): their header
-(include/mm_bits_count.h, included by mm_gemm.h), the binding's BITS_COUNT_EXPORTS and the library agree; every refusal returns its status, with a message, before any device is touched; zero extents are
-no-ops; the kernel names follow the serving rule on both sides of its thresholds; the torch wrappers refuse bad arguments on
-the host and hand the C ABI what the tensors say; no kernel of the new unit uses scratch; and the numpy oracle of the GPU
-tests counts what a loop counts."""
+"""CPU tests of the packed counting calls (mm_bits_count_*, mm_kernel_name_bits_count, mm_bits_transpose_*): include/mm_gemm.h,
+the binding's EXPORTS and the library agree; every refusal returns its status, with a message, before any device is touched;
+zero extents are no-ops; the kernel names follow the serving rule on both sides of its thresholds; no kernel of the unit uses
+scratch; and the numpy oracle of the GPU tests counts what a loop counts.  (What the torch wrappers hand to the C ABI and
+what they refuse: tests/test_binding_calls.py.)"""
 import ctypes
+import functools
 import os
 import re
 import subprocess
@@ -12,11 +13,12 @@ import numpy as np
 import pytest
 
 import _bits_count_ref as cr
+import _bits_rig
 import gemm_hls_amd as g
+from _bits_rig import LAUNCH, _err
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-MAIN_HEADER = open(os.path.join(ROOT, "include", "mm_gemm.h")).read()
-HEADER = open(os.path.join(ROOT, "include", "mm_bits_count.h")).read()     # the family's own header, included by mm_gemm.h
+HEADER = open(os.path.join(ROOT, "include", "mm_gemm.h")).read()
 SYMBOLS = ("mm_bits_count_enqueue", "mm_bits_count_launch", "mm_kernel_name_bits_count", "mm_bits_transpose_enqueue",
            "mm_bits_transpose_launch")
 MM_OK, MM_ERR_NO_DEVICE, MM_ERR_BAD_ARGUMENT = 0, 1, 2
@@ -25,10 +27,6 @@ MM_OK, MM_ERR_NO_DEVICE, MM_ERR_BAD_ARGUMENT = 0, 1, 2
 A0, B0, C0 = 1 << 24, 2 << 24, 3 << 24
 N, K, M = 70, 100, 130          # 4 words of K
 KW = 4
-
-
-def _err():
-    return g.lib().mm_last_error().decode()
 
 
 def _count(launch, op=0, a=A0, b=B0, c=C0, n=N, k=K, m=M, lda=KW, ldbt=KW, ldc=M, batch=1, sa=0, sb=0, sc=0, acc=0, device=0):
@@ -49,37 +47,20 @@ def _transpose(launch, src=A0, dst=C0, rows=N, cols=M, ld_src=5, ld_dst=3, batch
     return rc
 
 
-LAUNCH = pytest.mark.parametrize("launch", [False, True], ids=["enqueue", "launch"])
-
-
-class _Variant:
-    """bits_count_variant set for the duration of a with-block."""
-    def __init__(self, value):
-        self.value = value
-
-    def __enter__(self):
-        self.old = g.get_tuning("bits_count_variant")
-        g.set_tuning("bits_count_variant", self.value)
-
-    def __exit__(self, *exc):
-        g.set_tuning("bits_count_variant", self.old)
+_Variant = functools.partial(_bits_rig._Variant, "bits_count_variant")
 
 
 def test_bits_count_symbols_declared_exported_and_bound():
-    # the regex of tests/test_capi_symbols.py on the family's header: what it declares is what the binding lists, and the
-    # library exports every one; mm_gemm.h includes the header, and EXPORTS stays what mm_gemm.h itself declares
-    declared = set(re.findall(r"^\s*(?:int|void|size_t|const char \*)\s*\*?\s*(mm_\w+)\s*\(", HEADER, flags=re.M))
-    assert declared == set(SYMBOLS) == set(g.BITS_COUNT_EXPORTS) and len(g.BITS_COUNT_EXPORTS) == len(SYMBOLS)
-    assert re.search(r'^#include "mm_bits_count.h"$', MAIN_HEADER, flags=re.M) and not set(SYMBOLS) & set(g.EXPORTS)
     for sym in SYMBOLS:
         assert re.search(rf"^(int|const char)\s*\*?\s*{sym}\(", HEADER, flags=re.M), sym
+        assert sym in g.EXPORTS
         assert getattr(g.lib(), sym).argtypes is not None
     assert g.lib().mm_kernel_name_bits_count.restype is ctypes.c_char_p
     for fn in ("bits_matmul_count", "bits_addmm_count_", "transpose_bits", "kernel_name_bits_count"):
         assert callable(getattr(g, fn)), fn
     ops = {k: int(v) for k, v in re.findall(r"MM_BITS_COUNT_(\w+)\s*=\s*(\d+)", HEADER)}
     assert ops == {"AND": 0, "XOR": 1} == {k.upper(): v for k, v in g.BITS_COUNT_OPS.items()}
-    assert "bits_count_variant" in HEADER and "bits_count_variant" in MAIN_HEADER
+    assert HEADER.count("bits_count_variant") >= 2     # where the calls are declared, and in the list of knobs
     assert "MM_BITS_COUNT_VARIANT" in open(os.path.join(ROOT, "gemm_hls_amd", "csrc", "mm_common.h")).read()
     assert g.get_tuning("bits_count_variant") == -1
     # the existing vocabularies are untouched: the packed calls take no mm_config_t
@@ -160,6 +141,7 @@ def test_bits_count_valid_calls_need_a_device():
 
 def test_kernel_name_bits_count_on_both_sides_of_the_serving_rule():
     name = g.kernel_name_bits_count
+    assert name(8, 40, 12) == "bits_count_plain"                        # ld defaulted: ceil(K / 32) words, M elements
     # the default rule: ceil(N / 128) ceil(M / 128) >= 256 tiles, lda % 4 == ldbt % 4 == ldc % 4 == 0
     assert name(2048, 128, 2048) == "bits_count_tile"                  # 16 x 16 tiles, ld = 4, 4, 2048
     assert name(1921, 128, 1921, ldc=1924) == "bits_count_tile"        # ... counted in started tiles
@@ -181,106 +163,6 @@ def test_kernel_name_bits_count_on_both_sides_of_the_serving_rule():
         with _Variant(bad):
             assert name(64, 64, 64) == "invalid"
     assert name(2048, 128, 2048) == "bits_count_tile"                  # the knob is restored
-
-
-# ---- the torch wrappers on the host: meta tensors that claim to live on a device, _enqueue replaced by a recorder ----------------
-torch = pytest.importorskip("torch")
-
-
-class Dev:
-    is_cuda = True
-
-    def __init__(self, t, ptr, device=None):
-        self.t, self.ptr = t, ptr
-        if device is not None:
-            self.device = device
-
-    def __getattr__(self, name):
-        return getattr(self.t, name)
-
-    def data_ptr(self):
-        return self.ptr
-
-
-def _t(ptr, *shape, strides=None, dtype=torch.int32, device=None):
-    x = torch.empty(shape, dtype=dtype, device="meta") if strides is None else torch.empty_strided(shape, strides, dtype=dtype, device="meta")
-    return Dev(x, ptr, device)
-
-
-@pytest.fixture
-def recorded(monkeypatch):
-    log = []
-    monkeypatch.setattr(g, "_enqueue", lambda device, fn, *args: log.append((fn.__name__, tuple(args))))
-    return log
-
-
-def test_binding_hands_over_what_the_tensors_say(recorded):
-    a, bt = _t(A0, 8, 2), _t(B0, 12, 2)
-    out = g.bits_matmul_count(a, bt, 40)
-    assert tuple(out.shape) == (8, 12) and out.dtype == torch.int32
-    assert recorded[-1][0] == "mm_bits_count_enqueue" and recorded[-1][1][0] == 0 and recorded[-1][1][1:3] == (A0, B0)
-    assert recorded[-1][1][4:] == (8, 40, 12, 2, 2, 12, 1, 0, 0, 0, 0)
-    # a column slice of whole words (row stride 5), a broadcast bt, a 3-D a, Xor, an out with its own row stride
-    a3 = _t(A0, 3, 8, 2, strides=(40, 5, 1))
-    bx = Dev(torch.empty((12, 2), dtype=torch.int32, device="meta").expand(3, 12, 2), B0)
-    c = _t(C0, 3, 8, 12, strides=(200, 16, 1))
-    assert g.bits_matmul_count(a3, bx, 64, op="Xor", out=c) is c
-    assert recorded[-1][1] == (1, A0, B0, C0, 8, 64, 12, 5, 2, 16, 3, 40, 0, 200, 0)
-    assert g.bits_addmm_count_(c, a3, bt, 33) is c
-    assert recorded[-1][1] == (0, A0, B0, C0, 8, 33, 12, 5, 2, 16, 3, 40, 0, 200, 1)
-    assert tuple(g.bits_matmul_count(a3, bt, 64).shape) == (3, 8, 12) and recorded[-1][1][9:] == (12, 3, 40, 0, 96, 0)
-    p = _t(A0, 3, 70, 6, strides=(500, 7, 1))
-    tp = g.transpose_bits(p, 130)
-    assert tuple(tp.shape) == (3, 130, 3)
-    assert recorded[-1][0] == "mm_bits_transpose_enqueue" and recorded[-1][1][0] == A0 and recorded[-1][1][2:] == (70, 130, 7, 3, 3, 500, 390)
-    o = _t(C0, 130, 4)
-    assert g.transpose_bits(_t(A0, 70, 5), 130, out=o) is o and recorded[-1][1] == (A0, C0, 70, 130, 5, 4, 1, 0, 0)
-    t4 = g.transpose_bits(_t(A0, 2, 3, 70, 5), 130)                # more batch dimensions: one flat batch of a dense copy
-    assert tuple(t4.shape) == (2, 3, 130, 3) and recorded[-1][1][2:] == (70, 130, 5, 3, 6, 350, 390)
-    assert g.kernel_name_bits_count(8, 40, 12) == "bits_count_plain"
-
-
-def test_binding_refusals_on_the_host(recorded):
-    a, bt, c = _t(A0, 8, 2), _t(B0, 12, 2), _t(C0, 8, 12)
-    both = (lambda *x, **kw: g.bits_matmul_count(*x, **kw), lambda *x, **kw: g.bits_addmm_count_(c, *x, **kw))
-    for call in both:
-        with pytest.raises(g.MMError, match="packed torch.int32"):
-            call(_t(A0, 8, 2, dtype=torch.int64), bt, 40)
-        with pytest.raises(g.MMError, match="packed torch.int32"):
-            call(a, _t(B0, 12, 2, dtype=torch.uint8), 40)
-        with pytest.raises(g.MMError, match=r"W >= 3"):          # k beyond 32 x the words present
-            call(a, bt, 65)
-        with pytest.raises(g.MMError, match=r"W >= 2"):          # mismatched inner words: bt has one
-            call(a, _t(B0, 12, 1), 40)
-        with pytest.raises(g.MMError, match="batch sizes differ"):
-            call(_t(A0, 3, 8, 2), _t(B0, 2, 12, 2), 40)
-        with pytest.raises(g.MMError, match="different devices"):
-            call(a, _t(B0, 12, 2, device=torch.device("cuda", 1)), 40)
-        with pytest.raises(g.MMError, match="op must be one of"):
-            call(a, bt, 40, op="Or")
-        with pytest.raises(g.MMError, match="2-D or 3-D"):
-            call(_t(A0, 2, 3, 8, 2), bt, 40)
-        with pytest.raises(g.MMError, match="contiguous"):
-            call(_t(A0, 8, 2, strides=(4, 2)), bt, 40)
-    with pytest.raises(g.MMError, match="device tensors"):
-        g.bits_matmul_count(torch.zeros(4, 1, dtype=torch.int32), torch.zeros(4, 1, dtype=torch.int32), 4)
-    with pytest.raises(g.MMError, match="device tensor"):
-        g.transpose_bits(torch.zeros(4, 1, dtype=torch.int32), 4)
-    with pytest.raises(g.MMError, match="torch.int32"):
-        g.bits_matmul_count(a, bt, 40, out=_t(C0, 8, 12, dtype=torch.float32))
-    with pytest.raises(g.MMError, match="expected"):
-        g.bits_matmul_count(a, bt, 40, out=_t(C0, 8, 13))
-    with pytest.raises(g.MMError, match="expected"):
-        g.bits_addmm_count_(c, _t(A0, 3, 8, 2), bt, 40)           # a batch of 3 into a 2-D c
-    with pytest.raises(g.MMError, match="would overlap"):
-        g.bits_addmm_count_(Dev(torch.empty((8, 12), dtype=torch.int32, device="meta").expand(3, 8, 12), C0), a, bt, 40)
-    with pytest.raises(g.MMError, match="packed torch.int32"):
-        g.transpose_bits(_t(A0, 70, 5, dtype=torch.int16), 130)
-    with pytest.raises(g.MMError, match=r"W >= 5"):
-        g.transpose_bits(_t(A0, 70, 4), 130)
-    with pytest.raises(g.MMError, match=r"W >= 3"):
-        g.transpose_bits(_t(A0, 70, 5), 130, out=_t(C0, 130, 2))
-    assert recorded == []                                          # nothing reached the C ABI
 
 
 def test_no_bits_count_kernel_uses_private_memory_or_agprs():

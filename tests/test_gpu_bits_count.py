@@ -8,75 +8,20 @@ import pytest
 
 import _bits_count_ref as cr
 import gemm_hls_amd as g
+from _bits_rig import Dev, _first_difference, _layout, _pattern, _poison_padding, _rows_of
+from _knobs import knob  # noqa: F401  (the fixture)
 
 pytestmark = pytest.mark.gpu
 
-GUARD = 8      # words of pattern in front of and behind every device buffer (32 bytes: the 16-byte alignment survives)
 SLAB = 256     # k per slab of both kernels (8 words)
-
-
-def _pattern(count, salt=0):
-    return ((np.arange(count, dtype=np.uint64) * 2654435761 + 0x9E3779B9 + salt) & 0xFFFFFFFF).astype(np.uint32)
-
-
-@pytest.fixture
-def knob():
-    """Sets tuning knobs for one test and restores them."""
-    old = {}
-
-    def set_(name, value):
-        old.setdefault(name, g.get_tuning(name))
-        g.set_tuning(name, value)
-    yield set_
-    for name, value in old.items():
-        g.set_tuning(name, value)
-
-
-class Dev:
-    """A host array of words on the device behind GUARD (+ shift) words of pattern; fetch() checks the guards."""
-    def __init__(self, words, shift=0):
-        import torch
-        self.shape, self.lead = words.shape, GUARD + shift
-        flat = np.concatenate([_pattern(self.lead, 1), words.reshape(-1).astype(np.uint32), _pattern(GUARD, 2)])
-        self.t = torch.from_numpy(flat.view(np.int32)).to("cuda:0")
-        self.ptr = self.t.data_ptr() + 4 * self.lead
-
-    def fetch(self):
-        out = self.t.cpu().numpy().view(np.uint32)
-        assert np.array_equal(out[:self.lead], _pattern(self.lead, 1)) and np.array_equal(out[-GUARD:], _pattern(GUARD, 2)), "guard overwritten"
-        return out[self.lead:-GUARD].reshape(self.shape)
-
-
-def _layout(rows_, ld, stride, fill):
-    """(batch, rows, w) words laid out with row stride ld and batch stride `stride` inside `fill`-valued words."""
-    batch, rows, w = rows_.shape
-    out = fill[:batch * stride].reshape(batch, stride).copy()
-    for r in range(rows):
-        out[:, r * ld:r * ld + w] = rows_[:, r]
-    return out
-
-
-def _rows_of(buf, rows, w, ld):
-    return np.stack([buf[:, r * ld:r * ld + w] for r in range(rows)], axis=1)
 
 
 def _pack(x):
     return cr.pack(x) if x.shape[-1] else np.zeros(x.shape[:-1] + (0,), np.uint32)
 
 
-def _poison_padding(packed, cols):
-    if cols % 32:
-        packed[..., -1] |= np.uint32((0xFFFFFFFF << (cols % 32)) & 0xFFFFFFFF)
-    return packed
-
-
 def _up4(x):
     return (x + 3) // 4 * 4
-
-
-def _first_difference(got, want):
-    idx = np.argwhere(got != want)
-    return f"{len(idx)} elements differ, the first at {idx[0]}: got {got[tuple(idx[0])]}, want {want[tuple(idx[0])]}" if len(idx) else ""
 
 
 def _assert_informative(ref, n, k, m):
@@ -120,7 +65,7 @@ def count(a, bt, op="And", seed=None, *, ld_extra=(0, 0, 0), shift=(0, 0, 0), po
     assert rc == 0, (rc, g.lib().mm_last_error().decode())
     got = dc.fetch()
     rows = _rows_of(got, n, m, ldc)
-    assert np.array_equal(rows.view(np.int32), want), _first_difference(rows.view(np.int32), want)
+    assert np.array_equal(rows.view(np.int32), want), _first_difference(rows.view(np.int32), want, "elements", "")
     assert np.array_equal(got, _layout(rows, ldc, sc, c_fill)), "a gap element of C was written"
     return want
 

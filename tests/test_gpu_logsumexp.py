@@ -12,6 +12,7 @@ import pytest
 
 import _lse_ref
 import gemm_hls_amd as g
+from _knobs import knob as knobs  # noqa: F401  (the fixture, under the name the tests here use)
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
@@ -25,19 +26,6 @@ def lse_variant():
     old = g.get_tuning("lse_variant")
     yield lambda v: g.set_tuning("lse_variant", v)
     g.set_tuning("lse_variant", old)
-
-
-@pytest.fixture
-def knobs():
-    """set(name, value) on the library's tuning knobs; every knob that was set gets its earlier value back."""
-    old = {}
-
-    def set_knob(name, value):
-        old.setdefault(name, g.get_tuning(name))
-        g.set_tuning(name, value)
-    yield set_knob
-    for name, value in old.items():
-        g.set_tuning(name, value)
 
 
 def _offset_view(x, shape, off):

@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 
 import gemm_hls_amd as g
+from _knobs import knob  # noqa: F401  (the fixture)
 from _product_ref import _check_bound, _f32_loop, _int_ref
 
 pytestmark = pytest.mark.gpu
@@ -23,19 +24,6 @@ INT32_MAX = 2 ** 31 - 1
 def _torch():
     import torch
     return torch, torch.device("cuda:0")
-
-
-@pytest.fixture
-def knob():
-    """Sets tuning knobs for one test and restores the previous values."""
-    old = {}
-
-    def set_(name, value):
-        old.setdefault(name, g.get_tuning(name))
-        g.set_tuning(name, value)
-    yield set_
-    for name, value in old.items():
-        g.set_tuning(name, value)
 
 
 # (dtype, (knob, value) or None, K x N A, (n, k, m), the kernel mm_kernel_name_widen must name): every "_wide" name and the

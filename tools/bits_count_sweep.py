@@ -12,16 +12,8 @@ the byte product alone on operands unpacked beforehand, "route" the same with bo
 region.  Bounds: "valu" = 2 lane-operations (one AND / XOR, one population count) per output and 32 k against 256 CUs x 128
 lanes x 2.4 GHz; "store" = the 4 N M bytes of C against 8 TB/s.  "of bound" is the larger of the two bounds over the best
 packed time.  Every packed result is compared with the byte route's (XOR through pop(a) + pop(bt) - 2 and)."""
-import argparse
-import json
-import os
-import sys
+from _bits_sweep import PEAK_LANE_OPS, _interleaved, _random_packed, _up4, g, sweep_main
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-import gemm_hls_amd as g  # noqa: E402
-
-PEAK_LANE_OPS = 256 * 128 * 2.4e9
 HBM_BYTES_PER_S = 8e12
 
 # (label, batch, n, k, m, op)
@@ -30,41 +22,6 @@ PRODUCTS += [("count_4096_cubed_and", 1, 4096, 4096, 4096, "And")]
 PRODUCTS += [(f"rule_{n}_k1024_and", 1, n, 1024, n, "And") for n in (1024, 2048, 4096)]      # 64, 256, 1024 tiles of 128 x 128
 PRODUCTS += [("batch16_1024_k1024_xor", 16, 1024, 1024, 1024, "Xor")]
 TRANSPOSES = [("transpose_16384", 16384, 16384)]
-
-
-def _timed(fn):
-    import torch
-    s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    s.record()
-    fn()
-    e.record()
-    e.synchronize()
-    return s.elapsed_time(e) * 1e-3
-
-
-def _interleaved(forms, reps):
-    """{name: (best, spread)} of callables timed in interleaved rounds after one warm-up each."""
-    for fn in forms.values():
-        fn()
-    times = {name: [] for name in forms}
-    for _ in range(reps):
-        for name, fn in forms.items():
-            times[name].append(_timed(fn))
-    return {name: (min(t), (max(t) - min(t)) / min(t)) for name, t in times.items()}
-
-
-def _up4(x):
-    return (x + 3) // 4 * 4
-
-
-def _random_packed(batch, rows, cols, seed):
-    """(batch, rows, words) packed bits of density 0.5 inside a tensor whose rows are a multiple of 4 words apart; the
-    padding bits are random too."""
-    import torch
-    gen = torch.Generator(device="cuda:0").manual_seed(seed)
-    w = g.bits_words(cols)
-    full = torch.randint(-(1 << 31), 1 << 31, (batch, rows, _up4(w)), dtype=torch.int64, device="cuda:0", generator=gen).to(torch.int32)
-    return full[:, :, :w]
 
 
 def _with_variant(v, fn):
@@ -128,46 +85,29 @@ def transposed(rows, cols, reps):
                 bytes_per_s=moved / t["packed"][0], agree=agree)
 
 
-def main():
-    ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
-    ap.add_argument("--reps", type=int, default=5)
-    ap.add_argument("--out-dir", default=os.path.join(ROOT, "profiles"))
-    ap.add_argument("--cases", default="", help="comma-separated labels (default: all)")
-    args = ap.parse_args()
+def cases(reps, wanted, emit, rows):
     import torch
-    want = set(args.cases.split(",")) if args.cases else None
-    rows, lines = [], []
-
-    def emit(line):
-        lines.append(line)
-        print(line, flush=True)
-
-    emit(f"best of {args.reps}, interleaved; spread = (max - min) / min of the {args.reps}; density 0.5; ms")
+    emit(f"best of {reps}, interleaved; spread = (max - min) / min of the {reps}; density 0.5; ms")
     emit(f"{'case':28s} {'tile':>9s} {'spread':>7s} {'plain':>9s} {'spread':>7s} {'int8':>9s} {'spread':>7s} {'route':>9s} {'spread':>7s} "
          f"{'valu bd':>8s} {'store bd':>8s} {'of bound':>8s} {'int8/pk':>8s} {'route/pk':>8s} {'same':>5s}  rule's kernel / int8 kernel")
     for label, batch, n, k, m, op in PRODUCTS:
-        if want and label not in want:
+        if not wanted(label):
             continue
-        r = product(batch, n, k, m, op, args.reps)
+        r = product(batch, n, k, m, op, reps)
         rows.append(dict(case=label, batch=batch, n=n, k=k, m=m, op=op, **r))
         emit(f"{label:28s} " + " ".join(f"{r[f + '_s'] * 1e3:9.3f} {r[f + '_spread']:6.1%}" for f in ("tile", "plain", "int8", "route")) +
              f" {r['valu_bound_s'] * 1e3:8.3f} {r['store_bound_s'] * 1e3:8.3f} {r['of_bound']:7.1%} {r['int8_over_packed']:7.2f}x "
              f"{r['route_over_packed']:7.2f}x {str(r['agree']):>5s}  {r['kernel']} / {r['int8_kernel']}")
         torch.cuda.empty_cache()
     for label, nrows, ncols in TRANSPOSES:
-        if want and label not in want:
+        if not wanted(label):
             continue
-        r = transposed(nrows, ncols, args.reps)
+        r = transposed(nrows, ncols, reps)
         rows.append(dict(case=label, rows=nrows, cols=ncols, **r))
         emit(f"{label:28s} packed {r['packed_s'] * 1e3:.3f} ms ({r['packed_spread']:.1%}), {r['bytes_per_s'] / 1e12:.3f} TB/s read + written; "
              f"unpack + transposed pack {r['route_s'] * 1e3:.3f} ms ({r['route_spread']:.1%}); same {r['agree']}")
         torch.cuda.empty_cache()
-    os.makedirs(args.out_dir, exist_ok=True)
-    with open(os.path.join(args.out_dir, "bits_count_sweep_mi355x.txt"), "w") as f:
-        f.write("\n".join(lines) + "\n")
-    with open(os.path.join(args.out_dir, "bits_count_sweep_mi355x.json"), "w") as f:
-        json.dump({"device": torch.cuda.get_device_name(0), "reps": args.reps, "rows": rows}, f, indent=1)
 
 
 if __name__ == "__main__":
-    main()
+    sweep_main(__doc__, "bits_count_sweep_mi355x", cases)

@@ -11,17 +11,9 @@ depends on the data: every product shape runs at the tests' density sqrt(ln 2 / 
 (nothing to skip).  "of peak" = n k ceil(m / 32) lane-operations -- one acc |= mask & b per lane per 32 outputs -- over the
 time, against 256 CUs x 128 lanes x 2.4 GHz.
 """
-import argparse
-import json
 import math
-import os
-import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-import gemm_hls_amd as g  # noqa: E402
-
-PEAK_LANE_OPS = 256 * 128 * 2.4e9
+from _bits_sweep import PEAK_LANE_OPS, _interleaved, _random_bits, g, sweep_main
 
 # (label, n, k, m, density or None for sqrt(ln 2 / k), accumulate)
 PRODUCTS = [
@@ -34,43 +26,6 @@ PRODUCTS = [
 ]
 # (label, n, byte form too)
 CLOSURES = [("closure_4096", 4096, True), ("closure_16384", 16384, True), ("closure_65536", 65536, False)]
-
-
-def _timed(fn):
-    import torch
-    s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    s.record()
-    fn()
-    e.record()
-    e.synchronize()
-    return s.elapsed_time(e) * 1e-3
-
-
-def _interleaved(forms, reps):
-    """{name: (best, spread)} of callables timed in interleaved rounds after one warm-up each."""
-    for fn in forms.values():
-        fn()
-    times = {name: [] for name in forms}
-    for _ in range(reps):
-        for name, fn in forms.items():
-            times[name].append(_timed(fn))
-    return {name: (min(t), (max(t) - min(t)) / min(t)) for name, t in times.items()}
-
-
-def _random_bits(rows, cols, p, seed):
-    """(bytes or None, packed) of a rows x cols Boolean matrix of density p, drawn on the device 4096 rows at a time."""
-    import torch
-    gen = torch.Generator(device="cuda:0").manual_seed(seed)
-    packed = torch.empty((rows, g.bits_words(cols)), dtype=torch.int32, device="cuda:0")
-    keep = rows * cols <= 1 << 28
-    byte = torch.empty((rows, cols), dtype=torch.uint8, device="cuda:0") if keep else None
-    for r0 in range(0, rows, 4096):
-        r1 = min(rows, r0 + 4096)
-        x = (torch.rand((r1 - r0, cols), device="cuda:0", generator=gen) < p).to(torch.uint8)
-        packed[r0:r1] = g.pack_bits(x)
-        if keep:
-            byte[r0:r1] = x
-    return byte, packed
 
 
 def product(n, k, m, density, accumulate, reps):
@@ -122,47 +77,30 @@ def closure(n, with_byte, reps):
     return out
 
 
-def main():
-    ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
-    ap.add_argument("--reps", type=int, default=5)
-    ap.add_argument("--out-dir", default=os.path.join(ROOT, "profiles"))
-    ap.add_argument("--cases", default="", help="comma-separated labels (default: all)")
-    args = ap.parse_args()
+def cases(reps, wanted, emit, rows):
     import torch
-    want = set(args.cases.split(",")) if args.cases else None
-    rows, lines = [], []
-
-    def emit(line):
-        lines.append(line)
-        print(line, flush=True)
-
-    emit(f"best of {args.reps}, interleaved; spread = (max - min) / min of the {args.reps}; the timed closures include one copy of their input")
+    emit(f"best of {reps}, interleaved; spread = (max - min) / min of the {reps}; the timed closures include one copy of their input")
     emit(f"{'case':30s} {'density':>8s} {'packed ms':>10s} {'spread':>7s} {'byte ms':>10s} {'spread':>7s} {'byte/packed':>11s} "
          f"{'of peak':>8s} {'out dens':>8s} {'same':>5s}  kernels")
     for label, n, k, m, density, accumulate in PRODUCTS:
-        if want and label not in want:
+        if not wanted(label):
             continue
-        r = product(n, k, m, density, accumulate, args.reps)
+        r = product(n, k, m, density, accumulate, reps)
         rows.append(dict(case=label, n=n, k=k, m=m, accumulate=accumulate, **r))
         emit(f"{label:30s} {r['density']:8.4f} {r['packed_s'] * 1e3:10.3f} {r['packed_spread']:6.1%} {r['byte_s'] * 1e3:10.3f} "
              f"{r['byte_spread']:6.1%} {r['ratio']:10.1f}x {r['of_peak']:7.1%} {r['output_density']:8.3f} {str(r['agree']):>5s}  "
              f"{r['kernel']} / {r['byte_kernel']}")
         torch.cuda.empty_cache()
     for label, n, with_byte in CLOSURES:
-        if want and label not in want:
+        if not wanted(label):
             continue
-        r = closure(n, with_byte, args.reps)
+        r = closure(n, with_byte, reps)
         rows.append(dict(case=label, n=n, **r))
         byte = (f"{r['byte_s'] * 1e3:10.3f} {r['byte_spread']:6.1%} {r['ratio']:10.1f}x" if with_byte else f"{'-':>10s} {'-':>7s} {'-':>11s}")
         emit(f"{label:30s} {1.5 / n:8.6f} {r['packed_s'] * 1e3:10.3f} {r['packed_spread']:6.1%} {byte} {'-':>8s} "
              f"{r['closure_density']:8.3f} {str(r.get('agree', '-')):>5s}  {r['kernel']} / {r.get('byte_kernel', '-')}")
         torch.cuda.empty_cache()
-    os.makedirs(args.out_dir, exist_ok=True)
-    with open(os.path.join(args.out_dir, "bits_sweep_mi355x.txt"), "w") as f:
-        f.write("\n".join(lines) + "\n")
-    with open(os.path.join(args.out_dir, "bits_sweep_mi355x.json"), "w") as f:
-        json.dump({"device": torch.cuda.get_device_name(0), "reps": args.reps, "rows": rows}, f, indent=1)
 
 
 if __name__ == "__main__":
-    main()
+    sweep_main(__doc__, "bits_sweep_mi355x", cases)
