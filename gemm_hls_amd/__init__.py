@@ -36,7 +36,7 @@ EXPORTS = ["mm_init", "mm_alloc", "mm_free", "mm_copy_to_device", "mm_copy_to_ho
            "mm_kernel_name_bits_gemm", "mm_bits_closure_enqueue", "mm_bits_closure_launch", "mm_kernel_name_bits_closure",
            "mm_bits_pack_enqueue", "mm_bits_pack_launch", "mm_bits_unpack_enqueue", "mm_bits_unpack_launch",
            "mm_bits_count_enqueue", "mm_bits_count_launch", "mm_kernel_name_bits_count", "mm_bits_transpose_enqueue",
-           "mm_bits_transpose_launch"]
+           "mm_bits_transpose_launch", "mm_device_max_grid_dim_y"]
 
 
 class MMError(RuntimeError):
@@ -124,6 +124,7 @@ def lib():
         L.mm_tuning_get.argtypes = [ctypes.c_char_p, ctypes.POINTER(i)]
         L.mm_release_workspace.argtypes = [i]
         L.mm_device_pci_bus_id.argtypes = [i, ctypes.c_char_p, i]
+        L.mm_device_max_grid_dim_y.argtypes = [i, ctypes.POINTER(i)]
         L.mm_row_slab.argtypes = shape + [i, i, ctypes.POINTER(u), ctypes.POINTER(u)]
         L.mm_widen_dtype.argtypes = [i]
         _lib = L
@@ -162,6 +163,13 @@ def device_count():
     n = ctypes.c_int(0)
     _check(lib().mm_init(ctypes.byref(n)))
     return n.value
+
+
+def device_max_grid_dim_y(device=0):
+    """The largest gridDim.y HIP device `device` launches (mm_device_max_grid_dim_y)."""
+    v = ctypes.c_int(0)
+    _check(lib().mm_device_max_grid_dim_y(int(device), ctypes.byref(v)))
+    return v.value
 
 
 def _kernel_name(suffix, cfg, *args):

@@ -1475,6 +1475,14 @@ int mm_device_pci_bus_id(int device, char *buffer, int length) {
   return MM_OK;
 }
 
+int mm_device_max_grid_dim_y(int device, int *value) {
+  int rc = check_device(device);
+  if (rc) return rc;
+  if (!value) return fail(MM_ERR_BAD_ARGUMENT, "mm_device_max_grid_dim_y needs a place for the value");
+  MM_HIP(hipDeviceGetAttribute(value, hipDeviceAttributeMaxGridDimY, device));
+  return MM_OK;
+}
+
 int mm_copy_to_device(int device, void *dst, const void *src, size_t bytes) {
   int rc = check_device(device);
   if (rc) return rc;

@@ -140,6 +140,10 @@ int mm_release_workspace(int device);
  * power meter (the reference's PowerMeter role, host/RunHardware.cpp:156-172). */
 int mm_device_pci_bus_id(int device, char *buffer, int length);
 
+/* The largest gridDim.y HIP device `device` launches (hipDeviceAttributeMaxGridDimY): the limit the 2-D launches of this
+ * library stay under -- taller problems go to 1-D grids -- and the one its tests cross. */
+int mm_device_max_grid_dim_y(int device, int *value);
+
 int mm_copy_to_device(int device, void *device_dst, const void *host_src, size_t bytes);
 int mm_copy_to_host(int device, void *host_dst, const void *device_src, size_t bytes);
 

@@ -599,6 +599,7 @@ EXPECTED_PROTOTYPES = {
     "mm_tuning_get": "i <- str i*",
     "mm_release_workspace": "i <- i",
     "mm_device_pci_bus_id": "i <- i str i",
+    "mm_device_max_grid_dim_y": "i <- i i*",
     "mm_row_slab": "i <- cfg* u u u i i u* u*",
     "mm_gemm_multi_device_timed": f"i <- i {GEMM} d* d* d*",
     "mm_gemm_batched_enqueue": f"i <- vp {BATCHED}",
