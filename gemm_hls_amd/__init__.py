@@ -37,6 +37,9 @@ EXPORTS = ["mm_init", "mm_alloc", "mm_free", "mm_copy_to_device", "mm_copy_to_ho
            "mm_bits_pack_enqueue", "mm_bits_pack_launch", "mm_bits_unpack_enqueue", "mm_bits_unpack_launch",
            "mm_bits_count_enqueue", "mm_bits_count_launch", "mm_kernel_name_bits_count", "mm_bits_transpose_enqueue",
            "mm_bits_transpose_launch", "mm_device_max_grid_dim_y"]
+# what include/mm_bits_gf2.h declares (included by mm_gemm.h; asserted by tests/test_bits_gf2_capi.py).  A list of its own:
+# EXPORTS is pinned, symbol for symbol, against mm_gemm.h's own declarations and a literal prototype table
+BITS_GF2_EXPORTS = ["mm_bits_gf2_enqueue", "mm_bits_gf2_launch", "mm_kernel_name_bits_gf2"]
 
 
 class MMError(RuntimeError):
@@ -97,13 +100,14 @@ def lib():
                  "mm_closure": [cfgp, vp, vp, u, u, sz], "mm_bits_gemm": [vp, vp, vp, u, u, u, sz, sz, sz, u, sz, sz, sz, i],
                  "mm_bits_closure": [vp, u, sz, u, sz], "mm_bits_pack": convert, "mm_bits_unpack": convert,
                  "mm_bits_count": [i, vp, vp, vp, u, u, u, sz, sz, sz, u, sz, sz, sz, i], "mm_bits_transpose": convert}
+        pairs["mm_bits_gf2"] = pairs["mm_bits_gemm"]
         for stem, between in pairs.items():
             getattr(L, stem + "_enqueue").argtypes = [vp] + between
             getattr(L, stem + "_launch").argtypes = [i] + between + [dp]
         # mm_kernel_name<suffix>(...): a string
         shape = [cfgp, u, u, u]
         names = {"": shape, "_closure": [cfgp, u, u, i], "_bits_gemm": [u, u, u, sz, sz, sz, u], "_bits_closure": [u, u],
-                 "_bits_count": [u, u, u, sz, sz, sz, u]}
+                 "_bits_count": [u, u, u, sz, sz, sz, u], "_bits_gf2": [u, u, u, sz, sz, sz, u]}
         names.update((suffix, shape + [u]) for suffix in ("_batched", "_argreduce", "_logsumexp", "_widen", "_nt", "_argreduce_nt",
                                                           "_logsumexp_nt"))
         for suffix, args in names.items():
@@ -744,6 +748,25 @@ def bits_addmm_(c, a, b, k, m):
     (N, Wm) or (B, N, Wm) packed torch.int32 with its own row stride, not overlapping a or b.  Two calls on the halves of K
     equal one call on all of it.  Returns c.  Asynchronous."""
     return _packed_product("bits_addmm_", "mm_bits_gemm_enqueue", a, b, k, m, c=c)
+
+
+def kernel_name_bits_gf2(n, k, m, lda=None, ldb=None, ldc=None, batch=1):
+    """Name of the kernel bits_matmul_gf2 / bits_addmm_gf2_ run; the row strides (words) default to the rows' own word counts."""
+    lda, ldb, ldc = (bits_words(c) if ld is None else ld for ld, c in ((lda, k), (ldb, m), (ldc, m)))
+    return lib().mm_kernel_name_bits_gf2(n, k, m, lda, ldb, ldc, batch).decode()
+
+
+def bits_matmul_gf2(a, b, k, m, out=None):
+    """Packed product over GF(2) on torch's current stream (mm_bits_gf2_enqueue): C[i][j] = XOR_k (A[i][k] AND B[k][j]).
+    Operands, k, m, out and the result are those of bits_matmul; padding bits of a and b are ignored whatever they hold,
+    those of the result are 0.  Asynchronous."""
+    return _packed_product("bits_matmul_gf2", "mm_bits_gf2_enqueue", a, b, k, m, out=out)
+
+
+def bits_addmm_gf2_(c, a, b, k, m):
+    """In place C <- C ^ A B on torch's current stream (mm_bits_gf2_enqueue, accumulate); operands as for bits_addmm_.  Two
+    calls on the halves of K equal one call on all of it; the same call twice restores c.  Returns c.  Asynchronous."""
+    return _packed_product("bits_addmm_gf2_", "mm_bits_gf2_enqueue", a, b, k, m, c=c)
 
 
 def bits_closure_(d, n=None):

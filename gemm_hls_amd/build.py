@@ -100,7 +100,7 @@ def build(verbose=True):
     os.makedirs(OBJ, exist_ok=True)
     os.makedirs(BIN, exist_ok=True)
     headers = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".h", ".inc"))]
-    headers.append(os.path.join(ROOT, "include", "mm_gemm.h"))
+    headers += [os.path.join(ROOT, "include", h) for h in ("mm_gemm.h", "mm_bits_gf2.h")]
     sources = sorted(f for f in os.listdir(CSRC) if f.endswith(".hip"))
     jobs = []
     objs = []
@@ -121,7 +121,7 @@ def build(verbose=True):
     host_jobs = []
     shim_jobs = []
     host_hdrs = [os.path.join(host_dir, f) for f in os.listdir(host_dir) if f.endswith(".h")] + [
-        os.path.join(ROOT, "include", "mm_gemm.h")]
+        os.path.join(ROOT, "include", "mm_gemm.h"), os.path.join(ROOT, "include", "mm_bits_gf2.h")]
     rpath = "-Wl,-rpath,$ORIGIN/../gemm_hls_amd:$ORIGIN"
     cxx = "/opt/rocm/lib/llvm/bin/clang++"  # amdclang++ (not g++): the host needs _Float16 for MM_DATA_TYPE=half
     common = [cxx, "-O2", "-std=c++17", "-pthread", "-I" + os.path.join(ROOT, "include"), "-I" + host_dir]

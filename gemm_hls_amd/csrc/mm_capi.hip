@@ -92,11 +92,12 @@ std::atomic<int> g_tuning[mm::TUNE_COUNT];
 const char *const kTuneName[mm::TUNE_COUNT] = {"f32_variant", "f64_variant", "f16_variant", "i8_variant", "band_rows",
                                                "valu_variant", "split_variant", "f32_splitk", "ablations", "debug_poison", "kxn_prepass_min_m",
                                                "md_virtual_devices", "ordered_variant", "half_contract", "batch_chunk",
-                                               "closure_block", "lse_variant", "bits_variant", "bits_count_variant"};
+                                               "closure_block", "lse_variant", "bits_variant", "bits_count_variant", "bits_gf2_variant"};
 const char *const kTuneEnv[mm::TUNE_COUNT] = {"MM_F32_VARIANT", "MM_F64_VARIANT", "MM_F16_VARIANT", "MM_I8_VARIANT",
                                               "MM_BAND_ROWS", "MM_VALU_VARIANT", "MM_SPLIT_VARIANT", "MM_F32_SPLITK", "MM_ABLATIONS", "MM_DEBUG_POISON", "MM_KXN_PREPASS_MIN_M",
                                               "MM_MD_VIRTUAL_DEVICES", "MM_ORDERED_VARIANT", "MM_HALF_CONTRACT", "MM_BATCH_CHUNK",
-                                              "MM_CLOSURE_BLOCK", "MM_LSE_VARIANT", "MM_BITS_VARIANT", "MM_BITS_COUNT_VARIANT"};
+                                              "MM_CLOSURE_BLOCK", "MM_LSE_VARIANT", "MM_BITS_VARIANT", "MM_BITS_COUNT_VARIANT",
+                                              "MM_BITS_GF2_VARIANT"};
 void tuning_init() {
   for (int i = 0; i < mm::TUNE_COUNT; ++i) {
     const char *e = getenv(kTuneEnv[i]);
@@ -678,7 +679,14 @@ BitsKernel bits_count_kernel_for(unsigned n, unsigned m, size_t lda, size_t ldbt
   return bits_kernel_by_knob(mm::TUNE_BITS_COUNT_VARIANT, mm::bits_count_tile_serves(lda, ldbt, ldc), tiles >= kBitsCountTileMin);
 }
 
-// What is a packed product's own in its argument checks; everything else the two products share (check_bits_product).
+constexpr unsigned kBitsGf2TileMin = 128;    // N and M from which bits_gf2_tile serves (profiles/bits_gf2_sweep_mi355x.txt)
+
+// The kernel by shape, ld and knob alone (mm_kernel_name_bits_gf2).
+BitsKernel bits_gf2_kernel_for(unsigned n, unsigned m, size_t ldb, size_t ldc) {
+  return bits_kernel_by_knob(mm::TUNE_BITS_GF2_VARIANT, mm::bits_gf2_tile_serves(ldb, ldc), n >= kBitsGf2TileMin && m >= kBitsGf2TileMin);
+}
+
+// What is a packed product's own in its argument checks; everything else the three products share (check_bits_product).
 struct BitsProduct {
   mm::Tunable knob;        // the knob of its kernels
   BitsKernel ker;          // its kernel by shape, ld and knob
@@ -693,6 +701,14 @@ BitsProduct bits_gemm_rules(const mm::BitsProblem &p) {
   const size_t mw = bits_words(p.m);
   return {mm::TUNE_BITS_VARIANT, bits_kernel_for(p.m, p.ldb, p.ldc), p.k, mw, mw, {0, 16, 8}, "b", "ceil(M / 32)",
           "a row stride is below its row's words: lda %zu (needs %zu), ldb %zu (%zu), ldc %zu (%zu)"};
+}
+
+BitsProduct bits_gf2_rules(const mm::BitsProblem &p) {   // the Boolean product's operands and texts; its own knob and kernels
+  BitsProduct r = bits_gemm_rules(p);
+  r.knob = mm::TUNE_BITS_GF2_VARIANT;
+  r.ker = bits_gf2_kernel_for(p.n, p.m, p.ldb, p.ldc);
+  r.align[1] = 8;   // bits_gf2_tile's accesses of B and of C are 8 bytes wide
+  return r;
 }
 
 BitsProduct bits_count_rules(const mm::BitsProblem &p) {   // p.b: Bt, M x K
@@ -761,6 +777,13 @@ int dispatch_bits_gemm(hipStream_t s, const mm::BitsProblem &p, BitsKernel ker) 
   return for_each_bits_chunk(p, (unsigned long long)((p.n + 63) / 64) * ((bits_words(p.m) + 63) / 64), [&](const mm::BitsProblem &q) {
     const int e = mm::launch_bits_gemm(s, q, ker == BITS_TILE);
     return e ? hip_fail((hipError_t)e, "packed product kernel launch") : MM_OK;
+  });
+}
+
+int dispatch_bits_gf2(hipStream_t s, const mm::BitsProblem &p, BitsKernel ker) {   // tiles of 64 x 64 words (bits_gf2_tile's are larger)
+  return for_each_bits_chunk(p, (unsigned long long)((p.n + 63) / 64) * ((bits_words(p.m) + 63) / 64), [&](const mm::BitsProblem &q) {
+    const int e = mm::launch_bits_gf2(s, q, ker == BITS_TILE);
+    return e ? hip_fail((hipError_t)e, "packed GF(2) product kernel launch") : MM_OK;
   });
 }
 
@@ -1297,6 +1320,12 @@ int run_bits_gemm(const Target &t, const mm::BitsProblem &p) {
   return run(t, ker == BITS_NONE, [&](hipStream_t s) { return dispatch_bits_gemm(s, p, ker); });
 }
 
+int run_bits_gf2(const Target &t, const mm::BitsProblem &p) {
+  BitsKernel ker;
+  if (int rc = check_bits_product(p, bits_gf2_rules(p), &ker)) return rc;
+  return run(t, ker == BITS_NONE, [&](hipStream_t s) { return dispatch_bits_gf2(s, p, ker); });
+}
+
 int run_bits_count(const Target &t, int op, const mm::BitsProblem &p) {
   BitsKernel ker;
   if (int rc = check_bits_count(op, p, &ker)) return rc;
@@ -1660,6 +1689,19 @@ int mm_bits_gemm_launch(int device, const void *a, const void *b, void *c, unsig
                         double *elapsed_seconds) {
   return run_bits_gemm(timed_on(device, elapsed_seconds), {(const uint32_t *)a, (const uint32_t *)b, (uint32_t *)c, n, k, m, lda, ldb,
                                                            ldc, batch, stride_a, stride_b, stride_c, accumulate != 0});
+}
+
+int mm_bits_gf2_enqueue(void *hip_stream, const void *a, const void *b, void *c, unsigned n, unsigned k, unsigned m, size_t lda,
+                        size_t ldb, size_t ldc, unsigned batch, size_t stride_a, size_t stride_b, size_t stride_c, int accumulate) {
+  return run_bits_gf2(on_stream(hip_stream), {(const uint32_t *)a, (const uint32_t *)b, (uint32_t *)c, n, k, m, lda, ldb, ldc, batch,
+                                              stride_a, stride_b, stride_c, accumulate != 0});
+}
+
+int mm_bits_gf2_launch(int device, const void *a, const void *b, void *c, unsigned n, unsigned k, unsigned m, size_t lda, size_t ldb,
+                       size_t ldc, unsigned batch, size_t stride_a, size_t stride_b, size_t stride_c, int accumulate,
+                       double *elapsed_seconds) {
+  return run_bits_gf2(timed_on(device, elapsed_seconds), {(const uint32_t *)a, (const uint32_t *)b, (uint32_t *)c, n, k, m, lda, ldb,
+                                                          ldc, batch, stride_a, stride_b, stride_c, accumulate != 0});
 }
 
 int mm_bits_closure_enqueue(void *hip_stream, void *d, unsigned n, size_t ldd, unsigned batch, size_t stride_d) {
@@ -2105,6 +2147,15 @@ const char *mm_kernel_name_bits_gemm(unsigned n, unsigned k, unsigned m, size_t 
     case BITS_TILE: return "bits_tile";
     case BITS_INVALID: return "invalid";
     default: return "bits_plain";
+  }
+}
+
+const char *mm_kernel_name_bits_gf2(unsigned n, unsigned k, unsigned m, size_t lda, size_t ldb, size_t ldc, unsigned batch) {
+  (void)k, (void)lda, (void)batch;
+  switch (bits_gf2_kernel_for(n, m, ldb, ldc)) {   // the choice bits_gf2_rules makes, before alignment
+    case BITS_TILE: return "bits_gf2_tile";
+    case BITS_INVALID: return "invalid";
+    default: return "bits_gf2_plain";
   }
 }
 

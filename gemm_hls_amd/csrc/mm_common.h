@@ -193,6 +193,11 @@ struct BitsProblem {
 };
 bool bits_tile_serves(size_t ldb, size_t ldc);   // the ld half of the serving rule; the M half is mm_capi.hip's (a knob lifts it)
 int launch_bits_gemm(hipStream_t s, const BitsProblem &p, bool tile);
+// Bit-packed product over GF(2) (mm_bits_gf2_*, mm_bits_gf2.hip): BitsProblem as for launch_bits_gemm; seed: C <- C ^ A B.
+// tile: "bits_gf2_tile" (bits_gf2_tile_serves() on the ld's, b and c 8-byte aligned per element), else
+// "bits_gf2_plain" (anything).
+bool bits_gf2_tile_serves(size_t ldb, size_t ldc);   // the ld half of the serving rule; the shape half is mm_capi.hip's (a knob lifts it)
+int launch_bits_gf2(hipStream_t s, const BitsProblem &p, bool tile);
 // pack: src bytes -> dst words; unpack: src words -> dst bytes (0 / 1).  ld and batch strides in each side's own unit.
 struct BitsConvert {
   const void *src;
@@ -414,6 +419,8 @@ enum Tunable {
                            //                 -1: the default (bits_tile for M > 2048)
   TUNE_BITS_COUNT_VARIANT, // MM_BITS_COUNT_VARIANT  mm_bits_count_*: 0 bits_count_plain always, 1 bits_count_tile wherever its ld rule
                            //                 holds (any shape); -1: the default (bits_count_tile from 256 tiles of 128 x 128)
+  TUNE_BITS_GF2_VARIANT,   // MM_BITS_GF2_VARIANT  mm_bits_gf2_*: 0 bits_gf2_plain always, 1 bits_gf2_tile wherever its ld rule holds (any
+                           //                 shape); -1: the default (bits_gf2_tile from N >= 128 and M >= 128)
   TUNE_COUNT
 };
 int tuning(Tunable t);  // mm_capi.hip

@@ -537,6 +537,9 @@ int mm_bits_gemm_launch(int device, const void *a_dev, const void *b_dev, void *
 const char *mm_kernel_name_bits_gemm(unsigned size_n, unsigned size_k, unsigned size_m, size_t lda, size_t ldb, size_t ldc,
                                      unsigned batch);
 
+/* Product over the field GF(2), C = XOR_k (A AND B) on this format (mm_bits_gf2_*): "mm_bits_gf2.h", a header of its own,
+ * included at the end of this one. */
+
 /* Transitive closure, in place: D <- D+, (i, j) set when a path of one or more edges leads from i to j.  No identity is
  * added to the diagonal, as in mm_closure_*.  OR is idempotent, so the result does not depend on the algorithm.  d: n x n
  * packed, row stride ldd >= ceil(n / 32) words; graph e at d_dev + e * stride_d (stride_d >= (n - 1) ldd + ceil(n / 32)
@@ -711,6 +714,7 @@ int mm_kernel_info(const mm_config_t *cfg, unsigned size_n, unsigned size_k, uns
  * single ranges with its own fix-up kernel (cross-check, its own bits).
  * "closure_block": the block size of mm_closure_* (see there).  "lse_variant": the kernels of mm_gemm_logsumexp_* (see there).
  * "bits_variant": the kernels of mm_bits_gemm_* (see there).  "bits_count_variant": the kernels of mm_bits_count_* (see there).
+ * "bits_gf2_variant": the kernels of mm_bits_gf2_* (see there).
  * "debug_poison" = 1 fills the scratch that kernels hand partial tiles through, and C itself (pure output), with NaN before
  * every stream-K launch: a read of anything the launch did not write, or a tile nobody finished, then shows in C (tests only).  "md_virtual_devices": see mm_gemm_multi_device.  Any
  * other id is refused: the retired schedules and the work-skipping ablations of the measurement history exist only in the
@@ -727,4 +731,5 @@ const char *mm_last_error(void);
 #ifdef __cplusplus
 }
 #endif
+#include "mm_bits_gf2.h"
 #endif /* MM_GEMM_H */
